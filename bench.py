@@ -2,17 +2,29 @@
 """Headline benchmark: training images/sec of hierarchical HRNet-W48 at 620x620 on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--model hrnet|unet] [--batch B] [--size S]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = the reference's train-loop batch body (train.py:179-248) on one synthetic batch: forward
 of the L level passes, prediction prep + metrics, CE+Dice+consistency loss, backward, gradient
 all-reduce, AdamW, the per-class metric vectors and the ONE device->host readback of loss + metrics;
-the batch is resident in HBM when the timed region starts (`value`).  The same body fed from pinned
-host memory (H2D copy inside the timed step) is measured next to it (`batch_body_from_host`).
-N>1: one rank per GPU over RCCL, every rank on its own 4-image shard (weak scaling), rank 0 prints ONE
-JSON line.  `python bench.py --gpus N` starts its own N ranks (torch.distributed.run as a child
-process, before this process touches the GPU); under torchrun (WORLD_SIZE set) it is a rank itself.
+the batch is resident in HBM when the timed region starts (`value`, `ms_per_step`: K timed steps after
+W warm-up steps).  N>1: one rank per GPU over RCCL, every rank on its own 4-image shard (weak scaling),
+rank 0 prints ONE JSON line.  `python bench.py --gpus N` starts its own N ranks (torch.distributed.run
+as a child process, before this process touches the GPU); under torchrun (WORLD_SIZE set) it is a rank itself.
 
-Extra objects in that line:
+A plain run sets up, warms up, times the K steps, writes the outputs (--dump-outputs) and prints the line.
+--dump-outputs DIR: after the timed steps, what the last of them computed as DIR/<name>.npy (float32 / float64):
+  loss, metric_<name> (per-class accuracy / iou / dice / precision / recall) and confusion_level<L>, what the step
+  returns to its caller.  The inputs and the initial state are seeded and the last timed step restarts from that state,
+  so every run writes the same outputs and two builds can be compared output for output.
+
+--full adds everything else, measured after the headline (the opt-in lines, the probes and the CPU baseline each
+skippable by its --no-* flag):
+  batch_body_from_host -- the same body fed from pinned host memory (H2D copy inside the timed step)
+  ms_per_step_no_readback, host_issue_ms, conv_launches_per_step -- the step without its readback, the host time
+                  to issue it and the library's conv launches per step by kernel family
+  gradient_exchange -- N>1: the exchange alone and each bucket's overlap with the reverse pass
+  opt_in_dedup_passes, opt_in_bf16_convs, exact_f32_convs -- the same step in the opt-in modes (N=1)
   roofline     -- the dominant kernel (wave-specialised halo-patch 3x3 convolution of the parallel HRNet branches,
                   fp16x2 on the 16-bit matrix pipe): algorithmic FLOPs per launch / average launch time measured
                   here with events on the launch stream; `roofline_other` the next kernel families
@@ -88,6 +100,10 @@ def parse():
     ap.add_argument("--comm-only", action="store_true",
                     help="time ONLY the gradient exchange of a step (the bucketed all-reduce of the flat gradient buffer, "
                          "as GradSync issues it) on N ranks: compute and exchange can then be read apart in a scaling run")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the side lines, the kernel probes and the CPU baseline (off: the headline only)")
     return ap.parse_args()
 
 
@@ -437,6 +453,23 @@ def comm_only(args, model, sync, rank, world, device):
             "busbw_GBps": r["busbw_GBps"], "backend": r["backend"], "note": r["note"]}), flush=True)
 
 
+def dump_outputs(out_dir, last):
+    """--dump-outputs: what the last timed step returned (loss, metric vectors, confusion matrices), one float .npy per
+    array"""
+    import numpy as np
+    from hrseg_amd.Metrics.performance_metrics import METRIC_NAMES
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": np.array([last["loss"]], dtype=np.float64)}
+    for name, row in zip(METRIC_NAMES, last["metrics"]):
+        arrays["metric_" + name] = np.asarray(row.cpu() if torch.is_tensor(row) else row, dtype=np.float64)
+    for L, cm in enumerate(last["cms"]):
+        arrays["confusion_level%d" % L] = cm.cpu().numpy().astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sum(a.nbytes for a in arrays.values())
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -452,6 +485,7 @@ def main():
     device = torch.device("cuda", local)
     torch.cuda.set_device(device)
     tree, model, ns, loss_fns, opt = build(args, device)
+    initial = {k: v.detach().clone() for k, v in model.state_dict().items()}     # the seeded initial state
     sync = None
     if world > 1 or os.environ.get("HRSEG_FORCE_SYNC", "0") == "1":
         if os.environ.get("HRSEG_COMM", "torch") == "rccl":       # the library's own RCCL wrappers (hrseg_comm_*)
@@ -491,17 +525,22 @@ def main():
         torch.cuda.empty_cache()
         state["taped"] = T.TapedTrainStep(model, opt, loss_fns, ns, tree, x, t)
 
+    last = {}                                 # what the latest step returned (--dump-outputs)
+
     def body(xd, td):
         """the batch body of train_epoch (train.py:179-248): step, metric vectors, ONE device->host copy"""
         if state["taped"] is not None:
-            packed, _ = state["taped"](xd, td)
-            return state["taped"].unpack(packed.tolist())[0]
+            packed, cms = state["taped"](xd, td)
+            loss, _, rows = state["taped"].unpack(packed.tolist())
+            last.update(loss=loss, metrics=rows, cms=cms)
+            return loss
         if state["graphed"] is not None:
             loss, cms = state["graphed"](xd, td)
         else:
             loss, cms = T.train_step(model, opt, xd, td, loss_fns, ns, tree, level_loss)
         vec = T._metric_vectors(cms)
         host = torch.cat([loss.reshape(1)] + [vec[k] for k in METRIC_NAMES]).tolist()
+        last.update(loss=host[0], metrics=[vec[k] for k in METRIC_NAMES], cms=cms)
         return host[0]
 
     def step():
@@ -563,13 +602,34 @@ def main():
         torch.cuda.synchronize()
         log("warmup step %d: %.3f s, loss %.5f, peak mem %.1f GB" % (i, time.perf_counter() - tw, float(loss),
                                                                     torch.cuda.max_memory_allocated() / 2**30))
-    dt, final_loss = timed(step, args.steps)
-    dt_host, _ = timed(step_from_host, args.steps)
-    dt_async, _ = timed(step_async, args.steps)
-    host_ms, launches = host_issue()
-    log("host issue %.1f ms per step (%s); conv launches per step %s" % (host_ms, launch_mode(), launches))
+    def restore_initial_state():
+        """the seeded initial parameters and BatchNorm buffers, zero AdamW moments and step count, written in place (a
+        recorded tape or graph holds their addresses)"""
+        with torch.no_grad():
+            model.load_state_dict(initial)
+            for buf in (opt._m, opt._v, opt._state):
+                if buf is not None:
+                    buf.zero_()
+        opt._step = 0
+        model.notify_parameters_changed()
+
+    # The last timed step starts again from the seeded initial state (restored outside the timed region).  Every step adds
+    # its gradients and BatchNorm statistics with atomics in a run-dependent order; over a run's AdamW steps that drift grows
+    # far past rounding.  Restarted, the last step computes the same outputs from the same inputs in every run.
+    dt, final_loss = timed(step, args.steps - 1) if args.steps > 1 else (0.0, None)
+    restore_initial_state()
+    dt_last, final_loss = timed(step, 1)
+    dt += dt_last
+    if args.dump_outputs and rank == 0:
+        nbytes = dump_outputs(args.dump_outputs, last)
+        log("outputs of the last timed step: %.1f KB under %s" % (nbytes / 2**10, args.dump_outputs))
+    if args.full:
+        dt_host, _ = timed(step_from_host, args.steps)
+        dt_async, _ = timed(step_async, args.steps)
+        host_ms, launches = host_issue()
+        log("host issue %.1f ms per step (%s); conv launches per step %s" % (host_ms, launch_mode(), launches))
     exchange = None
-    if sync is not None:
+    if args.full and sync is not None:
         # what a scaling run needs to be read: the exchange alone (same job, same buckets), each bucket's overlap with the
         # reverse pass (events), and the slowest rank's host issue time
         sync.timing = True
@@ -608,24 +668,29 @@ def main():
                        "comm": (None if sync is None else
                                 "hrseg_comm_* (the library's own RCCL wrappers, HRSEG_COMM=rccl)" if sync.backend == "rccl" else
                                 "torch.distributed all_reduce (HRSEG_COMM=torch, default)")},
-            "batch_body_from_host": {"value": round(world * args.batch * args.steps / dt_host, 3), "unit": "images/s",
-                                     "ms_per_step": round(1e3 * dt_host / args.steps, 2),
-                                     "note": "same body with the batch copied from pinned host memory inside the timed "
-                                             "step (train.py:181); never the headline value"},
-            "ms_per_step_no_readback": round(1e3 * dt_async / args.steps, 2),
-            "host_issue_ms": host_ms, "conv_launches_per_step": launches,
         }
+        if args.full:
+            line.update({
+                "batch_body_from_host": {"value": round(world * args.batch * args.steps / dt_host, 3), "unit": "images/s",
+                                         "ms_per_step": round(1e3 * dt_host / args.steps, 2),
+                                         "note": "same body with the batch copied from pinned host memory inside the timed "
+                                                 "step (train.py:181); never the headline value"},
+                "ms_per_step_no_readback": round(1e3 * dt_async / args.steps, 2),
+                "host_issue_ms": host_ms, "conv_launches_per_step": launches})
         if exchange is not None:
             line["gradient_exchange"] = exchange
         if gf is not None and args.size == 620:
             tf = ips * gf / 1e3
             line["step_conv_roofline"] = {"train_gflop_per_image": gf, "achieved_tflops": round(tf, 2),
                                           "frac_of_fp32_mfma_peak": round(tf / (world * FP32_MFMA_PEAK_TFLOPS), 4)}
-        log("timed: %.3f s for %d steps (resident), %.3f s (from host), %.3f s (no readback)" % (dt, args.steps, dt_host, dt_async))
+        if args.full:
+            log("timed: %.3f s for %d steps (resident), %.3f s (from host), %.3f s (no readback)" % (dt, args.steps, dt_host, dt_async))
+        else:
+            log("timed: %.3f s for %d steps (resident)" % (dt, args.steps))
         line["config"]["level_passes"] = ("sequential" if getattr(model, "sequential_passes", False) else
                                           "batched (one launch per layer for all L passes)") if hier else "n/a"
         graphed = state["graphed"]
-        if world == 1 and hier and graphed is None and not args.no_dedup_line:
+        if args.full and world == 1 and hier and graphed is None and not args.no_dedup_line:
             # NOT the headline number: the opt-in mode that runs the L bit-identical level passes once
             # (Models/models.py:_run).  Same result, 1/L of the backbone FLOPs executed -- reported apart.
             model.dedup_passes = True
@@ -642,7 +707,7 @@ def main():
                 "note": "explicit opt-in (model.dedup_passes / HRSEG_DEDUP_PASSES=1); the default and headline value "
                         "execute all L passes"}
             log("opt-in dedup passes: %.1f ms/step" % (1e3 * td / args.steps))
-        if world == 1 and graphed is None and not args.no_bf16_line and hasattr(model, "conv_dtype"):
+        if args.full and world == 1 and graphed is None and not args.no_bf16_line and hasattr(model, "conv_dtype"):
             # NOT the headline: bf16-input / fp32-accumulate convolutions (BASELINE configs[4] arithmetic), opt-in
             prev = model.conv_dtype
             model.conv_dtype = "bf16"
@@ -658,7 +723,7 @@ def main():
                 "dtype": "bf16 inputs, fp32 accumulate (convolutions only; BN, loss, optimizer fp32)",
                 "note": "explicit opt-in (model.conv_dtype='bf16'): results differ from the fp32 reference beyond 1e-3"}
             log("opt-in bf16 convs: %.1f ms/step" % (1e3 * tb / args.steps))
-        if world == 1 and graphed is None and not args.no_f32_line and hasattr(model, "conv_dtype") and conv_dtype != "f32":
+        if args.full and world == 1 and graphed is None and not args.no_f32_line and hasattr(model, "conv_dtype") and conv_dtype != "f32":
             # the same step with every contraction on the exact-fp32 matrix instruction (model.conv_dtype = "f32"): the
             # figure to hold next to the headline, whose contractions run as fp16x2 splits
             prev = model.conv_dtype
@@ -679,9 +744,10 @@ def main():
                 line["exact_f32_convs"].update(achieved_tflops=round(tfl, 2), peak=FP32_MFMA_PEAK_TFLOPS,
                                                frac=round(tfl / FP32_MFMA_PEAK_TFLOPS, 4))
             log("exact-fp32 convs: %.1f ms/step" % (1e3 * tf32 / args.steps))
-        state["taped"] = None                     # the probes below launch kernels directly; release the tape's pool
-        torch.cuda.empty_cache()
-        if not args.no_probe:
+        if args.full:
+            state["taped"] = None                 # the probes below launch kernels directly; release the tape's pool
+            torch.cuda.empty_cache()
+        if args.full and not args.no_probe:
             # the level passes run batched: every conv launch sees batch * L images
             n_pass = len(model.levels) if (hier and not getattr(model, "sequential_passes", False)) else 1
             line["roofline"] = probe_dominant_kernel(device, args.batch * n_pass, args.size, conv_dtype)
@@ -694,7 +760,7 @@ def main():
             if args.model == "hrnet":
                 line["roofline_other"] = probe_secondary_kernels(device, args.batch * n_pass, args.size, conv_dtype)
             log("probe: %s" % json.dumps(line["roofline"]))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             log("cpu baseline (oracle train steps, batch 4, on %d cores) ..." % host_cores())
             line["cpu_baseline"] = cpu_baseline(args, tree)
         print(json.dumps(line), flush=True)

@@ -24,8 +24,19 @@ def _oracle_grads(name, dtype):
     x, t = torch.from_numpy(g["x"]), torch.from_numpy(g["target"])
     m = build_model(OM, kind, hier, tree, size).to(dtype)
     m.train()
-    out = OT.forward_loss(m, x.to(dtype), t.to(dtype), nc, w, hierarchical=hier, is_unet=(kind == "unet"), with_metrics=False)
-    out["loss"].backward()
+    # The yardstick is pinned, whatever the host: one thread, oneDNN off (torch's native im2col + GEMM convolutions).  Left
+    # alone, torch-CPU routes convolutions to oneDNN or not by thread count and CPU, and the fp32 reference's distance from
+    # fp64 moves with that choice: hrnet_flat_tl_64 median 1.4-1.7e-3 with oneDNN, 4.0-4.5e-3 on the native path (an Intel
+    # and an AMD host).  The bars of _check were set against a reference 4.7e-3 from fp64, the native path's magnitude.
+    threads, onednn = torch.get_num_threads(), torch.backends.mkldnn.enabled
+    torch.set_num_threads(1)
+    torch.backends.mkldnn.enabled = False
+    try:
+        out = OT.forward_loss(m, x.to(dtype), t.to(dtype), nc, w, hierarchical=hier, is_unet=(kind == "unet"), with_metrics=False)
+        out["loss"].backward()
+    finally:
+        torch.set_num_threads(threads)
+        torch.backends.mkldnn.enabled = onednn
     return {n: p.grad.double().numpy() for n, p in m.named_parameters()}
 
 
