@@ -464,6 +464,37 @@ int hrseg_comm_destroy(void* comm);
 int hrseg_encode_targets(const unsigned char* label, const unsigned long long* on_lut, const int* parent,
                          float* out, int B, int C, long hw, hrseg_stream_t stream);
 
+/* ------------------------------------------------------------------ device input pipeline (Data/augment.py)
+ * The reference's per-sample transforms (Data/dataloaders.py:49-70, Data/dataset.py:397-470) for a batch of RAGGED
+ * uint8 sources: one packed byte buffer plus a DEVICE descriptor table desc [B][4] of int64 (byte offset, H, W,
+ * channels 1|3; 3 = interleaved HWC).  Output: x [B,3,S,S] fp32 in [-1,1], y [B,C,S,S] fp32 targets as
+ * hrseg_encode_targets.  params: DEVICE table [B][HRSEG_AUG_PARAMS] fp32 drawn on the host, laid out as below.
+ * Workspaces: hrseg_augment_workspace gives the bytes each entry point needs (eval mode needs none). */
+#define HRSEG_AUG_PARAMS 48
+#define HRSEG_AUG_P_FLAGS 0      /* HRSEG_AUG_HFLIP | HRSEG_AUG_VFLIP | HRSEG_AUG_WARP, as a float */
+#define HRSEG_AUG_P_ORDER 1      /* [4] ColorJitter order: 0 brightness, 1 contrast, 2 saturation, 3 hue */
+#define HRSEG_AUG_P_BRIGHT 5     /* brightness factor b */
+#define HRSEG_AUG_P_CONTRAST 6   /* [2] c, (float)(1 - c) */
+#define HRSEG_AUG_P_SAT 8        /* [2] s, (float)(1 - s) */
+#define HRSEG_AUG_P_HUE 10       /* hue shift */
+#define HRSEG_AUG_P_THETA 12     /* [6] torchvision affine theta, transposed and divided by (S/2): t0 t1 / t2 t3 / t4 t5 */
+#define HRSEG_AUG_P_TAPS 18      /* [25] normalised 1-D Gaussian blur taps */
+#define HRSEG_AUG_HFLIP 1
+#define HRSEG_AUG_VFLIP 2
+#define HRSEG_AUG_WARP 4
+int hrseg_augment_workspace(int B, int S, size_t* image_bytes, size_t* target_bytes);
+/* train: resize + 25x25 Gaussian blur + ColorJitter + normalise + flips + nearest affine (fill -1), 2 launches;
+ * eval (train == 0): resize + normalise, 1 launch, params and work unused.  S > 12 in train mode. */
+int hrseg_augment_image(const unsigned char* src, const long* desc, const float* params, float* x, int B, int S,
+                        int train, void* work, size_t work_bytes, hrseg_stream_t stream);
+/* per-node masks of the label (on_lut / parent exactly as hrseg_encode_targets), resized with antialias (torch
+ * _upsample_bilinear2d_aa) or plain bilinear, thresholded at 0.5 and encoded.  warp: flips + nearest affine with the
+ * reference's fill rule (channel 0: max of its resized mask, other channels: -1 before the threshold), 2 launches;
+ * warp == 0: 1 launch, params and work unused. */
+int hrseg_augment_targets(const unsigned char* label, const long* desc, const unsigned long long* on_lut,
+                          const int* parent, const float* params, float* y, int B, int C, int S, int warp,
+                          int antialias, void* work, size_t work_bytes, hrseg_stream_t stream);
+
 /* ------------------------------------------------------------------ level synthesis for flat models (evaluation side)
  * predictEval.py:85-129 get_parent_masks (parent = union of its descendant leaves, "any > 0") and :134-185
  * combine_levels (per-level tensors stitched from leaf and parent channels).  out[b][o] is the COPY of the single

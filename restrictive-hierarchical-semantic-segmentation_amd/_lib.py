@@ -111,6 +111,8 @@ PROTOTYPES = {
     "hrseg_adamw_dev": [_p, _p, _p, _p, _l, _p, _p, _p],
     "hrseg_fill": [_p, _f, _l, _p],
     "hrseg_encode_targets": [_p, _p, C.POINTER(C.c_int), _p, _i, _i, _l, _p],
+    "hrseg_augment_image": [_p, _p, _p, _p, _i, _i, _i, _p, C.c_size_t, _p],
+    "hrseg_augment_targets": [_p, _p, _p, C.POINTER(C.c_int), _p, _p, _i, _i, _i, _i, _i, _p, C.c_size_t, _p],
     "hrseg_combine_levels": [_p, _i, _p, _i, _p, _p, _p, _i, _i, _l, _p],
     "hrseg_weight_images_refresh": [_p],
 }
@@ -123,6 +125,7 @@ RAW_PROTOTYPES = {
     "hrseg_comm_destroy": [_p],
     "hrseg_set_scratch": [_p, C.c_size_t],
     "hrseg_set_weight_image_arena": [_p, C.c_size_t, _p, C.c_size_t, _p, _p, _p, _p],
+    "hrseg_augment_workspace": [_i, _i, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)],
 }
 
 _lib.hrseg_last_error_string.restype = C.c_char_p
@@ -199,7 +202,8 @@ _deterministic = False
 
 
 def launch_count(family=None, reset=False) -> int:
-    """convolution launches issued so far by kernel family (hrseg_launch_count; None = all families)"""
+    """launches issued so far by kernel family (hrseg_launch_count; None = all convolution families; the input
+    pipeline counts under "augment_image" / "augment_targets")"""
     return int(_lib.hrseg_launch_count(None if family is None else family.encode(), int(reset)))
 
 

@@ -572,6 +572,56 @@ def encode_targets(label, on_lut, parent):
     return out
 
 
+def augment_workspace(B, S):
+    """bytes of device workspace (image, targets) that the train-mode augment entry points need"""
+    img, tgt = C.c_size_t(0), C.c_size_t(0)
+    _lib.call_raw("hrseg_augment_workspace", int(B), int(S), C.byref(img), C.byref(tgt))
+    return int(img.value), int(tgt.value)
+
+
+def _check_ragged(buf, desc, desc_host, channels):
+    """a packed uint8 buffer and its [B,4] int64 descriptor table (device) are consistent with the host copy"""
+    assert buf.dtype == torch.uint8 and buf.is_cuda and buf.dim() == 1 and buf.is_contiguous()
+    assert desc.dtype == torch.int64 and desc.is_cuda and desc.shape == desc_host.shape and desc.dim() == 2 and desc.shape[1] == 4
+    n = buf.numel()
+    for off, H, W, ch in desc_host.tolist():
+        if ch not in channels or H < 1 or W < 1 or off < 0 or off + H * W * ch > n:
+            raise ValueError(f"ragged descriptor (offset {off}, {H}x{W}, {ch} channels) does not fit a {n}-byte buffer")
+
+
+def augment_image(src, desc, desc_host, params, S, train):
+    """packed uint8 sources + [B,4] descriptors (device, and their host copy for the bounds check), [B,48] fp32 params
+    (device; None in eval mode) -> x [B,3,S,S] fp32"""
+    _check_ragged(src, desc, desc_host, (1, 3))
+    B = desc.shape[0]
+    x = torch.empty((B, 3, S, S), dtype=torch.float32, device=src.device)
+    work, nbytes = None, 0
+    if train:
+        assert params is not None and params.is_cuda and params.dtype == torch.float32 and params.shape == (B, 48)
+        nbytes = augment_workspace(B, S)[0]
+        work = torch.empty(nbytes, dtype=torch.uint8, device=src.device)
+    call("hrseg_augment_image", ptr(src), ptr(desc), ptr(params) if train else None, ptr(x), B, S, int(bool(train)),
+         ptr(work), nbytes)
+    return x
+
+
+def augment_targets(label, desc, desc_host, on_lut, parent, params, S, warp, antialias=True):
+    """packed uint8 label maps + [B,4] descriptors -> y [B,C,S,S] fp32 (resized per-node masks, thresholded, encoded as
+    encode_targets; warp: flips + affine from params)"""
+    _check_ragged(label, desc, desc_host, (1,))
+    assert on_lut.dtype == torch.int64 and on_lut.numel() == 256 and on_lut.is_cuda
+    B, Cn = desc.shape[0], len(parent)
+    y = torch.empty((B, Cn, S, S), dtype=torch.float32, device=label.device)
+    work, nbytes = None, 0
+    if warp:
+        assert params is not None and params.is_cuda and params.dtype == torch.float32 and params.shape == (B, 48)
+        nbytes = augment_workspace(B, S)[1]
+        work = torch.empty(nbytes, dtype=torch.uint8, device=label.device)
+    call("hrseg_augment_targets", ptr(label), ptr(desc), ptr(on_lut), _lib.int_array(list(parent)),
+         ptr(params) if warp else None, ptr(y), B, Cn, S, int(bool(warp)), int(bool(antialias)), ptr(work), nbytes)
+    return y
+
+
 def combine_levels(x0, x1, masks, is_union):
     """x0 [B,C0,H,W] (+ x1 [B,C1,H,W] or None), per output channel a bit mask over the C0+C1 input channels and a
     union flag -> [B,len(masks),H,W]: copy of the selected channel, or 1.0 where any selected channel is > 0"""
