@@ -154,7 +154,9 @@ int hrseg_conv_wgrad_group_ws(int n, const float* const* x, const float* const* 
 /* launches issued so far by kernel family ("ws", "ws_group", "patch_sp", "sp_im2col", "sp_pgroup", "sp_group", "f32",
  * "f32_group", "wgrad_sp", "wgrad_sp_group", "wgrad_f32", "wgrad_f32_group", "wgrad9", "small_cin", "sp_wide"; NULL = all); reset != 0
  * zeroes what it returns.  "ws_canvas" counts PROBLEMS (not launches, not part of the NULL total) that a "ws" / "ws_group"
- * launch tiled as one canvas of side-by-side images, "wgrad_sp_t5" the "wgrad_sp" launches on 80 x 80 tiles ("wgrad_sp_wide": the wide-tile weight-gradient kernel, a family of its own).  The parity tests use it to prove which kernels a case ran. */
+ * launch tiled as one canvas of side-by-side images, "wgrad_sp_t5" the "wgrad_sp" launches on 80 x 80 tiles ("wgrad_sp_wide": the wide-tile weight-gradient kernel, a family of its own).  The parity tests use it to prove which kernels a case ran.
+ * "augment_image" / "augment_targets" (the input pipeline) and "decode_labels" (the output pipeline, 1 launch per
+ * hrseg_decode_labels call) are families of their own, outside the NULL total and the convolution counts. */
 long hrseg_launch_count(const char* family, int reset);
 /* tile-plan overrides and A/B switches for the sweep tools under tools/ (value 0 = automatic plan).  Keys: igemm_wtm,
  * igemm_kc, igemm_db, igemm_ksplit, group_wtm, wgrad_pix, wgrad_db, wgrad_blocks, wgrad_group_mult,
@@ -494,6 +496,34 @@ int hrseg_augment_image(const unsigned char* src, const long* desc, const float*
 int hrseg_augment_targets(const unsigned char* label, const long* desc, const unsigned long long* on_lut,
                           const int* parent, const float* params, float* y, int B, int C, int S, int warp,
                           int antialias, void* work, size_t work_bytes, hrseg_stream_t stream);
+
+/* ------------------------------------------------------------------ device output pipeline (Data/decode.py)
+ * The inverse of the input pipeline: per-level logits at network size -> one label map per source image, at the source's
+ * own size, in the pixel values of class_map.csv.  z: HOST array of nlevels DEVICE pointers, level L is [B, C[L], S, S]
+ * fp32 NCHW, channels in breadth-first tree order (a flat model: one level over the leaves).  For output pixel (y, x) of
+ * sample b (H_b x W_b from desc, laid out as for hrseg_augment_*: byte offset, H, W, 1):
+ *   1. every logit that is needed is resampled S x S -> H_b x W_b bilinearly (torch align_corners=False, no antialias);
+ *   2. c = arg-max over the level-0 channels (lowest index wins ties);
+ *   3. while node c has children: c = arg-max over the consecutive channels of ITS child group at the next level only
+ *      (the model's composed probability P_parent * softmax_group(z) has the same arg-max: the decoded path is always
+ *      consistent with the tree);
+ *   4. labels[offset + y * W_b + x] = pixel value of the leaf reached;
+ *   5. confidence (optional, same packing in floats): sigmoid(z_0[c_0]) * prod_L softmax_group(z_L)[c_L]; with
+ *      root_softmax (flat models) the level-0 factor is softmax over the level instead of the sigmoid.
+ * Limits: nlevels <= 8, C[L] <= 16, sum C[L] <= 64, S <= 32768; labels 4-byte and confidence 16-byte aligned.  The tree
+ * travels as a kernel argument: no device allocation, no workspace, no synchronisation.  1 launch, counted under the
+ * family "decode_labels". */
+#define HRSEG_DECODE_MAX_LEVELS 8
+#define HRSEG_DECODE_MAX_CHANNELS 16
+typedef struct {
+  int first_child[HRSEG_DECODE_MAX_LEVELS][HRSEG_DECODE_MAX_CHANNELS]; /* first channel of the child group at level L+1, or -1 */
+  int n_children[HRSEG_DECODE_MAX_LEVELS][HRSEG_DECODE_MAX_CHANNELS];  /* 0: a leaf */
+  int pixel_val[HRSEG_DECODE_MAX_LEVELS][HRSEG_DECODE_MAX_CHANNELS];   /* leaves: 0..255 */
+  int root_softmax;                                                   /* confidence of level 0: 0 sigmoid, 1 softmax */
+} hrseg_decode_tree_t;
+int hrseg_decode_labels(int nlevels, const float* const* z, const int* C, const hrseg_decode_tree_t* tree,
+                        const long* desc, unsigned char* labels, float* confidence, int B, int S,
+                        hrseg_stream_t stream);
 
 /* ------------------------------------------------------------------ level synthesis for flat models (evaluation side)
  * predictEval.py:85-129 get_parent_masks (parent = union of its descendant leaves, "any > 0") and :134-185

@@ -1,0 +1,155 @@
+"""Device output pipeline: per-level logits at network size -> one label map per source image, at the source's own
+size, in the pixel values of class_map.csv -- the format `TargetEncoder` / `DeviceAugment` read.  Kernel: csrc/decode.hip.
+
+The decode is restrictive and top-down: arg-max over the level-0 channels, then at every level only the child group of
+the node chosen above it competes.  The model composes a child's probability as P_parent * softmax_group(z) (the
+log(P_parent + eps) bias is constant inside a group), so the arg-max of the group's logits is the arg-max of the
+model's own probabilities and the decoded path is always a path of the tree -- which the reference's independent
+per-level arg-max does not guarantee.  The logits are resampled bilinearly (F.interpolate, align_corners=False) to each
+image's own H x W inside the kernel; no full-size fp32 tensor exists at any point.
+
+The tables are built on the host without a GPU; only `decode` launches.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from .. import ops
+from .._lib import require_gpu
+from ..utils.hierarchy import TreeIndex
+from .dataset import TargetEncoder
+
+
+class DecodeTables:
+    """The tree as hrseg_decode_labels reads it, per level and channel: `first_child` (channel of the first child at the
+    next level, -1 for leaves), `n_children` (0 for leaves), `pixel_val` (leaves; -1 for parents); `C` channels per
+    level, `names` per level, `root_softmax` (flat models: the level-0 confidence is a soft-max, not a sigmoid)."""
+
+    def __init__(self, C, first_child, n_children, pixel_val, root_softmax, names=None):
+        self.C = [int(n) for n in C]
+        self.first_child = [list(r) for r in first_child]
+        self.n_children = [list(r) for r in n_children]
+        self.pixel_val = [list(r) for r in pixel_val]
+        self.root_softmax = bool(root_softmax)
+        self.names = names
+
+
+def build_tables(class_tree, class_map, model_type=1) -> DecodeTables:
+    """class_tree + class_map (any form TargetEncoder accepts) -> DecodeTables.  model_type 1: one level per tree depth,
+    channels in breadth-first order; model_type 0: one level over the leaves.  KeyError for a leaf without a pixel value,
+    ValueError for one outside uint8, NotImplementedError when a parent's children are not consecutive channels."""
+    name2pix = TargetEncoder._name2pix(class_map)
+    index = TreeIndex(class_tree)
+
+    def pixel(n):
+        if n not in name2pix:
+            raise KeyError(f"Class '{n}' not found in class_map.")
+        v = int(name2pix[n])
+        if not 0 <= v <= 255:
+            raise ValueError(f"pixel value {v} of class '{n}' does not fit a uint8 label image")
+        return v
+
+    if int(model_type) == 0:
+        leaves = index.leaf_names
+        tables = DecodeTables([len(leaves)], [[-1] * len(leaves)], [[0] * len(leaves)], [[pixel(n) for n in leaves]], True,
+                              [leaves])
+    else:
+        levels = index.levels
+        first, count, pix = [], [], []
+        for L, names in enumerate(levels):
+            f, c, p = [], [], []
+            for n in names:
+                kids = index.children[n]
+                if not kids:
+                    f.append(-1)
+                    c.append(0)
+                    p.append(pixel(n))
+                    continue
+                chans = [levels[L + 1].index(k) for k in kids]
+                if chans != list(range(chans[0], chans[0] + len(chans))):
+                    raise NotImplementedError("children of a parent must occupy consecutive channels (BFS channel order)")
+                f.append(chans[0])
+                c.append(len(chans))
+                p.append(-1)
+            first.append(f)
+            count.append(c)
+            pix.append(p)
+        tables = DecodeTables([len(n) for n in levels], first, count, pix, False, [list(n) for n in levels])
+    ops.check_decode_tables(tables)
+    return tables
+
+
+def label_desc(sizes) -> torch.Tensor:
+    """[(H, W), ...] -> the [B,4] int64 host descriptor table of a densely packed batch of label maps"""
+    rows, off = [], 0
+    for H, W in sizes:
+        rows.append([off, int(H), int(W), 1])
+        off += int(H) * int(W)
+    return torch.tensor(rows, dtype=torch.int64).reshape(-1, 4)
+
+
+class RaggedLabels:
+    """A decoded batch: `labels` packed uint8 (device), `confidence` packed fp32 (device) or None, `desc` [B,4] int64
+    (device) and `desc_host` (byte offset, H, W, 1)."""
+
+    def __init__(self, labels, confidence, desc, desc_host):
+        self.labels, self.confidence, self.desc, self.desc_host = labels, confidence, desc, desc_host
+
+    def __len__(self):
+        return self.desc_host.shape[0]
+
+    def _split(self, flat):
+        return [flat[off:off + H * W].reshape(H, W) for off, H, W, _ in self.desc_host.tolist()]
+
+    def unpack(self):
+        """list of H x W uint8 numpy arrays (views of ONE device-to-host copy)"""
+        return self._split(self.labels.cpu().numpy())
+
+    def unpack_confidence(self):
+        """list of H x W fp32 numpy arrays, or None when the decode did not keep the confidence"""
+        return None if self.confidence is None else self._split(self.confidence.cpu().numpy())
+
+
+class DeviceDecode:
+    """`dec = DeviceDecode(class_tree, class_map, model_type); out = dec.decode(output_logits, desc, desc_host)` with
+    the models' `output_logits` (a list of per-level [B,C_L,S,S] tensors, or the flat model's single tensor) and the label
+    descriptors of the wanted sizes (`label_desc`, or a RaggedBatch's `ldesc`) -> RaggedLabels."""
+
+    def __init__(self, class_tree, class_map, model_type=1):
+        self.class_tree, self.model_type = class_tree, int(model_type)
+        self.tables = build_tables(class_tree, class_map, self.model_type)
+        self.leaf_values = sorted(v for row, kids in zip(self.tables.pixel_val, self.tables.n_children)
+                                  for v, k in zip(row, kids) if k == 0)
+
+    def decode(self, output_logits, desc, desc_host=None, want_confidence=False) -> RaggedLabels:
+        require_gpu()
+        logits = [output_logits] if torch.is_tensor(output_logits) else list(output_logits)
+        if desc_host is None:
+            if desc.is_cuda:
+                raise ValueError("a device descriptor table needs its host copy (desc_host)")
+            desc_host = desc
+        desc = desc.to(logits[0].device, non_blocking=True)
+        labels, conf = ops.decode_labels(logits, self.tables, desc, desc_host, want_confidence)
+        return RaggedLabels(labels, conf, desc, desc_host)
+
+    def decode_sizes(self, output_logits, sizes, want_confidence=False) -> RaggedLabels:
+        """decode to a densely packed batch of the given [(H, W), ...]"""
+        return self.decode(output_logits, label_desc(sizes), None, want_confidence)
+
+
+def pack_images(images):
+    """list of uint8 HxW / HxWx3 arrays -> (packed uint8 tensor, [B,4] int64 descriptors), on the host"""
+    flat, rows, off = [], [], 0
+    for img in images:
+        a = torch.as_tensor(np.ascontiguousarray(img))
+        if a.dtype != torch.uint8:
+            raise TypeError("sources must be uint8")
+        if a.dim() == 3 and a.shape[2] == 1:
+            a = a[:, :, 0]
+        if not (a.dim() == 2 or (a.dim() == 3 and a.shape[2] == 3)):
+            raise ValueError(f"image of shape {tuple(a.shape)}: expected HxW or HxWx3")
+        rows.append([off, a.shape[0], a.shape[1], 1 if a.dim() == 2 else 3])
+        flat.append(a.reshape(-1))
+        off += flat[-1].numel()
+    return torch.cat(flat), torch.tensor(rows, dtype=torch.int64)

@@ -94,9 +94,11 @@ class PngPairDataset(torch.utils.data.Dataset):
 class DeviceAugmentLoader:
     """`for x, y in DeviceAugmentLoader(dataset, batch_size, shuffle, num_workers, augment)`: x [B,3,S,S] and y [B,C,S,S]
     device tensors from `augment` (a DeviceAugment).  The workers decode and collate uint8 only; batch k+1's host->device
-    copy is issued on a side stream before batch k is handed out, so it overlaps the step that consumes batch k."""
+    copy is issued on a side stream before batch k is handed out, so it overlaps the step that consumes batch k.
+    with_sources=True yields (x, y, sources): the batch's device RaggedBatch rides along, for consumers that need every
+    sample's own size (predictEval.predict_loop writing source-size label maps)."""
 
-    def __init__(self, dataset, batch_size, shuffle=False, num_workers=0, augment=None, drop_last=False):
+    def __init__(self, dataset, batch_size, shuffle=False, num_workers=0, augment=None, drop_last=False, with_sources=False):
         if augment is None:
             raise ValueError("DeviceAugmentLoader needs a DeviceAugment")
         self.dataset, self.augment = dataset, augment
@@ -104,6 +106,7 @@ class DeviceAugmentLoader:
                                                   collate_fn=ragged_collate, pin_memory=torch.cuda.is_available(),
                                                   drop_last=drop_last)
         self.batch_size = batch_size
+        self.with_sources = bool(with_sources)
 
     def __len__(self):
         return len(self.loader)
@@ -128,4 +131,4 @@ class DeviceAugmentLoader:
             dev.record_stream(torch.cuda.current_stream(device))
             nxt = next(it, None)
             pending = upload(nxt) if nxt is not None else None       # overlaps the augmentation and the step below
-            yield self.augment(dev)
+            yield (*self.augment(dev), dev) if self.with_sources else self.augment(dev)

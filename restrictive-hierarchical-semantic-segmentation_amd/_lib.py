@@ -54,6 +54,11 @@ class BnBwd(C.Structure):
                 ("dres_accumulate", _i), ("npix", _l), ("C", _i), ("partial", _p), ("nchunks", _i), ("dy_absmax", _p), ("nseg", _i), ("relu_mask", _p), ("sum_ranks", _i)]
 
 
+class DecodeTree(C.Structure):
+    """hrseg_decode_tree_t"""
+    _fields_ = [("first_child", (_i * 16) * 8), ("n_children", (_i * 16) * 8), ("pixel_val", (_i * 16) * 8), ("root_softmax", _i)]
+
+
 # name -> argtypes, exactly the prototypes of include/hrseg.h
 PROTOTYPES = {
     "hrseg_conv_fwd": [_p, _p, _p, _p, C.POINTER(ConvShape), _p],
@@ -113,6 +118,7 @@ PROTOTYPES = {
     "hrseg_encode_targets": [_p, _p, C.POINTER(C.c_int), _p, _i, _i, _l, _p],
     "hrseg_augment_image": [_p, _p, _p, _p, _i, _i, _i, _p, C.c_size_t, _p],
     "hrseg_augment_targets": [_p, _p, _p, C.POINTER(C.c_int), _p, _p, _i, _i, _i, _i, _i, _p, C.c_size_t, _p],
+    "hrseg_decode_labels": [_i, _p, C.POINTER(C.c_int), C.POINTER(DecodeTree), _p, _p, _p, _i, _i, _p],
     "hrseg_combine_levels": [_p, _i, _p, _i, _p, _p, _p, _i, _i, _l, _p],
     "hrseg_weight_images_refresh": [_p],
 }
@@ -203,7 +209,7 @@ _deterministic = False
 
 def launch_count(family=None, reset=False) -> int:
     """launches issued so far by kernel family (hrseg_launch_count; None = all convolution families; the input
-    pipeline counts under "augment_image" / "augment_targets")"""
+    pipeline counts under "augment_image" / "augment_targets", the output pipeline under "decode_labels")"""
     return int(_lib.hrseg_launch_count(None if family is None else family.encode(), int(reset)))
 
 

@@ -33,14 +33,16 @@
 // launch counters per kernel family (hrseg_launch_count): the parity tests assert that a case really ran the family
 // it claims to pin (e.g. the wave-specialised kernels on a 64x64 golden with lowered routing thresholds)
 enum { CNT_WS = 0, CNT_WS_GROUP, CNT_PATCH_SP, CNT_SP_IM2COL, CNT_SP_PGROUP, CNT_SP_GROUP, CNT_F32, CNT_F32_GROUP, CNT_WGRAD_SP,
-       CNT_WGRAD_F32, CNT_WGRAD_F32_GROUP, CNT_WGRAD9, CNT_SMALL_CIN, CNT_SP_WIDE, CNT_WS_CANVAS, CNT_WGRAD_SP_GROUP, CNT_WGRAD_SP_T5, CNT_WGRAD_SP_WIDE, CNT_AUG_IMAGE, CNT_AUG_TARGETS, CNT_N };
+       CNT_WGRAD_F32, CNT_WGRAD_F32_GROUP, CNT_WGRAD9, CNT_SMALL_CIN, CNT_SP_WIDE, CNT_WS_CANVAS, CNT_WGRAD_SP_GROUP, CNT_WGRAD_SP_T5, CNT_WGRAD_SP_WIDE, CNT_AUG_IMAGE, CNT_AUG_TARGETS, CNT_DECODE_LABELS, CNT_N };
 static const char* const g_cnt_names[CNT_N] = {"ws", "ws_group", "patch_sp", "sp_im2col", "sp_pgroup", "sp_group", "f32", "f32_group",
                                                "wgrad_sp", "wgrad_f32", "wgrad_f32_group", "wgrad9", "small_cin", "sp_wide", "ws_canvas", "wgrad_sp_group", "wgrad_sp_t5", "wgrad_sp_wide",
-                                               "augment_image", "augment_targets"};
+                                               "augment_image", "augment_targets", "decode_labels"};
 static long g_cnt[CNT_N];
 // the all-families total counts convolution launches: "ws_canvas" counts PROBLEMS laid out as a canvas inside ws / ws_group
-// launches, the augment families (augment.hip) are the input pipeline's
-static bool in_conv_total(int i) { return i != CNT_WS_CANVAS && i != CNT_WGRAD_SP_T5 && i != CNT_AUG_IMAGE && i != CNT_AUG_TARGETS; }
+// launches, the augment families (augment.hip) are the input pipeline's, "decode_labels" (decode.hip) the output pipeline's
+static bool in_conv_total(int i) {
+  return i != CNT_WS_CANVAS && i != CNT_WGRAD_SP_T5 && i != CNT_AUG_IMAGE && i != CNT_AUG_TARGETS && i != CNT_DECODE_LABELS;
+}
 extern "C" long hrseg_launch_count(const char* family, int reset) {
   long total = 0;
   for (int i = 0; i < CNT_N; ++i)
@@ -53,6 +55,7 @@ void hrseg_count_augment_launches(int image, int targets) {
   g_cnt[CNT_AUG_IMAGE] += image;
   g_cnt[CNT_AUG_TARGETS] += targets;
 }
+void hrseg_count_decode_launches(int n) { g_cnt[CNT_DECODE_LABELS] += n; }
 
 // tuning overrides (hrseg_tune, 0 = automatic): pixel tiles per wave, K chunks, LDS buffers, split-K
 static int g_tune_wtm = 0, g_tune_kc = 0, g_tune_db = 0, g_tune_ksplit = 0;

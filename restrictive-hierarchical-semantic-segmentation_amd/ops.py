@@ -622,6 +622,73 @@ def augment_targets(label, desc, desc_host, on_lut, parent, params, S, warp, ant
     return y
 
 
+DECODE_MAX_LEVELS, DECODE_MAX_CHANNELS, DECODE_MAX_TOTAL = 8, 16, 64
+
+
+def check_decode_tables(tables):
+    """the limits of hrseg_decode_labels on a Data.decode.DecodeTables: <= 8 levels, <= 16 channels per level, <= 64 in
+    all, child groups inside the next level, leaf pixel values in uint8 (ValueError otherwise; needs no GPU)"""
+    Cs = list(tables.C)
+    if not 1 <= len(Cs) <= DECODE_MAX_LEVELS:
+        raise ValueError(f"decode_labels: {len(Cs)} levels, supported 1..{DECODE_MAX_LEVELS}")
+    for L, n in enumerate(Cs):
+        if not 1 <= n <= DECODE_MAX_CHANNELS:
+            raise ValueError(f"decode_labels: level {L} has {n} channels, supported 1..{DECODE_MAX_CHANNELS}")
+        if not (len(tables.first_child[L]) == len(tables.n_children[L]) == len(tables.pixel_val[L]) == n):
+            raise ValueError(f"decode_labels: the tables of level {L} do not have {n} entries")
+    if sum(Cs) > DECODE_MAX_TOTAL:
+        raise ValueError(f"decode_labels: {sum(Cs)} channels over all levels, at most {DECODE_MAX_TOTAL}")
+    for L, n in enumerate(Cs):
+        for c in range(n):
+            first, kids, pv = tables.first_child[L][c], tables.n_children[L][c], tables.pixel_val[L][c]
+            if kids == 0:
+                if not 0 <= pv <= 255:
+                    raise ValueError(f"decode_labels: leaf (level {L}, channel {c}) has pixel value {pv}")
+            elif L + 1 >= len(Cs) or kids < 0 or first < 0 or first + kids > Cs[L + 1]:
+                raise ValueError(f"decode_labels: children [{first}, {first + kids}) of (level {L}, channel {c}) are not "
+                                 "channels of the next level")
+
+
+def _decode_tree_struct(tables):
+    t = _lib.DecodeTree()
+    for L, n in enumerate(tables.C):
+        for c in range(n):
+            t.first_child[L][c] = int(tables.first_child[L][c])
+            t.n_children[L][c] = int(tables.n_children[L][c])
+            t.pixel_val[L][c] = int(tables.pixel_val[L][c])
+    t.root_softmax = int(bool(tables.root_softmax))
+    return t
+
+
+def decode_labels(logits, tables, desc, desc_host, want_confidence=False):
+    """per-level logits (list of [B,C_L,S,S] fp32 device tensors, or one tensor) + a Data.decode.DecodeTables + [B,4] int64
+    label descriptors (byte offset, H, W, 1; device, and their host copy for the bounds check) -> the packed uint8
+    label maps (sum of H*W bytes: a densely packed batch), each at its own H x W, plus the packed fp32 path confidence
+    when asked for (else None).  The tables are read afresh on every call.  One launch, no synchronisation."""
+    logits = [logits] if torch.is_tensor(logits) else list(logits)
+    check_decode_tables(tables)
+    if len(logits) != len(tables.C):
+        raise ValueError(f"decode_labels: {len(logits)} logit levels for a {len(tables.C)}-level table")
+    B, S = logits[0].shape[0], logits[0].shape[2]
+    for L, z in enumerate(logits):
+        if z.dim() != 4 or tuple(z.shape) != (B, tables.C[L], S, S):
+            raise ValueError(f"decode_labels: level {L} logits of shape {tuple(z.shape)}, expected {(B, tables.C[L], S, S)}")
+        assert z.is_cuda and z.dtype == torch.float32
+    assert desc.dtype == torch.int64 and desc.is_cuda and desc.dim() == 2 and tuple(desc.shape) == tuple(desc_host.shape) == (B, 4)
+    rows = desc_host.tolist()
+    n = sum(H * W for _, H, W, _ in rows)
+    for off, H, W, ch in rows:
+        if ch != 1 or H < 1 or W < 1 or off < 0 or off + H * W > n:
+            raise ValueError(f"ragged descriptor (offset {off}, {H}x{W}, {ch} channels) does not fit a {n}-byte label buffer")
+    logits = [_c(z) for z in logits]
+    labels = torch.empty(n, dtype=torch.uint8, device=logits[0].device)
+    conf = torch.empty(n, dtype=torch.float32, device=logits[0].device) if want_confidence else None
+    call("hrseg_decode_labels", len(logits), _lib.ptr_array(logits), _lib.int_array(list(tables.C)),
+         C.byref(_decode_tree_struct(tables)),
+         ptr(desc), ptr(labels), ptr(conf), B, S)
+    return labels, conf
+
+
 def combine_levels(x0, x1, masks, is_union):
     """x0 [B,C0,H,W] (+ x1 [B,C1,H,W] or None), per output channel a bit mask over the C0+C1 input channels and a
     union flag -> [B,len(masks),H,W]: copy of the selected channel, or 1.0 where any selected channel is > 0"""

@@ -158,6 +158,63 @@ def save_prediction_images(output_class, save_dir, filename):
             k += 1
 
 
+def save_label_maps(save_dir, names, ragged_labels):
+    """one 8-bit grayscale PNG per image of a decoded batch (Data.decode.RaggedLabels), at the image's own size and in the
+    pixel values of class_map.csv: <save_dir>/<name>; one device-to-host copy for the whole batch"""
+    import os
+    maps = ragged_labels.unpack()
+    if len(names) != len(maps):
+        raise ValueError(f"{len(names)} file names for {len(maps)} label maps")
+    os.makedirs(save_dir, exist_ok=True)
+    paths = []
+    for name, m in zip(names, maps):
+        paths.append(os.path.join(save_dir, name))
+        write_png_gray(paths[-1], m)
+    return paths
+
+
+class Predictor:
+    """Deployment-side inference: `labels = Predictor(model, class_tree, class_map, args)(images)` with a list of ragged
+    uint8 HxW / HxWx3 sources (or a RaggedBatch) -> RaggedLabels, one label map per source at the source's own size.
+    Eval-mode resize + normalise to args.img_size on the device (ops.augment_image), the eval-mode forward, then the
+    restrictive top-down decode of the logits (Data/decode.py).  args: img_size, model_type, model_select.
+    The model runs in eval mode for the call and gets its previous mode back afterwards.  keep_logits=True keeps the
+    latest call's logits (what the decode read) alive in `last_logits`; by default nothing of a batch is held."""
+
+    def __init__(self, model, class_tree, class_map, args, want_confidence=False, keep_logits=False):
+        from .Data.decode import DeviceDecode
+        self.model, self.class_tree, self.args = model, class_tree, args
+        self.size = int(args.img_size)
+        self.decoder = DeviceDecode(class_tree, class_map, args.model_type)
+        self.want_confidence = bool(want_confidence)
+        self.keep_logits = bool(keep_logits)
+        self.last_logits = None
+
+    @torch.no_grad()
+    def __call__(self, images):
+        from . import train as T
+        from .Data.decode import label_desc, pack_images
+        from .Data.loader import RaggedBatch
+        device = next(self.model.parameters()).device
+        if isinstance(images, RaggedBatch):
+            src, desc, desc_host = images.src, images.desc, images.desc_host
+        else:
+            src, desc_host = pack_images(images)
+            desc = desc_host
+        src, desc = src.to(device, non_blocking=True), desc.to(device, non_blocking=True)
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            x = ops.augment_image(src, desc, desc_host, None, self.size, False)
+            _, output_logits = T._model_call(self.model, x, self.args, self.class_tree)
+        finally:
+            self.model.train(was_training)
+        if self.keep_logits:
+            self.last_logits = output_logits
+        ldesc = label_desc([(H, W) for _, H, W, _ in desc_host.tolist()])
+        return self.decoder.decode(output_logits, ldesc, None, self.want_confidence)
+
+
 def write_metrics_csv(path, accuracy, iou, dice, precision, recall, class_metrics):
     """metrics.csv of predict() (predictEval.py:556-573): one "Average" row, one row per class"""
     import csv
@@ -172,10 +229,14 @@ def write_metrics_csv(path, accuracy, iou, dice, precision, recall, class_metric
 
 @torch.no_grad()
 def predict_loop(model, device, test_loader, args, class_tree, Accuracy, Iou, perf_measure, Precision, Recall,
-                 save_dir=None, target_paths=None):
+                 save_dir=None, target_paths=None, label_dir=None, class_map=None):
     """The per-fold body of the reference's predict() (predictEval.py:305-573) on a built model and loader: eval-mode
     forward, prediction_prep, get_metrics per batch, optional PNG dump of each batch's first image and metrics.csv.
-    -> dict(accuracy, iou, dice, precision, recall, class_metrics, performance)."""
+    -> dict(accuracy, iou, dice, precision, recall, class_metrics, performance).
+    label_dir (with class_map): the loader yields (data, target, sources) -- DeviceAugmentLoader(with_sources=True) -- and
+    EVERY image's label map, decoded from the batch's logits at the source's own size, is written to
+    <label_dir>/<basename of its target path, or its running index>.png.  target_paths then holds one path per IMAGE, and
+    save_dir names a batch's dump after the batch's first image; without label_dir it holds one path per batch, as before."""
     import os
     import numpy as np
     from . import train as T
@@ -183,8 +244,14 @@ def predict_loop(model, device, test_loader, args, class_tree, Accuracy, Iou, pe
     n_cls = sum(args.num_classes_full) if hasattr(args, "num_classes_full") else sum(args.num_classes)
     acc2, iou2, dice2, prec2, rec2, perf = [], [], [], [], [], []
     cls2 = T._new_class_metrics(n_cls)
-    for i, (data, target) in enumerate(test_loader):
-        data, target = data.to(device), target.to(device)
+    decoder, n_images = None, 0
+    if label_dir is not None:
+        from .Data.decode import DeviceDecode, label_desc
+        if class_map is None:
+            raise ValueError("label_dir needs the class_map (leaf pixel values)")
+        decoder = DeviceDecode(class_tree, class_map, args.model_type)
+    for i, batch in enumerate(test_loader):
+        data, target = batch[0].to(device), batch[1].to(device)
         _, output_logits = T._model_call(model, data, args, class_tree)
         output_class, eval_targets = prediction_prep(output_logits, target, args, class_tree)
         cls2, acc2, iou2, dice2, prec2, rec2, no_bg = T.get_metrics(output_class, eval_targets, acc2, iou2, dice2, prec2, rec2,
@@ -192,8 +259,18 @@ def predict_loop(model, device, test_loader, args, class_tree, Accuracy, Iou, pe
                                                                     cls2, args)
         perf.append(float(no_bg.mean()))
         if save_dir is not None:
-            name = os.path.basename(target_paths[i]) if target_paths is not None else f"{i:05d}.png"
+            first = i if decoder is None else n_images
+            name = os.path.basename(target_paths[first]) if target_paths is not None else f"{i:05d}.png"
             save_prediction_images(output_class, save_dir, name)
+        if decoder is not None:
+            if len(batch) < 3:
+                raise ValueError("label_dir: the loader must yield (data, target, sources), e.g. "
+                                 "DeviceAugmentLoader(..., with_sources=True)")
+            sizes = [(H, W) for _, H, W, _ in batch[2].desc_host.tolist()]
+            names = [os.path.basename(target_paths[n_images + j]) if target_paths is not None else f"{n_images + j:05d}.png"
+                     for j in range(len(sizes))]
+            save_label_maps(label_dir, names, decoder.decode(output_logits, label_desc(sizes)))
+            n_images += len(sizes)
     if save_dir is not None:
         os.makedirs(save_dir, exist_ok=True)
         write_metrics_csv(os.path.join(save_dir, "metrics.csv"), acc2, iou2, dice2, prec2, rec2, cls2)
