@@ -18,8 +18,6 @@
 // channel 0 takes max(mask0) -> 1 if any pixel of it survived the threshold, every other channel 0) and the encode.
 #include "common.h"
 
-void hrseg_count_augment_launches(int image, int targets);     // conv.hip: hrseg_launch_count families
-
 typedef unsigned char u8;
 typedef unsigned long long u64;
 
@@ -382,7 +380,7 @@ extern "C" int hrseg_augment_image(const unsigned char* src, const long* desc, c
   if (!train) {
     hipLaunchKernelGGL(aug_image_eval, grid_px, dim3(AUG_TPB), 0, st, src, (const long long*)desc, x, S);
     HRSEG_LAUNCH_CHECK("augment_image_eval");
-    hrseg_count_augment_launches(1, 0);
+    hrseg_count(CNT_AUG_IMAGE);
     return 0;
   }
   HRSEG_CHECK_ARG(params && work, "hrseg_augment_image: train mode needs params and a workspace");
@@ -398,7 +396,7 @@ extern "C" int hrseg_augment_image(const unsigned char* src, const long* desc, c
   HRSEG_LAUNCH_CHECK("augment_image_pass_a");
   hipLaunchKernelGGL(aug_image_pass_b, grid_px, dim3(AUG_TPB), 0, st, state, partials, params, x, S, nt * nt);
   HRSEG_LAUNCH_CHECK("augment_image_pass_b");
-  hrseg_count_augment_launches(2, 0);
+  hrseg_count(CNT_AUG_IMAGE, 2);
   return 0;
 }
 
@@ -438,6 +436,6 @@ extern "C" int hrseg_augment_targets(const unsigned char* label, const long* des
     hipLaunchKernelGGL(aug_targets_warp, grid_px, dim3(AUG_TPB), 0, st, bits, flags, params, pr, y, C, S);
     HRSEG_LAUNCH_CHECK("augment_targets_warp");
   }
-  hrseg_count_augment_launches(0, warp ? 2 : 1);
+  hrseg_count(CNT_AUG_TARGETS, warp ? 2 : 1);
   return 0;
 }

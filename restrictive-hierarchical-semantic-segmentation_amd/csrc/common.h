@@ -39,8 +39,8 @@ __device__ __forceinline__ f32x4 hrseg_join_f16x2(const hrseg_u32x4& g) {
 void hrseg_set_error(const char* fmt, ...);
 // hrseg_tune("deterministic", 1): every reduction that would add floats with atomics in a run-dependent order
 // takes its single-adder form instead (no split-K, one pixel range per weight-gradient tile, one block per image
-// in the head / loss reductions): bit-reproducible gradients at some cost in speed
-extern int hrseg_g_deterministic;
+// in the head / loss reductions): bit-reproducible gradients at some cost in speed (the knob hrseg_g_deterministic)
+#include "runtime.h"      // launch-counter families (hrseg_count) and tuning knobs (int hrseg_g_<key>)
 
 #define HRSEG_CHECK_ARG(cond, ...)            \
   do {                                        \

@@ -22,43 +22,17 @@
 //  * Cin <= 8 (the image layer; with logit-concatenated re-encoding image + previous level's logits): direct VALU
 //    kernels (conv_small.hip).
 //
-// This file holds the dispatch (tile plans, kernel-family choice per problem) and the C ABI; the kernel families
-// and their launchers live in conv_f32.hip, conv_wgrad_f32.hip, conv_sp_im2col.hip, conv_sp_patch.hip,
-// conv_sp_pgroup.hip, conv_ws.hip and conv_wgrad_sp.hip (split for build time; conv_common.h declares the launchers).
+// This file holds the dispatch (tile plans, kernel-family choice per problem) and the convolution C ABI, nothing else:
+//  * the kernel families and their launchers live in conv_f32.hip, conv_wgrad_f32.hip, conv_sp_im2col.hip, conv_sp_patch.hip,
+//    conv_sp_pgroup.hip, conv_ws.hip, conv_wgrad_sp.hip and conv_small.hip (conv_common.h declares the launchers and the
+//    structs they take; this file does not include the kernel bodies of conv_sp.h);
+//  * the scratch ring and the weight-image cache live in conv_scratch.hip;
+//  * the launch counters (hrseg_count) and the tuning knobs (hrseg_g_<key>, set by hrseg_tune) are the rows of runtime.h.
 #include "conv_common.h"
-#include "conv_sp.h"
-#include <mutex>
-#include <vector>
 
-// launch counters per kernel family (hrseg_launch_count): the parity tests assert that a case really ran the family
-// it claims to pin (e.g. the wave-specialised kernels on a 64x64 golden with lowered routing thresholds)
-enum { CNT_WS = 0, CNT_WS_GROUP, CNT_PATCH_SP, CNT_SP_IM2COL, CNT_SP_PGROUP, CNT_SP_GROUP, CNT_F32, CNT_F32_GROUP, CNT_WGRAD_SP,
-       CNT_WGRAD_F32, CNT_WGRAD_F32_GROUP, CNT_WGRAD9, CNT_SMALL_CIN, CNT_SP_WIDE, CNT_WS_CANVAS, CNT_WGRAD_SP_GROUP, CNT_WGRAD_SP_T5, CNT_WGRAD_SP_WIDE, CNT_AUG_IMAGE, CNT_AUG_TARGETS, CNT_DECODE_LABELS, CNT_N };
-static const char* const g_cnt_names[CNT_N] = {"ws", "ws_group", "patch_sp", "sp_im2col", "sp_pgroup", "sp_group", "f32", "f32_group",
-                                               "wgrad_sp", "wgrad_f32", "wgrad_f32_group", "wgrad9", "small_cin", "sp_wide", "ws_canvas", "wgrad_sp_group", "wgrad_sp_t5", "wgrad_sp_wide",
-                                               "augment_image", "augment_targets", "decode_labels"};
-static long g_cnt[CNT_N];
-// the all-families total counts convolution launches: "ws_canvas" counts PROBLEMS laid out as a canvas inside ws / ws_group
-// launches, the augment families (augment.hip) are the input pipeline's, "decode_labels" (decode.hip) the output pipeline's
-static bool in_conv_total(int i) {
-  return i != CNT_WS_CANVAS && i != CNT_WGRAD_SP_T5 && i != CNT_AUG_IMAGE && i != CNT_AUG_TARGETS && i != CNT_DECODE_LABELS;
-}
-extern "C" long hrseg_launch_count(const char* family, int reset) {
-  long total = 0;
-  for (int i = 0; i < CNT_N; ++i)
-    if (family ? !strcmp(family, g_cnt_names[i]) : in_conv_total(i)) { total += g_cnt[i]; if (reset) g_cnt[i] = 0; }
-  if (!family && reset)
-    for (int i = 0; i < CNT_N; ++i) g_cnt[i] = 0;
-  return total;
-}
-void hrseg_count_augment_launches(int image, int targets) {
-  g_cnt[CNT_AUG_IMAGE] += image;
-  g_cnt[CNT_AUG_TARGETS] += targets;
-}
-void hrseg_count_decode_launches(int n) { g_cnt[CNT_DECODE_LABELS] += n; }
-
-// tuning overrides (hrseg_tune, 0 = automatic): pixel tiles per wave, K chunks, LDS buffers, split-K
-static int g_tune_wtm = 0, g_tune_kc = 0, g_tune_db = 0, g_tune_ksplit = 0;
+// hrseg_tune igemm_wtm / igemm_kc / igemm_db / igemm_ksplit: overrides of the fp32 tile plan.  A grouped launch has one common
+// plan they do not fit: under any of them grouped calls issue their problems one by one.
+static bool igemm_overridden() { return hrseg_g_igemm_wtm || hrseg_g_igemm_kc || hrseg_g_igemm_db || hrseg_g_igemm_ksplit; }
 
 // zero fill as a KERNEL node (not hipMemsetAsync): keeps a captured hipGraph a pure kernel chain
 __global__ void zero_f32_kernel(float* __restrict__ p, size_t n) {
@@ -92,11 +66,11 @@ static IgemmPlan plan_igemm(const IgemmArgs& a) {
     pl.ksplit = (int)((448 + blocks - 1) / blocks);
     if (pl.ksplit > nstages / 12) pl.ksplit = nstages / 12;
   }
-  if (g_tune_wtm >= 10 && a.N % 96 == 0) pl.wtn = 6;   // tuning: tens digit 1 = 96-channel tiles
-  if (g_tune_wtm % 10) pl.wtm = g_tune_wtm % 10;
-  if (g_tune_kc && a.K % (16 * g_tune_kc) == 0) pl.kc = g_tune_kc;
-  if (g_tune_db) pl.db = g_tune_db;
-  if (g_tune_ksplit) pl.ksplit = g_tune_ksplit;
+  if (hrseg_g_igemm_wtm >= 10 && a.N % 96 == 0) pl.wtn = 6;   // tuning: tens digit 1 = 96-channel tiles
+  if (hrseg_g_igemm_wtm % 10) pl.wtm = hrseg_g_igemm_wtm % 10;
+  if (hrseg_g_igemm_kc && a.K % (16 * hrseg_g_igemm_kc) == 0) pl.kc = hrseg_g_igemm_kc;
+  if (hrseg_g_igemm_db) pl.db = hrseg_g_igemm_db;
+  if (hrseg_g_igemm_ksplit) pl.ksplit = hrseg_g_igemm_ksplit;
   if (hrseg_g_deterministic) pl.ksplit = 1;
   // split-K needs an output it may add into: accumulate mode, or a contiguous tensor it can zero
   const int nst = a.ntaps * (a.K / (16 * pl.kc));
@@ -133,14 +107,13 @@ static int finalize_args(IgemmArgs& a) {
 }
 
 // ---- split-precision plan: 128-pixel tiles for large problems, 64 otherwise; split-K under 256 blocks
-static int g_sp_wtm = 0, g_sp_wtn = 0, g_sp_ksplit = 0;      // hrseg_tune overrides (0 = automatic)
 static SpPlan plan_sp(const IgemmArgs& a) {
   SpPlan pl;
   pl.wtn = (a.N % 48 == 0) ? 3 : (a.N % 64 == 0) ? 4 : (a.N % 32 == 0) ? 2 : 1;
-  if (g_sp_wtn && a.N % (16 * g_sp_wtn) == 0) pl.wtn = g_sp_wtn;
+  if (hrseg_g_sp_wtn && a.N % (16 * hrseg_g_sp_wtn) == 0) pl.wtn = hrseg_g_sp_wtn;
   const int ntn = a.N / (16 * pl.wtn);
   pl.wtm = ((long)ceil_div(a.M, 128) * ntn >= 512) ? 2 : 1;
-  if (g_sp_wtm) pl.wtm = g_sp_wtm;
+  if (hrseg_g_sp_wtm) pl.wtm = hrseg_g_sp_wtm;
   const long blocks = (long)ceil_div(a.M, 64 * pl.wtm) * ntn;
   const int nslabs = (a.ntaps * (a.K / 16) + 1) / 2;
   pl.ksplit = 1;
@@ -148,7 +121,7 @@ static SpPlan plan_sp(const IgemmArgs& a) {
     pl.ksplit = (int)((448 + blocks - 1) / blocks);
     if (pl.ksplit > nslabs / 8) pl.ksplit = nslabs / 8;
   }
-  if (g_sp_ksplit) pl.ksplit = g_sp_ksplit;
+  if (hrseg_g_sp_ksplit) pl.ksplit = hrseg_g_sp_ksplit;
   if (hrseg_g_deterministic) pl.ksplit = 1;
   if (pl.ksplit > nslabs) pl.ksplit = nslabs;
   if (pl.ksplit < 1) pl.ksplit = 1;
@@ -157,12 +130,6 @@ static SpPlan plan_sp(const IgemmArgs& a) {
   return pl;
 }
 
-// halo-patch body: full 3x3 stride-1 problems (forward or data gradient) on images wide enough that the
-// 8 x 16 tiles waste little and fill the chip; returns the chunks per K stage (3 or 4), 0 = not a patch case
-// routing thresholds (hrseg_tune keys sp_patch_min_tiles, auto_min_pixels, sp_ws_min_tiles): the parity tests lower them so that
-// the small golden cases run the kernels the headline sizes run
-static int g_patch_min_tiles = 192, g_auto_min_pix = 8192, g_ws_min_tiles = 96;
-static int g_sp_patch = 1;              // hrseg_tune "sp_patch": 0 = never use the patch body
 // tap geometry of a full 3x3 stride-1 problem: 0 = forward (tap t reads offset (t/3-1, t%3-1)), 1 = data gradient
 // (offset (1-t/3, 1-t%3)), -1 = neither; the weight tap index must be t
 static int patch_flip(const IgemmArgs& a) {
@@ -176,90 +143,39 @@ static int patch_flip(const IgemmArgs& a) {
   }
   return fwd ? 0 : bwd ? 1 : -1;
 }
+// halo-patch body: full 3x3 stride-1 problems (forward or data gradient) on images wide enough that the
+// 8 x 16 tiles waste little and fill the chip; returns the chunks per K stage (3 or 4), 0 = not a patch case
+// (the routing thresholds sp_patch_min_tiles, auto_min_pixels and sp_ws_min_tiles are knobs: the parity tests lower them so
+// that the small golden cases run the kernels the headline sizes run)
 static int patch_cs(const IgemmArgs& a, int wtn) {
-  if (!g_sp_patch || patch_flip(a) < 0 || a.ntaps != 9 || a.T != 9 || a.sy != 1 || a.sx != 1 || !a.direct_out || a.Hi != a.Ho || a.Wi != a.Wo)
+  if (!hrseg_g_sp_patch || patch_flip(a) < 0 || a.ntaps != 9 || a.T != 9 || a.sy != 1 || a.sx != 1 || !a.direct_out || a.Hi != a.Ho || a.Wi != a.Wo)
     return 0;
   if (a.oy_min != -1 || a.ox_min != -1 || (wtn != 3 && wtn != 4 && wtn != 6)) return 0;
   const int cs = (a.K % 48 == 0) ? 3 : (a.K % 64 == 0) ? 4 : 0;
   if (!cs) return 0;
   const long tiles = (long)a.B * ceil_div(a.Ho, 8) * ceil_div(a.Wo, 16);
   const double waste = (double)(ceil_div(a.Ho, 8) * 8) * (ceil_div(a.Wo, 16) * 16) / ((double)a.Ho * a.Wo);
-  if (waste > 1.22 || tiles * (a.N / (16 * wtn)) < g_patch_min_tiles) return 0;
+  if (waste > 1.22 || tiles * (a.N / (16 * wtn)) < hrseg_g_sp_patch_min_tiles) return 0;
   return cs;
 }
 static long patch_tiles(const IgemmArgs& a, int wtn) {
   return (long)a.B * ceil_div(a.Ho, 8) * ceil_div(a.Wo, 16) * (a.N / (16 * wtn));
 }
-// ---- wave-specialised halo-patch path (fp16x2; conv_sp.h: igemm_patch_ws_body)
-// The pre-split weight images live in a scratch buffer the host hands over once (hrseg_set_scratch; device memory is
-// the caller's, as everywhere in this ABI).  It is cut into eight regions, one per stream that launches convolutions,
-// each a ring: an image is written and read by kernels of ONE stream, in order, so reusing a slot after the ring
-// wraps needs no synchronisation.  Without a scratch buffer the path is simply not taken.
-extern int g_small_cin3;                // conv_small.hip
-static int g_sp_ws = 1;                 // hrseg_tune "sp_ws": 0 = never use the wave-specialised body
-static int g_ws_n48 = 1;                // hrseg_tune "sp_ws_n48": 0 = 48-channel tilings stay on the block-synchronous kernels
-static int g_ws_waste = 200;            // hrseg_tune "sp_ws_waste": tile padding accepted, percent of the image
-static int g_ws_bf16 = 1;               // hrseg_tune "sp_ws_bf16": 0 = the bf16 arithmetic (one piece, one product) stays off the wave-specialised kernels
-static unsigned char* g_scratch = nullptr;
-static size_t g_scratch_bytes = 0;
-static int g_scratch_device = -1;       // the device that was current when the buffer was attached: launches on another one do not use it
-static std::mutex g_scratch_mu;         // the region table is the only mutable state the launch path shares between host threads
-struct ScratchRegion { hipStream_t st; bool used; size_t head; };
-static const int SCRATCH_REGIONS = 8;
-static ScratchRegion g_regions[SCRATCH_REGIONS];
-extern "C" int hrseg_set_scratch(void* ptr, size_t bytes) {
-  HRSEG_CHECK_ARG((ptr && bytes >= (1u << 20)) || (!ptr && bytes == 0), "hrseg_set_scratch: need a buffer of at least 1 MiB, or (null, 0)");
-  HRSEG_CHECK_ARG(((uintptr_t)ptr & 255) == 0, "hrseg_set_scratch: the buffer must be 256-byte aligned");
-  std::lock_guard<std::mutex> lock(g_scratch_mu);
-  g_scratch = (unsigned char*)ptr;
-  g_scratch_bytes = bytes;
-  g_scratch_device = -1;
-  if (ptr && hipGetDevice(&g_scratch_device) != hipSuccess) g_scratch_device = -1;
-  for (auto& r : g_regions) r = ScratchRegion{nullptr, false, 0};
-  return 0;
-}
-static bool scratch_usable() {
-  if (!g_scratch) return false;
-  int dev = -1;
-  return hipGetDevice(&dev) == hipSuccess && dev == g_scratch_device;
-}
-// `bytes` CONTIGUOUS bytes of this stream's ring.  All images of one grouped launch are reserved together: they are written by one
-// kernel and read by the next, so a wrap between two of them would put a later image over an earlier one of the same launch.
-// nullptr: no buffer (or one of another device), no free region for a ninth stream, or more than a region holds.
-static unsigned char* scratch_reserve(hipStream_t st, size_t bytes) {
-  if (!scratch_usable()) return nullptr;
-  std::lock_guard<std::mutex> lock(g_scratch_mu);
-  const size_t region = (g_scratch_bytes / SCRATCH_REGIONS) & ~(size_t)255;
-  bytes = (bytes + 255) & ~(size_t)255;
-  if (bytes > region) return nullptr;
-  int r = -1;
-  for (int i = 0; i < SCRATCH_REGIONS && r < 0; ++i)
-    if (g_regions[i].used && g_regions[i].st == st) r = i;
-  for (int i = 0; i < SCRATCH_REGIONS && r < 0; ++i)
-    if (!g_regions[i].used) { g_regions[i] = ScratchRegion{st, true, 0}; r = i; }
-  if (r < 0) return nullptr;
-  if (g_regions[r].head + bytes > region) g_regions[r].head = 0;       // wrap BEFORE the group, never inside it
-  unsigned char* p = g_scratch + (size_t)r * region + g_regions[r].head;
-  g_regions[r].head += bytes;
-  return p;
-}
-// tiling of the wave-specialised body for a problem: 0 = not eligible, 1 = 48 channels x 48-channel K stages on
-// 8 x 16 pixel tiles, 2 = 96 x 48, 3 = 64 x 64, 4 = 48 x 48 on 16 x 16 pixel tiles (a 48-channel slab on 8 rows is
-// 18 MFMAs per wave: too short for the producers to keep up)
-static const int WS_WTN[5] = {0, 3, 6, 4, 3}, WS_CS[5] = {0, 3, 3, 4, 3}, WS_TH[5] = {0, 8, 8, 8, 16};
-// Canvas mode of the wave-specialised body (conv_sp.h): the images of the batch side by side with a zero column between
-// them, tiled as ONE image.  Taken when it cuts the padded area by at least 5 % (39 x 39: 1.26x -> 1.05x, 20 x 20: 1.92x ->
-// 1.32x at 8 images; the 155 / 78-pixel branches stay per image) and the multiply-high image lookup is exact.
-static int g_ws_canvas = 5;             // hrseg_tune "sp_ws_canvas": least cut of the padded area, percent (0 = per-image tiles everywhere)
+// ---- wave-specialised halo-patch path (conv_sp.h: igemm_patch_ws_body; tilings WS_WTN / WS_CS / WS_TH: conv_common.h)
+// Its pre-split weight images live in the scratch ring or the weight-image arena (conv_scratch.hip); without a scratch
+// buffer the path is simply not taken.
+// Canvas mode of the body: the images of the batch side by side with a zero column between them, tiled as ONE image.  Taken
+// when it cuts the padded area by at least sp_ws_canvas = 5 % (39 x 39: 1.26x -> 1.05x, 20 x 20: 1.92x -> 1.32x at 8 images;
+// the 155 / 78-pixel branches stay per image) and the multiply-high image lookup is exact.
 static long ws_pixel_tiles(const IgemmArgs& a, int kind, bool canvas) {       // 16-column x TH-row tiles of the whole batch
   const long ty = ceil_div(a.Ho, WS_TH[kind]);
   return canvas ? ty * ceil_div((long)a.B * (a.Wo + 1) - 1, 16) : (long)a.B * ty * ceil_div(a.Wo, 16);
 }
+static long ld_max(const IgemmArgs& a) { return a.ldx > a.ldy ? (a.ldx > a.ldr ? a.ldx : a.ldr) : (a.ldy > a.ldr ? a.ldy : a.ldr); }
 static bool ws_canvas(const IgemmArgs& a, int kind) {
-  if (!g_ws_canvas || a.B < 2 || (long)a.B * (a.Wo + 1) >= 65536) return false;
-  const long ldmax = a.ldx > a.ldy ? (a.ldx > a.ldr ? a.ldx : a.ldr) : (a.ldy > a.ldr ? a.ldy : a.ldr);
-  if ((long)a.B * a.Ho * a.Wo * ldmax * 4 >= (1l << 31)) return false;          // one buffer descriptor (input, output, residual) spans the batch
-  return ws_pixel_tiles(a, kind, true) * 100 <= ws_pixel_tiles(a, kind, false) * (100 - g_ws_canvas);
+  if (!hrseg_g_sp_ws_canvas || a.B < 2 || (long)a.B * (a.Wo + 1) >= 65536) return false;
+  if ((long)a.B * a.Ho * a.Wo * ld_max(a) * 4 >= (1l << 31)) return false;          // one buffer descriptor (input, output, residual) spans the batch
+  return ws_pixel_tiles(a, kind, true) * 100 <= ws_pixel_tiles(a, kind, false) * (100 - hrseg_g_sp_ws_canvas);
 }
 static long ws_tiles(const IgemmArgs& a, int kind) {
   return ws_pixel_tiles(a, kind, ws_canvas(a, kind)) * (a.N / (16 * WS_WTN[kind]));
@@ -275,14 +191,13 @@ static void ws_set_canvas(IgemmArgs& a, int kind) {
   a.cv_nb = a.B;
   a.cv_magic = (unsigned)(((1ull << 32) + a.cv_w1 - 1) / a.cv_w1);
 }
+// tiling of the body for a (finalized) problem by its geometry alone, 0 = not eligible
 static int ws_kind(const IgemmArgs& a) {
-  if (!g_sp_ws || !scratch_usable() || patch_flip(a) < 0 || a.T != 9 || a.sy != 1 || a.sx != 1 || !a.direct_out || a.Hi != a.Ho || a.Wi != a.Wo)
+  if (patch_flip(a) < 0 || a.T != 9 || a.sy != 1 || a.sx != 1 || !a.direct_out || a.Hi != a.Ho || a.Wi != a.Wo)
     return 0;
   if (a.oy_min != -1 || a.ox_min != -1) return 0;
-  {   // 32-bit byte offsets inside one image (input patch, output, residual)
-    const long ldmax = a.ldx > a.ldy ? (a.ldx > a.ldr ? a.ldx : a.ldr) : (a.ldy > a.ldr ? a.ldy : a.ldr);
-    if ((double)a.Ho * a.Wo * (double)ldmax * 4.0 >= 4294967040.0) return 0;
-  }
+  // 32-bit byte offsets inside one image (input patch, output, residual)
+  if ((double)a.Ho * a.Wo * (double)ld_max(a) * 4.0 >= 4294967040.0) return 0;
   int kind = (a.K % 48 == 0 && a.N % 48 == 0) ? 1 : (a.K % 64 == 0 && a.N % 64 == 0) ? 3 : 0;
   if (!kind) return 0;
   if (kind == 1) {      // the tiling is chosen on the per-image tile counts (a size class of the problem), canvas or not
@@ -290,141 +205,34 @@ static int ws_kind(const IgemmArgs& a) {
     if (a.N % 96 == 0 && plain_tiles(2) >= 160) kind = 2;
     else if (ws_pixel_tiles(a, 4, false) * 256 <= 1.10 * a.B * a.Ho * a.Wo && plain_tiles(4) >= 256) kind = 4;
   }
-  if (ws_waste(a, kind) * 100 > g_ws_waste) return 0;
-  if ((kind == 1 || kind == 4) && !g_ws_n48) return 0;
+  if (ws_waste(a, kind) * 100 > hrseg_g_sp_ws_waste) return 0;
+  if ((kind == 1 || kind == 4) && !hrseg_g_sp_ws_n48) return 0;
   return kind;
 }
-static size_t ws_image_bytes(const IgemmArgs& a, int kind, int ns) {      // ns = 4: two fp16 pieces per weight, 1: one bf16 piece
-  const int wtn = WS_WTN[kind], cs = WS_CS[kind];
-  return (size_t)(a.N / (16 * wtn)) * (a.K / (16 * cs)) * ((9 * cs + 1) / 2) * (size_t)((ns == 4 ? 2 : 1) * 16 * wtn * 64);
+// ---- routing to the body, stated once: the dispatchers below and hrseg_conv_x_split_ok all ask here
+// the body is switched on and has a scratch ring of this device for its weight images
+static bool ws_enabled() { return hrseg_g_sp_ws && scratch_usable(); }
+// ... and no sp_wtn override pins the channel tile of the block-synchronous bodies: the guard of every route to the body
+static bool ws_route_open() { return ws_enabled() && !hrseg_g_sp_wtn; }
+// the tiling of a problem the body is worth it for (enough tiles for its persistent blocks), else 0
+static int ws_fit(const IgemmArgs& a) {
+  const int k = ws_kind(a);
+  return (k && ws_tiles(a, k) >= hrseg_g_sp_ws_min_tiles) ? k : 0;
 }
-// ---- persistent weight images (hrseg_set_weight_image_arena / hrseg_weight_images_refresh) ------------------------------
-// A weight image depends on the weights alone, and those change once per step: instead of one small image launch in front
-// of every convolution (136 per HRNet step, 5.5 us + a kernel boundary each, all on the critical path) the images of the
-// model's parameters live in an arena the caller owns and are rebuilt by ONE launch when the caller says the weights
-// changed.  An image is cached only for a weight the caller flags as persistent (hrseg_conv_shape_t.w_persistent) AND that
-// lies inside one of the two registered source ranges (the flat parameter buffer and its transposed copy): a scratch tensor
-// that happens to reuse a dead model's addresses never hits.  First use of a weight registers it (and builds its image on
-// the spot, as before); every later refresh rebuilds all registered images.  Single-threaded like the rest of the launch path.
-struct ImgEntry { const float* w; unsigned char* img; int K, N, layout, ns, nblk; float wscale; };
-static std::vector<ImgEntry> g_img;
-static unsigned char* g_img_arena = nullptr;
-static size_t g_img_arena_bytes = 0, g_img_arena_head = 0;
-static WeightImageTabEntry* g_img_tab = nullptr;       // device copy of g_img for the refresh kernel (caller's memory)
-static size_t g_img_tab_cap = 0;
-static bool g_img_dirty = false;
-static const float* g_img_range[4] = {nullptr, nullptr, nullptr, nullptr};
-static int g_img_device = -1;
-extern "C" int hrseg_set_weight_image_arena(void* arena, size_t bytes, void* table, size_t table_bytes, const float* lo0,
-                                            const float* hi0, const float* lo1, const float* hi1) {
-  HRSEG_CHECK_ARG((arena && bytes >= (1u << 20) && table && table_bytes >= sizeof(WeightImageTabEntry)) || (!arena && bytes == 0),
-                  "hrseg_set_weight_image_arena: need an arena of at least 1 MiB and a table, or (null, 0)");
-  HRSEG_CHECK_ARG((((uintptr_t)arena | (uintptr_t)table) & 255) == 0, "hrseg_set_weight_image_arena: buffers must be 256-byte aligned");
-  g_img.clear();
-  g_img_arena = (unsigned char*)arena;
-  g_img_arena_bytes = bytes;
-  g_img_arena_head = 0;
-  g_img_tab = (WeightImageTabEntry*)table;
-  g_img_tab_cap = arena ? table_bytes / sizeof(WeightImageTabEntry) : 0;
-  g_img_dirty = false;
-  g_img_range[0] = lo0; g_img_range[1] = hi0; g_img_range[2] = lo1; g_img_range[3] = hi1;
-  g_img_device = -1;
-  if (arena && hipGetDevice(&g_img_device) != hipSuccess) g_img_device = -1;
-  return 0;
-}
-static bool img_cacheable(const IgemmArgs& a) {
-  if (!g_img_arena || !a.w_persistent) return false;
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess || dev != g_img_device) return false;
-  return (a.w >= g_img_range[0] && a.w < g_img_range[1]) || (a.w >= g_img_range[2] && a.w < g_img_range[3]);
-}
-extern "C" int hrseg_weight_images_refresh(hrseg_stream_t stream) {
-  if (g_img.empty()) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  if (g_img_dirty) {
-    std::vector<WeightImageTabEntry> tab(g_img.size());
-    int end = 0;
-    for (size_t i = 0; i < g_img.size(); ++i) {
-      end += g_img[i].nblk;
-      tab[i] = WeightImageTabEntry{g_img[i].w, g_img[i].img, g_img[i].K, g_img[i].layout, g_img[i].ns, end, g_img[i].wscale, 0};
-    }
-    // (pageable source: the call returns once the table is staged; only after new weights were registered)
-    if (hipMemcpyAsync(g_img_tab, tab.data(), tab.size() * sizeof(WeightImageTabEntry), hipMemcpyHostToDevice, st) != hipSuccess)
-    { hrseg_set_error("hrseg_weight_images_refresh: table upload failed"); return HRSEG_ERR_LAUNCH; }
-    g_img_dirty = false;
-  }
-  int total = 0;
-  for (const auto& e : g_img) total += e.nblk;
-  launch_weight_image_table(g_img_tab, (int)g_img.size(), total, st);
-  HRSEG_LAUNCH_CHECK("weight_image_table");
-  return 0;
-}
-// the weight images of n problems (sets a[i].wimg): cached ones are used as they are, the others are written with one launch
-// (into their new arena slot, or into this stream's scratch ring); false: no scratch space
-static bool ws_make_images(IgemmArgs* a, const int* kinds, int n, hipStream_t st, int ns) {
-  WeightImageGroup g;
-  g.n = 0;
-  g.ns = ns;
-  size_t off[MAXG], total = 0;
-  int build[MAXG], nb = 0;
-  unsigned char* dst[MAXG];
-  for (int i = 0; i < n; ++i) {
-    dst[i] = nullptr;
-    const int layout = kinds[i] == 4 ? 1 : kinds[i];        // kinds 1 and 4 share the (48, 48) image layout
-    const size_t bytes = (ws_image_bytes(a[i], kinds[i], ns) + 255) & ~(size_t)255;
-    if (img_cacheable(a[i])) {
-      for (const auto& e : g_img)
-        if (e.w == a[i].w && e.layout == layout && e.ns == ns && e.K == a[i].K && e.N == a[i].N && e.wscale == a[i].wscale) { dst[i] = e.img; break; }
-      if (dst[i]) continue;                                  // cached: kept current by hrseg_weight_images_refresh
-      if (g_img_arena_head + bytes <= g_img_arena_bytes && g_img.size() < g_img_tab_cap) {
-        const int wtn = WS_WTN[kinds[i]], cs = WS_CS[kinds[i]];
-        dst[i] = g_img_arena + g_img_arena_head;
-        g_img_arena_head += bytes;
-        g_img.push_back(ImgEntry{a[i].w, dst[i], a[i].K, a[i].N, layout, ns, (a[i].N / (16 * wtn)) * (a[i].K / (16 * cs)) * ((9 * cs + 1) / 2),
-                                 a[i].wscale});
-        g_img_dirty = true;
-        build[nb++] = i;
-        continue;
-      }
-    }
-    off[i] = total;
-    total += bytes;
-    build[nb++] = i;
-  }
-  unsigned char* base = total ? scratch_reserve(st, total) : nullptr;
-  if (total && !base) return false;
-  int end = 0;
-  for (int j = 0; j < nb; ++j) {
-    const int i = build[j];
-    if (!dst[i]) dst[i] = base + off[i];
-    const int wtn = WS_WTN[kinds[i]], cs = WS_CS[kinds[i]];
-    end += (a[i].N / (16 * wtn)) * (a[i].K / (16 * cs)) * ((9 * cs + 1) / 2);
-    g.blk_end[g.n] = end;
-    g.kind[g.n] = kinds[i];
-    g.K[g.n] = a[i].K;
-    g.wscale[g.n] = a[i].wscale;
-    g.w[g.n] = a[i].w;
-    g.img[g.n] = dst[i];
-    ++g.n;
-  }
-  for (int i = 0; i < n; ++i) a[i].wimg = dst[i];
-  if (g.n) launch_weight_images(g, end, st);
-  return true;
-}
-static int g_exp_nosplit = 0;           // hrseg_tune "exp_nosplit_x": MEASUREMENT ONLY -- the ceiling of "activations pre-split in HBM" (results wrong)
-static int g_ws_epi_early = 1;          // hrseg_tune "ws_epi_early": 0 = the wave-specialised body reads accumulate / residual values at the tile's end
+// does the body take this (finalized) problem?  Its tiling, 0 = no.
+static int ws_take(const IgemmArgs& a) { return ws_route_open() ? ws_fit(a) : 0; }
+
 // hrseg_tune "ws_epi_cost" / "ws_epi_acc_cost": what a tile costs beyond its slabs, in slab times (0 = the defaults below,
 // negative = none), for the block partition of a grouped launch.  A tile's prologue / epilogue (tile switch, 12 KB of stores per
 // consumer wave, the reads of an accumulating or residual epilogue) is worth about ten slabs: a 48-channel layer's tile is ONE
 // K stage of 14 slabs, so a partition by slab count alone starves it of blocks.  Measured in isolation (tools/ws_epilogue_ab.py,
 // B = 8): four-branch forward 150 -> 121 us, three-branch 112 -> 91, two-branch 75.5 -> 67; accumulating data gradient
 // 171 -> 126 / 127 -> 96 / 85 -> 75 us.  Results do not depend on the partition (no atomics, fixed per-tile order).
-static int g_ws_epi_cost = 0, g_ws_epi_acc_cost = 0;
 static const int WS_EPI_COST = 10, WS_EPI_ACC_COST = 16;
 static int launch_ws_single(IgemmArgs a, int kind, hipStream_t st, int ns = 4) {
   if (a.x_presplit && ns != 4) return 1;                   // (the caller refuses the route: the pre-split form is fp16x2's)
-  a.epi_early = g_ws_epi_early;
-  a.exp_nosplit = (g_exp_nosplit && !patch_flip(a)) ? 1 : 0;      // (forward only: the data gradient's operand is a scaled gradient)
+  a.epi_early = hrseg_g_ws_epi_early;
+  a.exp_nosplit = (hrseg_g_exp_nosplit_x && !patch_flip(a)) ? 1 : 0;      // (forward only: the data gradient's operand is a scaled gradient)
   ws_set_canvas(a, kind);
   const int ntotal = (int)ws_tiles(a, kind);
   if (!ws_make_images(&a, &kind, 1, st, ns)) return 1;
@@ -432,8 +240,8 @@ static int launch_ws_single(IgemmArgs a, int kind, hipStream_t st, int ns = 4) {
   const dim3 grid((unsigned)ceil_div(ntotal, per));
   const int flip = patch_flip(a);
   if (a.stat_partial) *a.stat_rows = (int)grid.x;           // one row of partial sums per block
-  ++g_cnt[CNT_WS];
-  g_cnt[CNT_WS_CANVAS] += a.cv_w1 > 0;
+  hrseg_count(CNT_WS);
+  hrseg_count(CNT_WS_CANVAS, a.cv_w1 > 0);
   return launch_ws_kernel(a, kind, flip, (int)grid.x, ntotal, st, ns);
 }
 // One launch for several problems: the 256 persistent blocks are divided among the problems in proportion to their
@@ -451,11 +259,11 @@ static int launch_ws_group(IgemmArgs* a, const int* kinds, int n, hipStream_t st
     const int cs = WS_CS[kinds[i]];
     ws_set_canvas(a[i], kinds[i]);
     ntot[i] = ws_tiles(a[i], kinds[i]);
-    a[i].epi_early = g_ws_epi_early;
-    a[i].exp_nosplit = (g_exp_nosplit && !f) ? 1 : 0;
+    a[i].epi_early = hrseg_g_ws_epi_early;
+    a[i].exp_nosplit = (hrseg_g_exp_nosplit_x && !f) ? 1 : 0;
     // slabs per tile, plus the tile's epilogue in slab times (an accumulating / residual epilogue waits for its reads)
-    const int ec = g_ws_epi_cost ? (g_ws_epi_cost > 0 ? g_ws_epi_cost : 0) : WS_EPI_COST;
-    const int eac = g_ws_epi_acc_cost ? (g_ws_epi_acc_cost > 0 ? g_ws_epi_acc_cost : 0) : WS_EPI_ACC_COST;
+    const int ec = hrseg_g_ws_epi_cost ? (hrseg_g_ws_epi_cost > 0 ? hrseg_g_ws_epi_cost : 0) : WS_EPI_COST;
+    const int eac = hrseg_g_ws_epi_acc_cost ? (hrseg_g_ws_epi_acc_cost > 0 ? hrseg_g_ws_epi_acc_cost : 0) : WS_EPI_ACC_COST;
     cost[i] = (long)(a[i].K / (16 * cs)) * ((9 * cs + 1) / 2) + ((a[i].accumulate || a[i].res) ? eac : ec);
     total += ntot[i] * cost[i];
   }
@@ -490,50 +298,46 @@ static int launch_ws_group(IgemmArgs* a, const int* kinds, int n, hipStream_t st
     g.blk_end[i] = end;
     g.kind[i] = kinds[i];
     g.a[i] = a[i];
-    g_cnt[CNT_WS_CANVAS] += a[i].cv_w1 > 0;
+    hrseg_count(CNT_WS_CANVAS, a[i].cv_w1 > 0);
   }
-  ++g_cnt[CNT_WS_GROUP];
+  hrseg_count(CNT_WS_GROUP);
   return launch_ws_group_kernel(g, flip, st, ns);
 }
 
-static int g_sp_img = 1;               // hrseg_tune "sp_img": 0 = the block-synchronous patch body splits its weights on the fly
-static int g_sp_persist = 2;            // hrseg_tune "sp_persist": persistent patch blocks per CU (0 = one tile per block)
 static int launch_patch_sp(int ns, const IgemmArgs& a_in, int wtn, int cs, hipStream_t st) {
   const int ntotal = (int)patch_tiles(a_in, wtn);
   int blocks = ntotal;
-  if (g_sp_persist > 0 && ntotal > 256 * g_sp_persist) {
+  if (hrseg_g_sp_persist > 0 && ntotal > 256 * hrseg_g_sp_persist) {
     // equal chunks: the block count that gives every block the same number of tiles (+-1)
-    const int per = ceil_div(ntotal, 256 * g_sp_persist);
+    const int per = ceil_div(ntotal, 256 * hrseg_g_sp_persist);
     blocks = ceil_div(ntotal, per);
   }
   const int flip = patch_flip(a_in);
   IgemmArgs a = a_in;
-  if (ns == 4 && g_sp_img) {      // pre-split weights where an image layout exists for the tiling (else on the fly)
+  if (ns == 4 && hrseg_g_sp_img) {      // pre-split weights where an image layout exists for the tiling (else on the fly)
     int kind = (wtn == 3 && cs == 3) ? 1 : (wtn == 6 && cs == 3) ? 2 : (wtn == 4 && cs == 4) ? 3 : 0;
     if (kind) ws_make_images(&a, &kind, 1, st, 4);      // (no scratch space: a.wimg stays null)
   }
-  ++g_cnt[CNT_PATCH_SP];
+  hrseg_count(CNT_PATCH_SP);
   return launch_patch_sp_kernel(ns, a, wtn, cs, flip, blocks, ntotal, st);
 }
 
 // wide-tile im2col body (conv_sp.h: igemm_spw_body): channel tile in 16-channel units, 0 = not a case for it.
 // At least 96 output channels, a tile count that fills the chip (128-pixel tiles), and room in the scratch ring.
-static int g_sp_wide = 1;               // hrseg_tune "sp_wide": 0 = never use the wide-tile body
-static int g_spw_min_blocks = 256;      // hrseg_tune "sp_wide_min_blocks"
 static int spw_wtn(const IgemmArgs& a) {
-  if (!g_sp_wide || !scratch_usable() || a.K % 16 || a.M < 128) return 0;
+  if (!hrseg_g_sp_wide || !scratch_usable() || a.K % 16 || a.M < 128) return 0;
   const int wtn = (a.N % 240 == 0) ? 15 : (a.N % 192 == 0) ? 12 : (a.N % 128 == 0) ? 8 : (a.N % 96 == 0) ? 6 : 0;
   if (!wtn) return 0;
-  if ((long)ceil_div(a.M, 128) * (a.N / (16 * wtn)) < g_spw_min_blocks) return 0;
+  if ((long)ceil_div(a.M, 128) * (a.N / (16 * wtn)) < hrseg_g_sp_wide_min_blocks) return 0;
   // the body walks its slabs six at a time (register sets and LDS buffers are compile-time): short reductions would
   // multiply zeros for most of a trip -- they stay on the narrow body (hrseg_tune sp_wide = 2 lifts the rule: tests)
   const int nslabs = (a.ntaps * (a.K / 16) + 1) / 2, padded = (nslabs + 5) / 6 * 6;
-  if (g_sp_wide < 2 && (padded - nslabs) * 10 > nslabs) return 0;
+  if (hrseg_g_sp_wide < 2 && (padded - nslabs) * 10 > nslabs) return 0;
   return wtn;
 }
 
 static int launch_sp(int ns, const IgemmArgs& a, const SpPlan& pl, hipStream_t st) {
-  if (launch_sp_kernel(ns, a, pl, st) == 0) { ++g_cnt[CNT_SP_IM2COL]; return 0; }
+  if (launch_sp_kernel(ns, a, pl, st) == 0) { hrseg_count(CNT_SP_IM2COL); return 0; }
   hrseg_set_error("igemm_sp: no kernel for plan wtm=%d wtn=%d", pl.wtm, pl.wtn);
   return HRSEG_ERR_UNSUPPORTED;
 }
@@ -558,9 +362,10 @@ static void set_sp_scales(IgemmArgs& a, int precision, const float* grad_absmax)
 // the small ones; weight gradients: fp16x2 throughout
 static int resolve_auto(const IgemmArgs& a, int precision) {
   if (precision != HRSEG_CONV_AUTO) return precision;
-  if (a.M >= g_auto_min_pix) return HRSEG_CONV_FP16X2;
-  const int k = ws_kind(a);           // the wave-specialised patch body also wins on small images
-  return (k && ws_tiles(a, k) >= g_ws_min_tiles) ? HRSEG_CONV_FP16X2 : HRSEG_CONV_F32;
+  if (a.M >= hrseg_g_auto_min_pixels) return HRSEG_CONV_FP16X2;
+  // the wave-specialised patch body also wins on small images (ws_enabled, not ws_route_open: under an sp_wtn override such a
+  // problem keeps the fp16x2 arithmetic and runs it on the block-synchronous bodies)
+  return (ws_enabled() && ws_fit(a)) ? HRSEG_CONV_FP16X2 : HRSEG_CONV_F32;
 }
 
 // a pre-split pixel operand (hrseg_conv_shape_t.x_split) is readable by the wave-specialised forward kernels and the nine-tap
@@ -575,24 +380,19 @@ static int dispatch_igemm(const IgemmArgs& a_in, int precision, hipStream_t st) 
   precision = resolve_auto(a, precision);
   if (const int ns = sp_pieces(precision)) {
     const SpPlan pl = plan_sp(a);
-    if ((ns == 4 || (ns == 1 && g_ws_bf16)) && !g_sp_wtn) {
-      const int kind = ws_kind(a);
-      if (kind && ws_tiles(a, kind) >= g_ws_min_tiles && launch_ws_single(a, kind, st, ns) == 0) return 0;
+    if (ns == 4 || (ns == 1 && hrseg_g_sp_ws_bf16)) {
+      const int kind = ws_take(a);
+      if (kind && launch_ws_single(a, kind, st, ns) == 0) return 0;
     }
     if (a.x_presplit) return x_split_unsupported("hrseg_conv_fwd");
-    if (const int cs = patch_cs(a, pl.wtn)) {
-      const int rc = launch_patch_sp(ns, a, pl.wtn, cs, st);
-      if (rc == 0) return 0;
-    }
-    if (ns == 4 && !g_sp_wtn) {
-      // wide channel tiles + pre-split weights (igemm_spw_body): layers of at least 96 output channels on large images
-      const int wtn = spw_wtn(a);
-      if (wtn) {
-        const size_t bytes = (size_t)(a.N / (16 * wtn)) * ((a.ntaps * (a.K / 16) + 1) / 2) * (size_t)(2 * 16 * wtn * 64);
-        if (unsigned char* img = scratch_reserve(st, bytes)) {
-          ++g_cnt[CNT_SP_WIDE];
-          if (launch_spw_kernel(a, wtn, 1, img, st) == 0) return 0;
-        }
+    if (const int cs = patch_cs(a, pl.wtn))
+      if (launch_patch_sp(ns, a, pl.wtn, cs, st) == 0) return 0;
+    // wide channel tiles + pre-split weights (igemm_spw_body): layers of at least 96 output channels on large images
+    if (const int wtn = (ns == 4 && !hrseg_g_sp_wtn) ? spw_wtn(a) : 0) {
+      const size_t bytes = (size_t)(a.N / (16 * wtn)) * ((a.ntaps * (a.K / 16) + 1) / 2) * (size_t)(2 * 16 * wtn * 64);
+      if (unsigned char* img = scratch_reserve(st, bytes)) {
+        hrseg_count(CNT_SP_WIDE);
+        if (launch_spw_kernel(a, wtn, 1, img, st) == 0) return 0;
       }
     }
     if (pl.ksplit > 1 && !a.accumulate) zero_f32(a.y, (size_t)a.B * a.Hy * a.Wy * a.N, st);
@@ -601,19 +401,36 @@ static int dispatch_igemm(const IgemmArgs& a_in, int precision, hipStream_t st) 
   if (a.x_presplit) return x_split_unsupported("hrseg_conv_fwd");
   IgemmPlan pl = plan_igemm(a);
   if (pl.ksplit > 1 && !a.accumulate) zero_f32(a.y, (size_t)a.B * a.Hy * a.Wy * a.N, st);
-  if (launch_igemm_f32(a, pl, st) == 0) { ++g_cnt[CNT_F32]; return 0; }
+  if (launch_igemm_f32(a, pl, st) == 0) { hrseg_count(CNT_F32); return 0; }
   hrseg_set_error("igemm: no kernel for plan wtm=%d wtn=%d kc=%d db=%d", pl.wtm, pl.wtn, pl.kc, pl.db);
   return HRSEG_ERR_UNSUPPORTED;
+}
+// the problems one by one, after other launches of the same call went out: a positive return (nothing launched for this
+// problem) can no longer be handed up as "fall back", so it becomes a launch error
+static int issue_each(const IgemmArgs* a, int n, int precision, hipStream_t st) {
+  for (int i = 0; i < n; ++i)
+    if (int e = dispatch_igemm(a[i], precision, st)) return e < 0 ? e : HRSEG_ERR_LAUNCH;
+  return 0;
+}
+// splits a group into the problems the wave-specialised body takes (finalized, with their tilings) and the rest (as given);
+// false: a problem failed finalize_args (the per-problem launches report the error)
+static bool partition_ws(const IgemmArgs* a, int n, IgemmArgs* wsa, int* kinds, int& nw, IgemmArgs* rest, int& nr) {
+  nw = nr = 0;
+  for (int i = 0; i < n; ++i) {
+    IgemmArgs f = a[i];
+    if (finalize_args(f)) return false;
+    if (const int k = ws_take(f)) { wsa[nw] = f; kinds[nw++] = k; }
+    else rest[nr++] = a[i];
+  }
+  return true;
 }
 
 // group dispatch: one common plan (64-pixel tiles, widest K stage, single LDS buffer); problems whose
 // channel tiling differs from the first one's, or that need a zero-fill they cannot get, make the
 // caller fall back to per-problem launches (return 1).
-static int g_group_wtm = 0;     // tuning override of the grouped launches' pixel tile (0 = automatic, 1 = 64, 2 = 128 pixels)
-
 static int launch_sp_group(int ns, const IgemmGroup& g_in, int wtm, int wtn, int cs, hipStream_t st) {
   IgemmGroup g = g_in;
-  if (ns == 4 && cs && g_sp_img && ((wtn == 3 && cs == 3) || (wtn == 4 && cs == 4))) {
+  if (ns == 4 && cs && hrseg_g_sp_img && ((wtn == 3 && cs == 3) || (wtn == 4 && cs == 4))) {
     IgemmArgs im[MAXG];
     int kinds[MAXG], idx[MAXG], m = 0;
     for (int i = 0; i < g.n; ++i)
@@ -631,31 +448,31 @@ static int launch_sp_group(int ns, const IgemmGroup& g_in, int wtm, int wtn, int
         if (flip >= 0 && f != flip) return 1;
         flip = f;
       }
-    ++g_cnt[CNT_SP_PGROUP];
+    hrseg_count(CNT_SP_PGROUP);
     return launch_sp_pgroup_kernel(ns, g, wtm, wtn, cs, flip, st);
   }
-  ++g_cnt[CNT_SP_GROUP];
+  hrseg_count(CNT_SP_GROUP);
   return launch_sp_group_kernel(ns, g, wtm, wtn, full, st);
 }
 
 static int dispatch_igemm_group(const IgemmArgs* a, int n, int precision, hipStream_t st);
+// ... for the entry points: the grouped launch with its launch check (same contract)
+static int launch_group_checked(const IgemmArgs* a, int n, int precision, hipStream_t st, const char* what) {
+  const int rc = dispatch_igemm_group(a, n, precision, st);
+  if (rc == 0) HRSEG_LAUNCH_CHECK(what);
+  return rc;
+}
 // HRSEG_CONV_AUTO on a group: the problems the halo-patch body takes go out as one fp16x2 launch (a
 // low-resolution branch inside a patch launch would run at the patch body's occupancy); of the rest, the small ones
 // (< 8192 pixels) as one fp32 launch and the others one by one
 // Contract of the group dispatchers: 1 = nothing was launched (the caller issues the problems one by one), 0 = all launched,
 // negative = hard error after some launches went out (the caller must NOT re-issue: accumulating problems would add twice)
 static int dispatch_igemm_group_auto(const IgemmArgs* a, int n, hipStream_t st, bool try_ws = true) {
-  if (try_ws && g_sp_ws && scratch_usable() && !g_sp_wtn) {
+  if (try_ws && ws_route_open()) {
     // the problems the wave-specialised body takes go out as one launch of 256 persistent blocks; the rest as before
     IgemmArgs wsa[MAXG], rest[MAXG];
-    int kinds[MAXG], nw = 0, nr = 0;
-    for (int i = 0; i < n; ++i) {
-      IgemmArgs f = a[i];
-      if (finalize_args(f)) return 1;
-      const int k = ws_kind(f);
-      if (k && ws_tiles(f, k) >= g_ws_min_tiles) { wsa[nw] = f; kinds[nw++] = k; }
-      else rest[nr++] = a[i];
-    }
+    int kinds[MAXG], nw, nr;
+    if (!partition_ws(a, n, wsa, kinds, nw, rest, nr)) return 1;
     // (a lone taker next to a 48-channel high-resolution branch: the two share one halo-patch group launch instead,
     // measured 79 us against 41 + 49)
     bool pair = false;
@@ -667,12 +484,8 @@ static int dispatch_igemm_group_auto(const IgemmArgs* a, int n, hipStream_t st, 
     for (int i = 0; i < nr; ++i) split_rest = split_rest || rest[i].x_presplit;
     if (split_rest || (pair && (wsa[0].x_presplit))) return x_split_unsupported("hrseg_conv_fwd_group");
     if (nw >= 1 && !pair && launch_ws_group(wsa, kinds, nw, st) == 0) {
-      if (nr == 0) return 0;
-      if (nr == 1) { const int e = dispatch_igemm(rest[0], HRSEG_CONV_AUTO, st); return e < 0 ? e : (e ? HRSEG_ERR_LAUNCH : 0); }
-      if (dispatch_igemm_group_auto(rest, nr, st, false) == 0) return 0;
-      for (int i = 0; i < nr; ++i)
-        if (int e = dispatch_igemm(rest[i], HRSEG_CONV_AUTO, st)) return e < 0 ? e : HRSEG_ERR_LAUNCH;
-      return 0;
+      if (nr >= 2 && dispatch_igemm_group_auto(rest, nr, st, false) == 0) return 0;
+      return issue_each(rest, nr, HRSEG_CONV_AUTO, st);
     }
   }
   for (int i = 0; i < n; ++i)
@@ -688,58 +501,44 @@ static int dispatch_igemm_group_auto(const IgemmArgs* a, int n, hipStream_t st, 
   }
   if (nh == 0) {
     bool small = true, large = true;
-    for (int i = 0; i < n; ++i) { small = small && a[i].M < g_auto_min_pix; large = large && a[i].M >= g_auto_min_pix; }
+    for (int i = 0; i < n; ++i) { small = small && a[i].M < hrseg_g_auto_min_pixels; large = large && a[i].M >= hrseg_g_auto_min_pixels; }
     if (small) return dispatch_igemm_group(a, n, HRSEG_CONV_F32, st);
     if (large) return dispatch_igemm_group(a, n, HRSEG_CONV_FP16X2, st);
   }
   int rc = (nh >= 2) ? dispatch_igemm_group(hi, nh, HRSEG_CONV_FP16X2, st) : 1;
   if (rc != 0)
-    for (int i = 0; i < nh; ++i)
-      if (int e = dispatch_igemm(hi[i], HRSEG_CONV_FP16X2, st)) return e < 0 ? e : HRSEG_ERR_LAUNCH;
+    if (int e = issue_each(hi, nh, HRSEG_CONV_FP16X2, st)) return e;
   IgemmArgs sm[MAXG];
   int nsm = 0;
   for (int i = 0; i < nl; ++i) {
-    if (lo[i].M < g_auto_min_pix) { sm[nsm++] = lo[i]; continue; }
-    if (int e = dispatch_igemm(lo[i], HRSEG_CONV_FP16X2, st)) return e < 0 ? e : HRSEG_ERR_LAUNCH;
+    if (lo[i].M < hrseg_g_auto_min_pixels) { sm[nsm++] = lo[i]; continue; }
+    if (int e = issue_each(&lo[i], 1, HRSEG_CONV_FP16X2, st)) return e;
   }
   rc = (nsm >= 2) ? dispatch_igemm_group(sm, nsm, HRSEG_CONV_F32, st) : 1;
-  if (rc != 0)
-    for (int i = 0; i < nsm; ++i)
-      if (int e = dispatch_igemm(sm[i], HRSEG_CONV_F32, st)) return e < 0 ? e : HRSEG_ERR_LAUNCH;
-  return 0;
+  return rc != 0 ? issue_each(sm, nsm, HRSEG_CONV_F32, st) : 0;
 }
 
 static int dispatch_igemm_group(const IgemmArgs* a, int n, int precision, hipStream_t st) {
-  if (n < 2 || n > MAXG || g_tune_wtm || g_tune_kc || g_tune_db || g_tune_ksplit) return 1;
+  if (n < 2 || n > MAXG || igemm_overridden()) return 1;
   if (precision == HRSEG_CONV_AUTO) return dispatch_igemm_group_auto(a, n, st);
   for (int i = 0; i < n; ++i)
     if (a[i].x_presplit) return x_split_unsupported("hrseg_conv_fwd_group");
   const int ns = sp_pieces(precision);
-  if (ns == 1 && g_ws_bf16 && g_sp_ws && scratch_usable() && !g_sp_wtn) {
+  if (ns == 1 && hrseg_g_sp_ws_bf16 && ws_route_open()) {
     // bf16 arithmetic (BASELINE configs[4]): the problems the wave-specialised body takes go out as one launch of its
-    // one-piece instance, the rest as before
+    // one-piece instance, the rest one by one
     IgemmArgs wsa[MAXG], rest[MAXG];
-    int kinds[MAXG], nw = 0, nr = 0;
-    for (int i = 0; i < n; ++i) {
-      IgemmArgs f = a[i];
-      if (finalize_args(f)) return 1;
-      const int k = ws_kind(f);
-      if (k && ws_tiles(f, k) >= g_ws_min_tiles) { wsa[nw] = f; kinds[nw++] = k; }
-      else rest[nr++] = a[i];
-    }
-    if (nw >= 1 && launch_ws_group(wsa, kinds, nw, st, 1) == 0) {
-      for (int i = 0; i < nr; ++i)
-        if (int e = dispatch_igemm(rest[i], precision, st)) return e < 0 ? e : HRSEG_ERR_LAUNCH;
-      return 0;
-    }
+    int kinds[MAXG], nw, nr;
+    if (!partition_ws(a, n, wsa, kinds, nw, rest, nr)) return 1;
+    if (nw >= 1 && launch_ws_group(wsa, kinds, nw, st, 1) == 0) return issue_each(rest, nr, precision, st);
   }
   int wtn = (a[0].N % 48 == 0) ? 3 : (a[0].N % 64 == 0) ? 4 : 0;
   const int kc = ns ? 1 : (a[0].K % 48 == 0) ? 3 : (a[0].K % 32 == 0) ? 2 : 1;
   if (!wtn) return 1;
-  if (ns && g_sp_wtn) {
+  if (ns && hrseg_g_sp_wtn) {
     bool ok = true;
-    for (int i = 0; i < n; ++i) ok = ok && a[i].N % (16 * g_sp_wtn) == 0;
-    if (ok && (g_sp_wtn == 3 || g_sp_wtn == 4 || g_sp_wtn == 6)) wtn = g_sp_wtn;
+    for (int i = 0; i < n; ++i) ok = ok && a[i].N % (16 * hrseg_g_sp_wtn) == 0;
+    if (ok && (hrseg_g_sp_wtn == 3 || hrseg_g_sp_wtn == 4 || hrseg_g_sp_wtn == 6)) wtn = hrseg_g_sp_wtn;
   }
   IgemmGroup g;
   g.n = n;
@@ -748,7 +547,7 @@ static int dispatch_igemm_group(const IgemmArgs* a, int n, int precision, hipStr
   // per-problem split-K, then order the problems by stages per block, longest first: the blocks
   // that run longest must not be the ones dispatched last (the grid's tail)
   int tiles[MAXG], ks[MAXG], work[MAXG], order[MAXG], kind[MAXG];
-  const int wtm = ns ? (g_sp_wtm ? g_sp_wtm : 2) : (g_group_wtm ? g_group_wtm : 1);
+  const int wtm = ns ? (hrseg_g_sp_wtm ? hrseg_g_sp_wtm : 2) : (hrseg_g_group_wtm ? hrseg_g_group_wtm : 1);
   if (ns && wtm > 2) return 1;
   int group_cs = 0;
   IgemmArgs fa[MAXG];
@@ -791,11 +590,9 @@ static int dispatch_igemm_group(const IgemmArgs* a, int n, int precision, hipStr
     g.a[o] = fa[i];
   }
   if (ns) return launch_sp_group(ns, g, wtm, wtn, group_cs, st);
-  ++g_cnt[CNT_F32_GROUP];
+  hrseg_count(CNT_F32_GROUP);
   return launch_igemm_group_f32(g, wtm, wtn, kc, st);
 }
-
-static int g_tune_wg_pix = 0, g_tune_wg_db = 0, g_tune_wg_blocks = 0;
 
 // host-side check behind the 32-bit buffer offsets of wgrad_body: one block's pixel range
 int check_wgrad_span(const WgradArgs& a) {
@@ -807,8 +604,6 @@ int check_wgrad_span(const WgradArgs& a) {
   return 0;
 }
 
-static int g_wg_t5 = 1;                // hrseg_tune "wgrad_sp_t5": 0 = no 80 x 80 tiles in the tap-per-block weight gradient
-static int g_wg_wide = 1;              // hrseg_tune "wgrad_sp_wide": 0 = never the wide-tile weight-gradient body
 // pixel ranges per tile set such that the blocks fill whole rounds of `slots` (one block per CU): the k in [kmin, kmax] with the
 // best fill, the smallest such k on ties
 static int ksplit_for_rounds(int tiles, int kmin, int kmax, int slots) {
@@ -821,16 +616,18 @@ static int ksplit_for_rounds(int tiles, int kmin, int kmax, int slots) {
   }
   return best;
 }
+// tap-per-block weight gradients, automatic grid (tools/wgrad_sweep.py): ~7 blocks per output tile set, between 2 and 16 per CU
+static int wgrad_target_blocks(int tiles) { return 7 * tiles < 512 ? 512 : 7 * tiles > 4096 ? 4096 : 7 * tiles; }
 static int dispatch_wgrad_sp(int ns, WgradArgs a, hipStream_t st) {
   // wide layers whose channels divide into 240 x 144 block tiles (the 720 -> 720 head layer): wgrad_spw_body
-  if (ns == 4 && g_wg_wide && a.Cout % 240 == 0 && a.Cin % 144 == 0 && a.M >= 65536 && !hrseg_g_deterministic && !g_tune_wg_blocks) {
+  if (ns == 4 && hrseg_g_wgrad_sp_wide && a.Cout % 240 == 0 && a.Cin % 144 == 0 && a.M >= 65536 && !hrseg_g_deterministic && !hrseg_g_wgrad_blocks) {
     const int tiles = (a.Cout / 240) * (a.Cin / 144) * a.T;
     int kmax = a.M / 2048;                       // at least 64 stages of 32 pixels per block
     if (kmax > 64) kmax = 64;
     const int ksplit = ksplit_for_rounds(tiles, 1, kmax, 256);
     a.pix_per_block = ceil_div(ceil_div(a.M, ksplit), 32) * 32;
     if (int e = check_wgrad_span(a)) return e;
-    ++g_cnt[CNT_WGRAD_SP_WIDE];
+    hrseg_count(CNT_WGRAD_SP_WIDE);
     return launch_wgrad_spw_kernel(a, ceil_div(a.M, a.pix_per_block), tiles, st);
   }
   int tn = (a.Cout % 48 == 0) ? 3 : (a.Cout % 64 == 0) ? 4 : (a.Cout % 32 == 0) ? 2 : 1;
@@ -840,18 +637,16 @@ static int dispatch_wgrad_sp(int ns, WgradArgs a, hipStream_t st) {
   // per wave and 32 pixels next to tn * tk * 3 MFMAs: at 48 x 48 the split outweighs the MFMAs (MFMA-busy 0.19) and every
   // operand row is pulled Cin / 48 resp. Cout / 48 = 15 times through L2; at 80 x 80 it is 120 VALU : 75 MFMAs and 9 pulls.
   // One block per CU (80 KB of LDS): the pixel ranges are sized so that the blocks fill whole rounds of 256.
-  const bool t5 = ns == 4 && g_wg_t5 && a.Cout % 80 == 0 && a.Cin % 80 == 0 && (long)a.Cout * a.Cin >= 240 * 240 && a.M >= 65536;
+  const bool t5 = ns == 4 && hrseg_g_wgrad_sp_t5 && a.Cout % 80 == 0 && a.Cin % 80 == 0 && (long)a.Cout * a.Cin >= 240 * 240 && a.M >= 65536;
   if (t5) tn = tk = 5;
   const int tiles = (a.Cout / (16 * tn)) * (a.Cin / (16 * tk)) * a.T;
-  int target = 7 * tiles;
-  if (target < 512) target = 512;
-  if (target > 4096) target = 4096;
+  int target = wgrad_target_blocks(tiles);
   if (t5) {
     int kmax = a.M / (PIX * 8);
     if (kmax > 32) kmax = 32;
     if (const int best = ksplit_for_rounds(tiles, 4, kmax, 256)) target = best * tiles;
   }
-  if (g_tune_wg_blocks) target = g_tune_wg_blocks;
+  if (hrseg_g_wgrad_blocks) target = hrseg_g_wgrad_blocks;
   int ksplit = target / tiles;
   if (ksplit < 1 || hrseg_g_deterministic) ksplit = 1;
   int ppb = ceil_div(ceil_div(a.M, ksplit), PIX) * PIX;
@@ -859,19 +654,18 @@ static int dispatch_wgrad_sp(int ns, WgradArgs a, hipStream_t st) {
   a.pix_per_block = ppb;
   if (int e = check_wgrad_span(a)) return e;
   const int gx = ceil_div(a.M, ppb);
-  ++g_cnt[CNT_WGRAD_SP];
-  g_cnt[CNT_WGRAD_SP_T5] += t5;      // ("wgrad_sp" launches that used 80 x 80 tiles)
+  hrseg_count(CNT_WGRAD_SP);
+  hrseg_count(CNT_WGRAD_SP_T5, t5);      // ("wgrad_sp" launches that used 80 x 80 tiles)
   return launch_wgrad_sp_kernel(ns, a, tn, tk, gx, tiles, st);
 }
 
-static int g_wg_mult = 0, g_wg_min = 0, g_wg_max = 0;      // tuning overrides of the grouped weight-gradient grid
 static void plan_wgrad_blocks(WgradArgs& a, int tn, int tk, int pix, int& gx, int& tiles) {
   tiles = (a.Cout / (16 * tn)) * (a.Cin / (16 * tk)) * a.T;
   // measured (tools/wgrad_group_plan.py, groups of 2-4 branch convs at 4 and 8 images): 2 pixel ranges per tile
   // set, at least 768 and at most 2048 blocks per problem -- 7 ranges per tile set left the 384-channel
   // problem with 4032 blocks of 8 stages whose cross-wave reduction and atomics cost as much as their MFMAs
-  int target = (g_wg_mult ? g_wg_mult : 2) * tiles;
-  const int tmin = g_wg_min ? g_wg_min : 768, tmax = g_wg_max ? g_wg_max : 2048;
+  int target = (hrseg_g_wgrad_group_mult ? hrseg_g_wgrad_group_mult : 2) * tiles;
+  const int tmin = hrseg_g_wgrad_group_min ? hrseg_g_wgrad_group_min : 768, tmax = hrseg_g_wgrad_group_max ? hrseg_g_wgrad_group_max : 2048;
   if (target < tmin) target = tmin;
   if (target > tmax) target = tmax;
   int ksplit = target / tiles;
@@ -883,10 +677,9 @@ static void plan_wgrad_blocks(WgradArgs& a, int tn, int tk, int pix, int& gx, in
 }
 
 // returns 1 when the problems cannot share one kernel instance (caller falls back)
-static int g_wg_group_sp = 1;          // hrseg_tune "wgrad_group_sp": 0 = grouped tap-per-block weight gradients stay on the fp32 kernel
 static int dispatch_wgrad_group(WgradArgs* a, int n, int prec, hipStream_t st) {
-  if (n < 2 || n > MAXG || g_tune_wg_pix || g_tune_wg_db || g_tune_wg_blocks) return 1;
-  const bool sp = prec == HRSEG_CONV_FP16X2 && g_wg_group_sp;       // every problem asked for fp16x2 (AUTO resolves to it)
+  if (n < 2 || n > MAXG || hrseg_g_wgrad_pix || hrseg_g_wgrad_db || hrseg_g_wgrad_blocks) return 1;
+  const bool sp = prec == HRSEG_CONV_FP16X2 && hrseg_g_wgrad_group_sp;       // every problem asked for fp16x2 (AUTO resolves to it)
   const int tn = (a[0].Cout % 48 == 0) ? 3 : (a[0].Cout % 64 == 0) ? 4 : 0;
   const int tk = (a[0].Cin % 48 == 0) ? 3 : (a[0].Cin % 64 == 0) ? 4 : 0;
   if (!tn || !tk) return 1;
@@ -904,20 +697,17 @@ static int dispatch_wgrad_group(WgradArgs* a, int n, int prec, hipStream_t st) {
     g.a[i] = a[i];
   }
   if (sp) {
-    ++g_cnt[CNT_WGRAD_SP_GROUP];
+    hrseg_count(CNT_WGRAD_SP_GROUP);
     return launch_wgrad_group_sp(g, tn, tk, end, st);
   }
-  ++g_cnt[CNT_WGRAD_F32_GROUP];
+  hrseg_count(CNT_WGRAD_F32_GROUP);
   return launch_wgrad_group_f32(g, tn, tk, end, st);
 }
 
 // --------------------------------------------------------------------------- nine-tap weight gradient (workspace + ordered reduce)
-static int g_wg9_blocks = 0;           // hrseg_tune "wgrad9_blocks": target blocks per problem (0 = the table below)
-static int g_wg9_blocks_n[WG9_MAXG + 1] = {0, 0, 0, 0, 0};   // hrseg_tune "wgrad9_blocks1" .. "wgrad9_blocks4": the same, per group size
-static int g_wg9 = 1;                  // hrseg_tune "wgrad9": 0 = never use the nine-tap kernel
 // tiles per side of the dW tile (3: channels multiple of 48, 4: multiple of 64), 0 = not a nine-tap case
 static int wgrad9_tnk(const hrseg_conv_shape_t& s) {
-  if (!g_wg9 || s.ksize != 3 || s.stride != 1 || sp_pieces(s.precision) == 0) return 0;
+  if (!hrseg_g_wgrad9 || s.ksize != 3 || s.stride != 1 || sp_pieces(s.precision) == 0) return 0;
   if (s.Cin % 48 == 0 && s.Cout % 48 == 0) return 3;
   if (s.Cin % 64 == 0 && s.Cout % 64 == 0) return 4;
   return 0;
@@ -934,7 +724,9 @@ static void wgrad9_plan(const hrseg_conv_shape_t& s, int tnk, Wgrad9Args& a, int
   a.tiles_x = ceil_div(s.Wi, 16); a.tiles_y = ceil_div(s.Hi, 4);
   a.ntiles = s.B * a.tiles_x * a.tiles_y;
   const int npairs = (s.Cout / (16 * tnk)) * (s.Cin / (16 * tnk));
-  const int target = g_wg9_blocks_n[group_n] ? g_wg9_blocks_n[group_n] : g_wg9_blocks ? g_wg9_blocks : WG9_TARGET[group_n < 4 ? group_n : 4];
+  // (hrseg_tune wgrad9_blocks1 .. wgrad9_blocks4 override the target for a call of that many problems, wgrad9_blocks for any)
+  const int by_n[5] = {0, hrseg_g_wgrad9_blocks1, hrseg_g_wgrad9_blocks2, hrseg_g_wgrad9_blocks3, hrseg_g_wgrad9_blocks4};
+  const int target = (group_n <= 4 && by_n[group_n]) ? by_n[group_n] : hrseg_g_wgrad9_blocks ? hrseg_g_wgrad9_blocks : WG9_TARGET[group_n < 4 ? group_n : 4];
   int chunks = ceil_div(target, npairs);
   if (chunks > a.ntiles) chunks = a.ntiles;
   if (chunks < 1) chunks = 1;
@@ -961,11 +753,13 @@ static size_t wgrad9_ws_bytes(int n, const hrseg_conv_shape_t* shapes) {
   for (int i = 0; i < n; ++i) total += (size_t)pl.a[i].nchunks * shapes[i].Cout * 9 * shapes[i].Cin * 4;
   return total;
 }
+// the nine-tap kernel reads a pre-split pixel operand in its fp16x2 instance only (the pre-split form IS fp16x2's)
+static bool wgrad9_reads_x_split(int precision) { return sp_pieces(precision) == 4; }
 static int dispatch_wgrad9(int n, const float* const* x, const float* const* dy, float* const* dw,
                            const hrseg_conv_shape_t* shapes, float* ws, hipStream_t st) {
   const int ns = sp_pieces(shapes[0].precision);
   for (int i = 0; i < n; ++i)
-    if (shapes[i].x_split && ns != 4) return x_split_unsupported("hrseg_conv_wgrad_group_ws");
+    if (shapes[i].x_split && !wgrad9_reads_x_split(shapes[0].precision)) return x_split_unsupported("hrseg_conv_wgrad_group_ws");
   Wg9Plan pl;
   if (!wgrad9_plan_all(n, shapes, pl)) return HRSEG_ERR_UNSUPPORTED;      // (the caller asked wgrad9_ws_bytes first)
   const int tnk = pl.tnk;
@@ -976,7 +770,7 @@ static int dispatch_wgrad9(int n, const float* const* x, const float* const* dy,
   for (int i = 0; i < n; ++i) {
     Wgrad9Args& a = pl.a[i];
     a.x = x[i]; a.dy = dy[i]; a.ws = ws;
-    a.exp_nosplit = g_exp_nosplit;
+    a.exp_nosplit = hrseg_g_exp_nosplit_x;
     a.x_presplit = shapes[i].x_split;
     a.dymax = shapes[i].precision == HRSEG_CONV_FP16X2 ? shapes[i].grad_absmax : nullptr;
     HRSEG_CHECK_ARG((double)shapes[i].Hi * shapes[i].Wi * (double)(shapes[i].ldx > shapes[i].ldy ? shapes[i].ldx : shapes[i].ldy) * 4.0 < 4294967296.0,
@@ -990,7 +784,7 @@ static int dispatch_wgrad9(int n, const float* const* x, const float* const* dy,
     r.blk_end[i] = rend;
     ws += (size_t)a.nchunks * elems;
   }
-  ++g_cnt[CNT_WGRAD9];
+  hrseg_count(CNT_WGRAD9);
   return launch_wgrad9_kernels(ns, tnk, g, end, r, rend, st);
 }
 
@@ -1086,21 +880,28 @@ static void fill_fwd_args(IgemmArgs& a, const float* x, const float* w, const fl
   }
 }
 
-// stride-1 data gradient as a forward-style gather over dy with the transposed weights
-static void fill_dgrad_s1_args(IgemmArgs& a, const float* dy, const float* wt, float* dx, int accumulate,
-                               const hrseg_conv_shape_t* s) {
+// data gradient as a forward-style gather over dy (the GEMM input) with the transposed weights: what every such problem
+// shares; the iteration grid, its place in dx and the taps are the caller's
+static void fill_dgrad_base(IgemmArgs& a, const float* dy, const float* wt, float* dx, int accumulate,
+                            const hrseg_conv_shape_t* s) {
   a = IgemmArgs{};
   a.x = dy; a.w = wt; a.bias = nullptr; a.y = dx; a.ldx = s->ldy; a.ldy = s->ldx;
   a.B = s->B; a.Hi = s->Ho; a.Wi = s->Wo; a.K = s->Cout;
   a.N = s->Cin; a.T = s->ksize * s->ksize; a.accumulate = accumulate;
   a.Hy = s->Hi; a.Wy = s->Wi;
+  a.sy = a.sx = 1;
+  set_sp_scales(a, s->precision, s->grad_absmax);
+}
+// stride 1: every pixel of dx, all taps mirrored
+static void fill_dgrad_s1_args(IgemmArgs& a, const float* dy, const float* wt, float* dx, int accumulate,
+                               const hrseg_conv_shape_t* s) {
+  fill_dgrad_base(a, dy, wt, dx, accumulate, s);
   a.Ho = s->Hi; a.Wo = s->Wi; a.M = s->B * s->Hi * s->Wi;
-  a.sy = a.sx = 1; a.oys = a.oxs = 1; a.oy0 = a.ox0 = 0;
+  a.oys = a.oxs = 1; a.oy0 = a.ox0 = 0;
   const int ks = s->ksize, pad = (ks - 1) / 2;
   int oy[9], ox[9], wtp[9];
   for (int t = 0; t < a.T; ++t) { oy[t] = pad - t / ks; ox[t] = pad - t % ks; wtp[t] = t; }
   pack_taps(a, a.T, oy, ox, wtp);
-  set_sp_scales(a, s->precision, s->grad_absmax);
   a.w_persistent = s->w_persistent;
 }
 
@@ -1140,12 +941,8 @@ extern "C" int hrseg_conv_fwd_group(int n, const float* const* x, const float* c
   if (ok && n >= 2) {
     IgemmArgs a[MAXG];
     for (int i = 0; i < n; ++i) fill_fwd_args(a[i], x[i], w[i], bias ? bias[i] : nullptr, y[i], &shapes[i]);
-    const int rc = dispatch_igemm_group(a, n, shapes[0].precision, st);
-    if (rc < 0) return rc;
-    if (rc == 0) {
-      HRSEG_LAUNCH_CHECK("igemm_group(fwd)");
-      return 0;
-    }
+    const int rc = launch_group_checked(a, n, shapes[0].precision, st, "igemm_group(fwd)");
+    if (rc <= 0) return rc;
   }
   for (int i = 0; i < n; ++i)
     if (int e = hrseg_conv_fwd(x[i], w[i], bias ? bias[i] : nullptr, y[i], &shapes[i], stream)) return e;
@@ -1165,12 +962,8 @@ extern "C" int hrseg_conv_dgrad_group(int n, const float* const* dy, const float
   if (ok && n >= 2) {
     IgemmArgs a[MAXG];
     for (int i = 0; i < n; ++i) fill_dgrad_s1_args(a[i], dy[i], wt[i], dx[i], accumulate[i], &shapes[i]);
-    const int rc = dispatch_igemm_group(a, n, shapes[0].precision, st);
-    if (rc < 0) return rc;
-    if (rc == 0) {
-      HRSEG_LAUNCH_CHECK("igemm_group(dgrad)");
-      return 0;
-    }
+    const int rc = launch_group_checked(a, n, shapes[0].precision, st, "igemm_group(dgrad)");
+    if (rc <= 0) return rc;
   }
   for (int i = 0; i < n; ++i)
     if (int e = hrseg_conv_dgrad(dy[i], wt[i], dx[i], accumulate[i], &shapes[i], stream)) return e;
@@ -1216,13 +1009,14 @@ extern "C" size_t hrseg_conv_wgrad_workspace_bytes(int n, const hrseg_conv_shape
   return wgrad9_ws_bytes(n, shapes);
 }
 
-static int g_x_split = 1;              // hrseg_tune "x_split": 0 = hrseg_conv_x_split_ok always answers no (activations stay fp32 everywhere)
-// Mirrors the routing of hrseg_conv_fwd(_group) and hrseg_conv_wgrad_group_ws for these shapes: yes only when EVERY problem of
-// the forward call goes out through the wave-specialised kernels (fp16x2 arithmetic) and the weight gradients through the
-// nine-tap kernel.  The calls themselves refuse x_split on any other route, so a mismatch is an error, never a misread tensor.
+// Yes only when EVERY problem of the forward call goes out through the wave-specialised kernels (fp16x2 arithmetic) and the
+// weight gradients through the nine-tap kernel.  It asks the predicates hrseg_conv_fwd(_group) and hrseg_conv_wgrad_group_ws
+// route by (ws_take, igemm_overridden, wgrad9_ws_bytes, wgrad9_reads_x_split) and adds only what is its own: which calls it
+// vouches for.  The calls themselves refuse x_split on any other route, so a mismatch is an error, never a misread tensor.
 extern "C" int hrseg_conv_x_split_ok(int n, const hrseg_conv_shape_t* shapes) {
-  if (!g_x_split || !shapes || n < 1 || n > MAXG || n > WG9_MAXG) return 0;
-  if (!g_sp_ws || !scratch_usable() || g_sp_wtn || g_tune_wtm || g_tune_kc || g_tune_db || g_tune_ksplit) return 0;
+  if (!hrseg_g_x_split || !shapes || n < 1 || n > MAXG || n > WG9_MAXG) return 0;
+  // (the overrides make a grouped call issue its problems one by one: not vouched for, whatever n)
+  if (!ws_route_open() || igemm_overridden()) return 0;
   for (int i = 0; i < n; ++i) {
     const hrseg_conv_shape_t& s = shapes[i];
     if (s.ksize != 3 || s.stride != 1 || s.residual || s.relu || !mfma_shape(&s) || s.precision != shapes[0].precision) return 0;
@@ -1231,14 +1025,12 @@ extern "C" int hrseg_conv_x_split_ok(int n, const hrseg_conv_shape_t* shapes) {
     IgemmArgs a;
     fill_fwd_args(a, reinterpret_cast<const float*>(256), reinterpret_cast<const float*>(256), nullptr, reinterpret_cast<float*>(256), &s);
     a.stat_partial = nullptr; a.stat_rows = nullptr;
-    if (finalize_args(a)) return 0;
-    const int k = ws_kind(a);
-    if (!k || ws_tiles(a, k) < g_ws_min_tiles) return 0;
+    if (finalize_args(a) || !ws_take(a)) return 0;
   }
   hrseg_conv_shape_t rs[WG9_MAXG];
   resolve_wgrad_shapes(n, shapes, rs);
   for (int i = 0; i < n; ++i)
-    if (sp_pieces(rs[i].precision) != 4) return 0;
+    if (!wgrad9_reads_x_split(rs[i].precision)) return 0;
   return wgrad9_ws_bytes(n, rs) > 0 ? 1 : 0;
 }
 
@@ -1267,7 +1059,7 @@ extern "C" int hrseg_conv_fwd(const float* x, const float* w, const float* bias,
   HRSEG_CHECK_ARG(s->Cout % 16 == 0 || s->Cin <= HRSEG_SMALL_CIN_MAX, "hrseg_conv_fwd: Cout %d not a multiple of 16", s->Cout);
   if (s->Cin <= HRSEG_SMALL_CIN_MAX) {
     launch_small_cin_fwd(x, w, bias, y, s, st);
-    ++g_cnt[CNT_SMALL_CIN];
+    hrseg_count(CNT_SMALL_CIN);
     HRSEG_LAUNCH_CHECK("conv_small_cin_fwd");
     return 0;
   }
@@ -1287,7 +1079,7 @@ extern "C" int hrseg_conv_dgrad(const float* dy, const float* wt, float* dx, int
   if (s->Cin <= HRSEG_SMALL_CIN_MAX) {
     // first layer with a differentiable input (logit-concatenated re-encoding): `wt` is the FORWARD weight [Cout][k*k][Cin]
     launch_small_cin_dgrad(dy, wt, dx, accumulate, s, (hipStream_t)stream);
-    ++g_cnt[CNT_SMALL_CIN];
+    hrseg_count(CNT_SMALL_CIN);
     HRSEG_LAUNCH_CHECK("conv_small_cin_dgrad");
     return 0;
   }
@@ -1295,25 +1087,20 @@ extern "C" int hrseg_conv_dgrad(const float* dy, const float* wt, float* dx, int
                   s->Cin, s->Cout);
   HRSEG_CHECK_ARG(s->ldx % 4 == 0 && s->ldy % 4 == 0, "hrseg_conv_dgrad: ld must be a multiple of 4");
   hipStream_t st = (hipStream_t)stream;
-  IgemmArgs a{};
-  a.x = dy; a.w = wt; a.bias = nullptr; a.y = dx; a.ldx = s->ldy; a.ldy = s->ldx;
-  a.B = s->B; a.Hi = s->Ho; a.Wi = s->Wo; a.K = s->Cout;  // GEMM input = dy
-  a.N = s->Cin; a.T = s->ksize * s->ksize; a.accumulate = accumulate;
-  a.Hy = s->Hi; a.Wy = s->Wi;
-  set_sp_scales(a, s->precision, s->grad_absmax);
-  const int ks = s->ksize, pad = (ks - 1) / 2;
+  IgemmArgs a;
   if (s->stride == 1) {
-    a.Ho = s->Hi; a.Wo = s->Wi; a.M = s->B * s->Hi * s->Wi;
-    a.sy = a.sx = 1; a.oys = a.oxs = 1; a.oy0 = a.ox0 = 0;
-    int oy[9], ox[9], wtp[9];
-    for (int t = 0; t < a.T; ++t) { oy[t] = pad - t / ks; ox[t] = pad - t % ks; wtp[t] = t; }
-    pack_taps(a, a.T, oy, ox, wtp);
+    fill_dgrad_s1_args(a, dy, wt, dx, accumulate, s);
+    // This entry point does not pass w_persistent on (the grouped one does): a single data gradient builds its weight
+    // image in the scratch ring at every call and registers nothing in the caller's arena.
+    a.w_persistent = 0;
     if (int e = dispatch_igemm(a, s->precision, st)) return e;
     HRSEG_LAUNCH_CHECK("igemm_conv(dgrad)");
     return 0;
   }
   // stride 2: dx[y,x] = sum_{kh,kw : (y+pad-kh) even, (x+pad-kw) even} dy[(y+pad-kh)/2, (x+pad-kw)/2] w[kh,kw]
   // The four output-parity classes write disjoint pixels of dx: one grouped launch.
+  fill_dgrad_base(a, dy, wt, dx, accumulate, s);
+  const int ks = s->ksize, pad = (ks - 1) / 2;
   IgemmArgs cls[4];
   int ncls = 0;
   for (int py = 0; py < 2; ++py)
@@ -1332,17 +1119,13 @@ extern "C" int hrseg_conv_dgrad(const float* dy, const float* wt, float* dx, int
         }
       IgemmArgs c = a;
       c.Ho = hc; c.Wo = wc; c.M = s->B * hc * wc;
-      c.sy = c.sx = 1; c.oys = c.oxs = 2; c.oy0 = py; c.ox0 = px;
+      c.oys = c.oxs = 2; c.oy0 = py; c.ox0 = px;
       pack_taps(c, n, oy, ox, wtp);
       cls[ncls++] = c;
     }
   if (ncls >= 2) {
-    const int rc = dispatch_igemm_group(cls, ncls, s->precision, st);
-    if (rc < 0) return rc;
-    if (rc == 0) {
-      HRSEG_LAUNCH_CHECK("igemm_group(dgrad s2)");
-      return 0;
-    }
+    const int rc = launch_group_checked(cls, ncls, s->precision, st, "igemm_group(dgrad s2)");
+    if (rc <= 0) return rc;
   }
   for (int i = 0; i < ncls; ++i) {
     if (int e = dispatch_igemm(cls[i], s->precision, st)) return e;
@@ -1361,29 +1144,22 @@ extern "C" int hrseg_conv_wgrad(const float* x, const float* dy, float* dw, cons
   if (int e = check_shape(s, "hrseg_conv_wgrad")) return e;
   HRSEG_CHECK_ARG(x && dy && dw, "hrseg_conv_wgrad: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  const int T = s->ksize * s->ksize;
   if (s->Cin <= HRSEG_SMALL_CIN_MAX) {
     const long M = (long)s->B * s->Ho * s->Wo;
     // ~512 blocks (measured, tools/misc_bench.py): every block adds into the same Cout*T*Cin
     // addresses, ~0.35 us of serialized atomics per block; fewer blocks leave CUs idle
-    const int nblk_target = hrseg_g_deterministic ? 1 : g_tune_wg_blocks ? g_tune_wg_blocks : 512;
+    const int nblk_target = hrseg_g_deterministic ? 1 : hrseg_g_wgrad_blocks ? hrseg_g_wgrad_blocks : 512;
     int ppb = (int)ceil_div(ceil_div(M, nblk_target), 64) * 64;
     launch_small_cin_wgrad(x, dy, dw, s, ppb, st);
-    ++g_cnt[CNT_SMALL_CIN];
+    hrseg_count(CNT_SMALL_CIN);
     HRSEG_LAUNCH_CHECK("conv_small_cin_wgrad");
     return 0;
   }
   HRSEG_CHECK_ARG(s->Cin % 16 == 0 && s->Cout % 16 == 0, "hrseg_conv_wgrad: channels (%d,%d) must be multiples of 16",
                   s->Cin, s->Cout);
   HRSEG_CHECK_ARG(s->ldx % 4 == 0 && s->ldy % 4 == 0, "hrseg_conv_wgrad: ld must be a multiple of 4");
-  WgradArgs a{};
-  a.x = x; a.dy = dy; a.dw = dw; a.ldx = s->ldx; a.lddy = s->ldy;
-  a.B = s->B; a.Hi = s->Hi; a.Wi = s->Wi; a.Cin = s->Cin; a.Ho = s->Ho; a.Wo = s->Wo; a.Cout = s->Cout;
-  a.M = s->B * s->Ho * s->Wo; a.ks = s->ksize; a.stride = s->stride; a.T = T;
-  const bool big = (long)s->B * s->Ho * s->Wo >= (1L << 24);   // float-reciprocal division is exact below 2^24
-  a.rcp_hw = big ? 0.f : 1.0f / (float)(s->Ho * s->Wo);
-  a.rcp_w = big ? 0.f : 1.0f / (float)s->Wo;
-  a.dymax = s->precision == HRSEG_CONV_FP16X2 ? s->grad_absmax : nullptr;
+  WgradArgs a;
+  fill_wgrad_args(a, x, dy, dw, s);
   if (const int ns = sp_pieces(s->precision)) {
     if (int e = dispatch_wgrad_sp(ns, a, st)) return e;
     HRSEG_LAUNCH_CHECK("wgrad_sp");
@@ -1391,19 +1167,12 @@ extern "C" int hrseg_conv_wgrad(const float* x, const float* dy, float* dw, cons
   }
   const int tn = (s->Cout % 48 == 0) ? 3 : (s->Cout % 64 == 0) ? 4 : (s->Cout % 32 == 0) ? 2 : 1;
   const int tk = (s->Cin % 48 == 0) ? 3 : (s->Cin % 64 == 0) ? 4 : (s->Cin % 32 == 0) ? 2 : 1;
-  {
-    // measured (tools/wgrad_sweep.py): 64-pixel stages, single LDS buffer; grid of ~7 blocks per
-    // output tile set, between 2 and 16 blocks per CU
-    const int tiles = (a.Cout / (16 * tn)) * (a.Cin / (16 * tk)) * a.T;
-    int pix = 64, db = 1, target = 7 * tiles;
-    if (target < 512) target = 512;
-    if (target > 4096) target = 4096;
-    if (g_tune_wg_pix) pix = g_tune_wg_pix;
-    if (g_tune_wg_db) db = g_tune_wg_db;
-    if (g_tune_wg_blocks) target = g_tune_wg_blocks;
-    if (int e = launch_wgrad_f32(a, tn, tk, pix, db, target, st)) return e;
-    ++g_cnt[CNT_WGRAD_F32];
-  }
+  // measured (tools/wgrad_sweep.py): 64-pixel stages, single LDS buffer
+  const int tiles = (a.Cout / (16 * tn)) * (a.Cin / (16 * tk)) * a.T;
+  const int pix = hrseg_g_wgrad_pix ? hrseg_g_wgrad_pix : 64, db = hrseg_g_wgrad_db ? hrseg_g_wgrad_db : 1;
+  const int target = hrseg_g_wgrad_blocks ? hrseg_g_wgrad_blocks : wgrad_target_blocks(tiles);
+  if (int e = launch_wgrad_f32(a, tn, tk, pix, db, target, st)) return e;
+  hrseg_count(CNT_WGRAD_F32);
   HRSEG_LAUNCH_CHECK("wgrad");
   return 0;
 }
@@ -1424,33 +1193,5 @@ extern "C" int hrseg_weight_transpose_all(const float* flat, float* flat_t, cons
                      table);
   HRSEG_LAUNCH_CHECK("weight_transpose_all");
   return 0;
-}
-
-// --------------------------------------------------------------------------- tuning knobs
-// One entry point for the tile-plan overrides the sweep tools under tools/ use (0 = automatic plan):
-//   igemm_wtm / igemm_kc / igemm_db / igemm_ksplit   fp32 implicit GEMM: pixel tiles per wave (1,2,4; +10 = 96-channel
-//                                                     tiles), 16-channel chunks per stage, LDS buffers, split-K factor
-//   group_wtm                                         grouped launches: 1 = 64-pixel, 2 = 128-pixel tiles
-//   wgrad_pix / wgrad_db / wgrad_blocks               weight gradient: pixels per stage, LDS buffers, target grid
-//   wgrad_group_mult / _min / _max                    grouped weight gradient: blocks per problem = clamp(mult*tiles, min, max)
-extern "C" int hrseg_tune(const char* key, int value) {
-  struct { const char* k; int* v; } tab[] = {
-      {"igemm_wtm", &g_tune_wtm}, {"igemm_kc", &g_tune_kc}, {"igemm_db", &g_tune_db}, {"igemm_ksplit", &g_tune_ksplit},
-      {"group_wtm", &g_group_wtm}, {"wgrad_pix", &g_tune_wg_pix}, {"wgrad_db", &g_tune_wg_db},
-      {"wgrad_blocks", &g_tune_wg_blocks}, {"wgrad_group_mult", &g_wg_mult}, {"wgrad_group_min", &g_wg_min},
-      {"wgrad_group_max", &g_wg_max}, {"sp_wtm", &g_sp_wtm}, {"sp_wtn", &g_sp_wtn}, {"sp_ksplit", &g_sp_ksplit}, {"sp_patch", &g_sp_patch}, {"sp_persist", &g_sp_persist}, {"sp_ws", &g_sp_ws}, {"sp_ws_waste", &g_ws_waste}, {"small_cin3", &g_small_cin3}, {"sp_ws_bf16", &g_ws_bf16}, {"sp_ws_n48", &g_ws_n48}, {"sp_img", &g_sp_img}, {"wgrad9", &g_wg9}, {"ws_epi_early", &g_ws_epi_early}, {"exp_nosplit_x", &g_exp_nosplit}, {"x_split", &g_x_split}, {"ws_epi_cost", &g_ws_epi_cost}, {"ws_epi_acc_cost", &g_ws_epi_acc_cost}, {"wgrad9_blocks", &g_wg9_blocks}, {"wgrad9_blocks1", &g_wg9_blocks_n[1]}, {"wgrad9_blocks2", &g_wg9_blocks_n[2]}, {"wgrad9_blocks3", &g_wg9_blocks_n[3]}, {"wgrad9_blocks4", &g_wg9_blocks_n[4]}, {"sp_wide", &g_sp_wide}, {"sp_ws_canvas", &g_ws_canvas}, {"wgrad_group_sp", &g_wg_group_sp}, {"wgrad_sp_t5", &g_wg_t5}, {"wgrad_sp_wide", &g_wg_wide}, {"sp_wide_min_blocks", &g_spw_min_blocks},
-      {"sp_patch_min_tiles", &g_patch_min_tiles}, {"auto_min_pixels", &g_auto_min_pix}, {"sp_ws_min_tiles", &g_ws_min_tiles},
-      {"deterministic", &hrseg_g_deterministic}};
-  HRSEG_CHECK_ARG(key != nullptr, "hrseg_tune: null key");
-  for (auto& e : tab)
-    if (!strcmp(e.k, key)) {
-      *e.v = value;
-      if (g_patch_min_tiles <= 0) g_patch_min_tiles = 192;      // (0 = the default plan, as for every key)
-      if (g_auto_min_pix <= 0) g_auto_min_pix = 8192;
-      if (g_ws_min_tiles <= 0) g_ws_min_tiles = 96;
-      return 0;
-    }
-  hrseg_set_error("hrseg_tune: unknown key '%s'", key);
-  return HRSEG_ERR_INVALID_ARG;
 }
 

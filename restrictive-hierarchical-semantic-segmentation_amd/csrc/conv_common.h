@@ -1,11 +1,13 @@
-// Shared structs and device helpers of the convolution translation units (conv.hip = dispatch + C ABI;
-// conv_f32.hip, conv_wgrad_f32.hip, conv_sp_im2col.hip, conv_sp_patch.hip, conv_sp_pgroup.hip, conv_ws.hip,
-// conv_wgrad_sp.hip = the kernel families and their launchers).  The split exists for build time only: every
-// launcher below is a plain function that picks the template instance for a plan the dispatcher made.
+// Shared structs and device helpers of the convolution translation units:
+//   conv.hip          the dispatch (tile plans, kernel-family choice per problem) and the convolution C ABI
+//   conv_scratch.hip  the scratch ring and the persistent weight-image cache behind the pre-split weight images
+//   conv_f32.hip, conv_wgrad_f32.hip, conv_sp_im2col.hip, conv_sp_patch.hip, conv_sp_pgroup.hip, conv_ws.hip,
+//   conv_wgrad_sp.hip, conv_small.hip   the kernel families and their launchers (bodies of the split-precision ones: conv_sp.h)
+// Every launcher below is a plain function that picks the template instance for a plan the dispatcher made, and every
+// struct a launcher takes is declared here: the dispatcher does not see the kernel bodies, so editing one rebuilds its
+// family's unit only.
 #pragma once
 #include "common.h"
-#include <string.h>
-#include <stdint.h>
 
 // ---------------------------------------------------------------------------
 struct IgemmArgs {
@@ -36,7 +38,7 @@ struct IgemmArgs {
   int epi_early;             // wave-specialised body: issue the epilogue's reads (accumulate / residual) ahead of the tile's last slab
   double* stat_partial;      // wave-specialised body, forward: BatchNorm partial sums of the output, one row [2][N] per block (else null)
   int* stat_rows;            // HOST pointer: the launcher writes the number of rows (blocks) there; not read by any kernel
-  int w_persistent;          // w is a parameter the caller keeps images of up to date (hrseg_weight_images_refresh): see conv.hip
+  int w_persistent;          // w is a parameter the caller keeps images of up to date (hrseg_weight_images_refresh): see conv_scratch.hip
   int exp_nosplit;           // MEASUREMENT ONLY (hrseg_tune exp_nosplit_x): the wave-specialised producers stage x without splitting it
   int x_presplit;            // x is stored pre-split (hrseg_conv_shape_t.x_split): only the wave-specialised forward body reads that form
 };
@@ -113,6 +115,61 @@ struct WgradGroup {
 struct IgemmPlan { int wtm, wtn, kc, db, ksplit; };
 struct SpPlan { int wtm, wtn, ksplit; };
 
+// ---- wave-specialised halo-patch body: tilings and pre-split weight images
+// tiling `kind` of a problem: 1 = 48 channels x 48-channel K stages on 8 x 16 pixel tiles, 2 = 96 x 48, 3 = 64 x 64,
+// 4 = 48 x 48 on 16 x 16 pixel tiles (a 48-channel slab on 8 rows is 18 MFMAs per wave: too short for the producers to keep
+// up); 0 = not eligible.  Channel tile and K stage in 16-channel units, tile height in rows:
+static const int WS_WTN[5] = {0, 3, 6, 4, 3}, WS_CS[5] = {0, 3, 3, 4, 3}, WS_TH[5] = {0, 8, 8, 8, 16};
+static inline size_t ws_image_bytes(const IgemmArgs& a, int kind, int ns) {      // ns = 4: two fp16 pieces per weight, 1: one bf16 piece
+  const int wtn = WS_WTN[kind], cs = WS_CS[kind];
+  return (size_t)(a.N / (16 * wtn)) * (a.K / (16 * cs)) * ((9 * cs + 1) / 2) * (size_t)((ns == 4 ? 2 : 1) * 16 * wtn * 64);
+}
+// one launch that writes the images of up to MAXG weights (sp_weight_image_kernel)
+struct WeightImageGroup {
+  int n;
+  int ns;                  // 4: two fp16 pieces per weight (fp16x2), 1: one bf16 piece (bf16)
+  int blk_end[MAXG];
+  int kind[MAXG];          // channel tiling of the wave-specialised body (index of WS_WTN; conv.hip: ws_kind)
+  int K[MAXG];
+  float wscale[MAXG];
+  const float* w[MAXG];
+  unsigned char* img[MAXG];
+};
+// table form: the images of EVERY registered convolution weight in one launch (hrseg_weight_images_refresh); the table lives
+// in device memory, a block finds its entry by bisection over the running block counts
+struct WeightImageTabEntry {
+  const float* w;
+  unsigned char* img;
+  int K, kind, ns, blk_end;
+  float wscale;
+  int pad;
+};
+
+// ---- nine-tap weight gradient (wgrad9_sp_body: per-block partial sums in a workspace, then an ordered reduce)
+struct Wgrad9Args {
+  const float* x; const float* dy; float* ws;     // ws: [nchunks][Cout][9][Cin]
+  const float* dymax;                              // device scalar |dy|_max (fp16x2 scaling) or null
+  int ldx, lddy, B, H, W, Cin, Cout;
+  int tiles_x, tiles_y, ntiles, nchunks, per;      // per = tiles per chunk
+  int exp_nosplit;                                 // MEASUREMENT ONLY (hrseg_tune exp_nosplit_x): stage x as if it came pre-split
+  int x_presplit;                                  // x is stored pre-split (hrseg_conv_shape_t.x_split)
+};
+#define WG9_MAXG 8
+struct Wgrad9Group {
+  int n;
+  int blk_end[WG9_MAXG];
+  Wgrad9Args a[WG9_MAXG];
+};
+// dW[i] += sum over chunks (in chunk order) of ws[chunk][i]; n4 = elements / 4 per problem
+struct Wgrad9Reduce {
+  int n;
+  int blk_end[WG9_MAXG];
+  const float* ws[WG9_MAXG];
+  float* dw[WG9_MAXG];
+  int nchunks[WG9_MAXG];
+  long n4[WG9_MAXG];
+};
+
 // ---- launchers (one translation unit per kernel family); return 0, 1 = no instance for the plan
 int launch_igemm_f32(const IgemmArgs& a, const IgemmPlan& pl, hipStream_t st);                       // conv_f32.hip
 int launch_igemm_group_f32(const IgemmGroup& g, int wtm, int wtn, int kc, hipStream_t st);
@@ -125,14 +182,20 @@ int launch_patch_sp_kernel(int ns, const IgemmArgs& a, int wtn, int cs, int flip
 int launch_sp_pgroup_kernel(int ns, const IgemmGroup& g, int wtm, int wtn, int cs, int flip, hipStream_t st);               // conv_sp_pgroup.hip
 int launch_ws_kernel(const IgemmArgs& a, int kind, int flip, int blocks, int ntotal, hipStream_t st, int ns = 4);    // conv_ws.hip
 int launch_ws_group_kernel(const IgemmGroup& g, int flip, hipStream_t st, int ns = 4);
-int launch_weight_images(const struct WeightImageGroup& g, int nblocks, hipStream_t st);
-int launch_weight_image_table(const struct WeightImageTabEntry* tab, int n, int nblocks, hipStream_t st);
+int launch_weight_images(const WeightImageGroup& g, int nblocks, hipStream_t st);
+int launch_weight_image_table(const WeightImageTabEntry* tab, int n, int nblocks, hipStream_t st);
 int launch_wgrad_sp_kernel(int ns, const WgradArgs& a, int tn, int tk, int gx, int tiles, hipStream_t st);     // conv_wgrad_sp.hip
 int launch_wgrad_group_sp(const WgradGroup& g, int tn, int tk, int nblocks, hipStream_t st);
 int launch_wgrad_spw_kernel(const WgradArgs& a, int gx, int tiles, hipStream_t st);
-int launch_wgrad9_kernels(int ns, int tnk, const struct Wgrad9Group& g, int nblocks, const struct Wgrad9Reduce& r, int rblocks, hipStream_t st);
+int launch_wgrad9_kernels(int ns, int tnk, const Wgrad9Group& g, int nblocks, const Wgrad9Reduce& r, int rblocks, hipStream_t st);
 int check_wgrad_span(const WgradArgs& a);
 #define HRSEG_SMALL_CIN_MAX 8
 void launch_small_cin_fwd(const float* x, const float* w, const float* bias, float* y, const hrseg_conv_shape_t* s, hipStream_t st);  // conv_small.hip
 void launch_small_cin_wgrad(const float* x, const float* dy, float* dw, const hrseg_conv_shape_t* s, int pix_per_block, hipStream_t st);
-void launch_small_cin_dgrad(const float* dy, const float* w, float* dx, int accumulate, const hrseg_conv_shape_t* s, hipStream_t st);                                                              // conv.hip
+void launch_small_cin_dgrad(const float* dy, const float* w, float* dx, int accumulate, const hrseg_conv_shape_t* s, hipStream_t st);
+
+// ---- scratch ring + weight-image cache (conv_scratch.hip; attached by hrseg_set_scratch / hrseg_set_weight_image_arena)
+bool scratch_usable();                                            // a scratch buffer of the current device is attached
+unsigned char* scratch_reserve(hipStream_t st, size_t bytes);     // contiguous bytes of this stream's ring, nullptr = no room
+// sets a[i].wimg of n problems with tilings kinds[i] (cached images as they are, the others written by one launch); false = no room
+bool ws_make_images(IgemmArgs* a, const int* kinds, int n, hipStream_t st, int ns);

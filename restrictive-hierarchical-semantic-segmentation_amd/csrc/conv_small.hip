@@ -3,8 +3,6 @@
 // channel capacity (the 3-channel layer keeps its 4-wide vectors).
 #include "conv_common.h"
 
-int g_small_cin3 = 1;       // hrseg_tune "small_cin3": 0 = the 3-channel 3x3 first layer stays on the generic Cin <= 8 kernels
-
 // y[b,oy,ox,co] = bias[co] + sum_{t,ci} x[b, oy*s+kh-1, ox*s+kw-1, ci] * w[co][t][ci]
 // one thread = one output pixel x 16 channels; weights of the block's 64 channels in LDS.
 template <int CMAX>
@@ -325,7 +323,7 @@ void launch_small_cin_fwd(const float* x, const float* w, const float* bias, flo
   const float* res = s->residual;
   const int ldr = s->ldr, relu = s->relu;
   const long M = (long)s->B * s->Ho * s->Wo;
-  if (s->Cin == 3 && s->ksize == 3 && s->Cout % 64 == 0 && s->ldy % 4 == 0 && (!res || ldr % 4 == 0) && M < (1L << 31) && g_small_cin3) {
+  if (s->Cin == 3 && s->ksize == 3 && s->Cout % 64 == 0 && s->ldy % 4 == 0 && (!res || ldr % 4 == 0) && M < (1L << 31) && hrseg_g_small_cin3) {
     long gx = ceil_div(M, 16);
     if (gx > 4096) gx = 4096;
     hipLaunchKernelGGL(conv_cin3_k3_fwd_kernel, dim3((unsigned)gx, s->Cout / 64), dim3(256), 0, st, x, s->ldx, w, bias, y, s->ldy, s->B,
@@ -342,7 +340,7 @@ void launch_small_cin_fwd(const float* x, const float* w, const float* bias, flo
 }
 void launch_small_cin_wgrad(const float* x, const float* dy, float* dw, const hrseg_conv_shape_t* s, int ppb, hipStream_t st) {
   const long M = (long)s->B * s->Ho * s->Wo;
-  if (s->Cin == 3 && s->ksize == 3 && s->Cout % 64 == 0 && s->ldy % 4 == 0 && M < (1L << 31) && g_small_cin3) {
+  if (s->Cin == 3 && s->ksize == 3 && s->Cout % 64 == 0 && s->ldy % 4 == 0 && M < (1L << 31) && hrseg_g_small_cin3) {
     hipLaunchKernelGGL(conv_cin3_k3_wgrad_kernel, dim3(ceil_div(M, ppb), s->Cout / 64), dim3(256), 0, st, x, s->ldx, dy, s->ldy, dw,
                        s->B, s->Hi, s->Wi, s->Ho, s->Wo, s->stride, ppb);
     return;

@@ -1,4 +1,4 @@
-// Split-precision implicit GEMM on the bf16 matrix pipe (gfx950), included by conv.hip.
+// Split-precision implicit GEMM on the bf16 matrix pipe (gfx950), included by the launcher units of its kernel families (conv_sp_*.hip, conv_ws.hip, conv_wgrad_sp.hip).
 //
 // v_mfma_f32_16x16x4_f32 runs at 1/16 of the bf16 MFMA rate.  An fp32 value splits EXACTLY into three bf16
 // pieces (8 significand bits each: hi = truncate(x), mid = truncate(x - hi), lo = x - hi - mid), so an fp32
@@ -1447,25 +1447,6 @@ __device__ __forceinline__ void sp_weight_image_body(const float* __restrict__ w
     for (int q = 0; q < sp_np(NS); ++q) *reinterpret_cast<u32x2*>(dst + q * L::WPIECE + o) = pc[q];
   }
 }
-struct WeightImageGroup {
-  int n;
-  int ns;                  // 4: two fp16 pieces per weight (fp16x2), 1: one bf16 piece (bf16)
-  int blk_end[MAXG];
-  int kind[MAXG];          // channel tiling of the wave-specialised body (conv.hip: ws_kind)
-  int K[MAXG];
-  float wscale[MAXG];
-  const float* w[MAXG];
-  unsigned char* img[MAXG];
-};
-// table form: the images of EVERY registered convolution weight in one launch (hrseg_weight_images_refresh); the table lives
-// in device memory, a block finds its entry by bisection over the running block counts
-struct WeightImageTabEntry {
-  const float* w;
-  unsigned char* img;
-  int K, kind, ns, blk_end;
-  float wscale;
-  int pad;
-};
 #ifdef HRSEG_TU_WS          // non-template kernels are defined in the one translation unit that launches them
 __global__ __launch_bounds__(256) void sp_weight_image_table_kernel(const WeightImageTabEntry* __restrict__ tab, int n) {
   int lo = 0, hi = n - 1;
@@ -2242,15 +2223,6 @@ struct SpWgrad9Lds {
   static constexpr int BYTES = sp_np(NS) * PIECE;
 };
 
-struct Wgrad9Args {
-  const float* x; const float* dy; float* ws;     // ws: [nchunks][Cout][9][Cin]
-  const float* dymax;                              // device scalar |dy|_max (fp16x2 scaling) or null
-  int ldx, lddy, B, H, W, Cin, Cout;
-  int tiles_x, tiles_y, ntiles, nchunks, per;      // per = tiles per chunk
-  int exp_nosplit;                                 // MEASUREMENT ONLY (hrseg_tune exp_nosplit_x): stage x as if it came pre-split
-  int x_presplit;                                  // x is stored pre-split (hrseg_conv_shape_t.x_split)
-};
-
 template <int NS, int TNK>
 __device__ __forceinline__ void wgrad9_sp_body(const Wgrad9Args& p, unsigned char* lds, const int pair, const int chunk) {
   using L = SpWgrad9Lds<NS, TNK>;
@@ -2434,12 +2406,6 @@ __device__ __forceinline__ void wgrad9_sp_body(const Wgrad9Args& p, unsigned cha
           out[obase + (16 * n + e) * row9 + kw * p.Cin + 16 * k] = NS == 4 ? acc[kw][n][k][e] * dyinv : acc[kw][n][k][e];
 }
 
-#define WG9_MAXG 8
-struct Wgrad9Group {
-  int n;
-  int blk_end[WG9_MAXG];
-  Wgrad9Args a[WG9_MAXG];
-};
 template <int NS, int TNK>
 __device__ __forceinline__ void wgrad9_sp_group_entry(const Wgrad9Group& grp, unsigned char* lds) {
   const int bid = (int)blockIdx.x;
@@ -2463,15 +2429,6 @@ __global__ __launch_bounds__(192) void wgrad9_sp_group_kernel4(Wgrad9Group grp) 
   wgrad9_sp_group_entry<NS, 4>(grp, lds);
 }
 
-// dW[i] += sum over chunks (in chunk order) of ws[chunk][i]; n4 = elements / 4 per problem
-struct Wgrad9Reduce {
-  int n;
-  int blk_end[WG9_MAXG];
-  const float* ws[WG9_MAXG];
-  float* dw[WG9_MAXG];
-  int nchunks[WG9_MAXG];
-  long n4[WG9_MAXG];
-};
 #ifdef HRSEG_TU_WGRAD_SP
 __global__ __launch_bounds__(256) void wgrad9_reduce_kernel(Wgrad9Reduce r) {
   // block = 32 consecutive float4 x 8 chunk groups (group j sums chunks j, j+8, ... in order); the eight partial

@@ -24,8 +24,6 @@
 // block copies the node table to LDS once because lanes index it with their own channel.
 #include "common.h"
 
-void hrseg_count_decode_launches(int n);      // conv.hip: hrseg_launch_count family "decode_labels"
-
 typedef unsigned char u8;
 
 #define DEC_TPB 256
@@ -218,6 +216,6 @@ extern "C" int hrseg_decode_labels(int nlevels, const float* const* z, const int
     hipLaunchKernelGGL(decode_labels_kernel<false>, grid, dim3(DEC_TPB), 0, (hipStream_t)stream, a, (const long long*)desc, labels,
                        confidence, S);
   HRSEG_LAUNCH_CHECK("decode_labels");
-  hrseg_count_decode_launches(1);
+  hrseg_count(CNT_DECODE_LABELS);
   return 0;
 }

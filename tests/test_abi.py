@@ -63,3 +63,47 @@ def test_invalid_arguments_are_reported_without_a_gpu():
     lib.hrseg_tune.argtypes = [ctypes.c_char_p, ctypes.c_int]
     assert lib.hrseg_tune(b"igemm_wtm", 0) == 0
     assert lib.hrseg_tune(b"no_such_knob", 1) == -1 and b"unknown key" in lib.hrseg_last_error_string()
+
+
+KNOBS = ["igemm_wtm", "igemm_kc", "igemm_db", "igemm_ksplit", "group_wtm", "wgrad_pix", "wgrad_db", "wgrad_blocks",
+         "wgrad_group_mult", "wgrad_group_min", "wgrad_group_max", "sp_wtm", "sp_wtn", "sp_ksplit", "sp_patch", "sp_persist",
+         "sp_ws", "sp_ws_waste", "small_cin3", "sp_ws_bf16", "sp_ws_n48", "sp_img", "wgrad9", "ws_epi_early", "exp_nosplit_x",
+         "x_split", "ws_epi_cost", "ws_epi_acc_cost", "wgrad9_blocks", "wgrad9_blocks1", "wgrad9_blocks2", "wgrad9_blocks3",
+         "wgrad9_blocks4", "sp_wide", "sp_ws_canvas", "wgrad_group_sp", "wgrad_sp_t5", "wgrad_sp_wide", "sp_wide_min_blocks",
+         "sp_patch_min_tiles", "auto_min_pixels", "sp_ws_min_tiles", "deterministic"]
+FAMILIES = ["ws", "ws_group", "patch_sp", "sp_im2col", "sp_pgroup", "sp_group", "f32", "f32_group", "wgrad_sp", "wgrad_f32",
+            "wgrad_f32_group", "wgrad9", "small_cin", "sp_wide", "ws_canvas", "wgrad_sp_group", "wgrad_sp_t5", "wgrad_sp_wide",
+            "augment_image", "augment_targets", "decode_labels"]
+
+_REGISTRY_CHILD = r"""
+import ctypes, json, sys
+lib = ctypes.CDLL(sys.argv[1])
+lib.hrseg_last_error_string.restype = ctypes.c_char_p
+lib.hrseg_tune.argtypes = [ctypes.c_char_p, ctypes.c_int]
+lib.hrseg_launch_count.argtypes = [ctypes.c_char_p, ctypes.c_int]
+lib.hrseg_launch_count.restype = ctypes.c_long
+spec = json.load(sys.stdin)
+out = {"knobs": {k: lib.hrseg_tune(k.encode(), 0) for k in spec["knobs"]},
+       "unknown": [lib.hrseg_tune(b"no_such_knob", 0), lib.hrseg_last_error_string().decode()],
+       "families": {f: lib.hrseg_launch_count(f.encode(), 0) for f in spec["families"]},
+       "total": lib.hrseg_launch_count(None, 0)}
+print(json.dumps(out))
+"""
+
+
+def test_every_knob_and_family_is_registered():
+    """hrseg_tune knows each of the 43 keys and hrseg_launch_count each of the 21 families (csrc/runtime.h), by their literal
+    names; in a child process, so that the knob writes (0 switches several kernels off) cannot leak into other tests"""
+    import json
+    import subprocess
+    import sys
+    from hrseg_amd import _lib
+    assert len(set(KNOBS)) == 43 and len(set(FAMILIES)) == 21
+    r = subprocess.run([sys.executable, "-c", _REGISTRY_CHILD, _lib.LIB_PATH], input=json.dumps({"knobs": KNOBS, "families": FAMILIES}),
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    assert out["knobs"] == {k: 0 for k in KNOBS}
+    assert out["unknown"][0] == -1 and "unknown key" in out["unknown"][1]
+    assert out["families"] == {f: 0 for f in FAMILIES}, "a process that launched nothing has only zero counters"
+    assert out["total"] == 0

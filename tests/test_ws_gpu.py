@@ -485,3 +485,71 @@ def test_ws_results_do_not_depend_on_timing():
     for _ in range(25):
         ys = ops.conv_fwd_group(xs, ws, [None] * 4, 3, 1, chans, prec=pr)
         assert all(torch.equal(a, b) for a, b in zip(ys, y0))
+
+
+# name, [(Cin, Cout, ksize, stride, relu) per problem], what hrseg_conv_x_split_ok answers for them at B = 2, 32 x 32 with the
+# routing threshold sp_ws_min_tiles lowered to 1 (16 resp. 32 tiles here).  A 48- and a 64-channel problem together are refused:
+# the nine-tap weight gradient wants ONE tile size per call (48- or 64-channel tiles); 48 and 96 channels share the 48-channel tiles.
+X_SPLIT_SETS = [
+    ("one48", [(48, 48, 3, 1, False)], 1),
+    ("group48_64", [(48, 48, 3, 1, False), (64, 64, 3, 1, False)], 0),
+    ("group48_96", [(48, 48, 3, 1, False), (96, 96, 3, 1, False)], 1),
+    ("one96", [(96, 96, 3, 1, False)], 1),
+    ("relu", [(48, 48, 3, 1, True)], 0),
+    ("k1", [(48, 48, 1, 1, False)], 0),
+    ("stride2", [(48, 48, 3, 2, False)], 0),
+    ("mixed_k", [(48, 48, 3, 1, False), (48, 48, 1, 1, False)], 0),
+]
+
+
+@pytest.mark.parametrize("name,probs,want", X_SPLIT_SETS, ids=[s[0] for s in X_SPLIT_SETS])
+def test_x_split_ok_agrees_with_what_the_calls_do(name, probs, want):
+    """hrseg_conv_x_split_ok promises a route; the calls must take it: where it says yes, the ordinary fp32-input forward call
+    under HRSEG_CONV_AUTO raises only the ws / ws_group counters (and the convolution total is their sum) and the weight
+    gradient with the workspace the library asks for raises only wgrad9"""
+    from hrseg_amd import _lib, ops
+    from tests.test_abi import FAMILIES
+    auto = _lib.CONV_PRECISION["auto"]
+    B, H = 2, 32
+    dev = torch.device("cuda:0")
+    _lib.ensure_scratch(dev)
+    g = torch.Generator().manual_seed(11)
+    xs = [torch.randn(B, H, H, ci, generator=g).cuda() for ci, co, k, s, relu in probs]
+
+    def counts():
+        return {f: _lib.launch_count(f) for f in FAMILIES}, _lib.launch_count(None)
+
+    try:
+        _lib.tune(sp_ws_min_tiles=1)
+        shapes = [ops._shape(tuple(x.shape), ci, co, co, k, s, auto, relu=relu) for x, (ci, co, k, s, relu) in zip(xs, probs)]
+        got = int(_lib.conv_x_split_ok(ops._shape_array(shapes), len(shapes)))
+        print(name, "x_split_ok =", got)
+        assert got == want
+        if not got:
+            return
+        k, s = 3, 1
+        couts = [p[1] for p in probs]
+        ws = [(torch.randn(co, 9, ci, generator=g) / (9 * ci) ** 0.5).cuda() for ci, co, *_ in probs]
+        _lib.launch_count(None, reset=True)
+        if len(probs) == 1:
+            ys = [ops.conv_fwd(xs[0], ws[0], None, k, s, prec=auto)]
+        else:
+            ys = ops.conv_fwd_group(xs, ws, [None] * len(xs), k, s, couts, prec=auto)
+        by_family, total = counts()
+        print(name, "forward:", {f: c for f, c in by_family.items() if c}, "total", total)
+        assert by_family["ws"] + by_family["ws_group"] >= 1
+        assert all(c == 0 for f, c in by_family.items() if f not in ("ws", "ws_group")), by_family
+        assert total == by_family["ws"] + by_family["ws_group"]
+        dys = [torch.randn(y.shape, generator=g).cuda() * 1e-3 for y in ys]
+        gms = [d.abs().max().reshape(1).repeat(64) for d in dys]
+        dws = [torch.zeros_like(w) for w in ws]
+        assert _lib.conv_wgrad_workspace_bytes(ops._shape_array(shapes), len(shapes)) > 0
+        _lib.launch_count(None, reset=True)
+        ops.conv_wgrad_group(xs, dys, dws, k, s, prec=auto, gmaxs=gms)
+        by_family, total = counts()
+        print(name, "weight gradient:", {f: c for f, c in by_family.items() if c}, "total", total)
+        assert by_family["wgrad9"] == 1 and total == 1
+        assert all(c == 0 for f, c in by_family.items() if f != "wgrad9"), by_family
+        torch.cuda.synchronize()
+    finally:
+        _lib.tune(sp_ws_min_tiles=0)

@@ -3,7 +3,7 @@
 //   HOT   = every block gathers the SAME pixels (all loads hit L1/L2): the memory system taken out
 // Loads are unconditional (clamped address + select) so the wait counts stay static.
 // hipcc --offload-arch=gfx950 -O3 depth_lab.hip -o depth_lab     (diagnostic only, never product output)
-#include "../../restrictive-hierarchical-semantic-segmentation_amd/csrc/error.hip"
+#include "../../restrictive-hierarchical-semantic-segmentation_amd/csrc/runtime.hip"
 #include "../../restrictive-hierarchical-semantic-segmentation_amd/csrc/conv.hip"
 #include <vector>
 #include <stdlib.h>

@@ -2,7 +2,7 @@
 // round trip, no ds_write, NBUF-deep LDS ring, one barrier per stage.  Compared against the
 // production register-staged kernel.  Diagnostic build.
 // hipcc --offload-arch=gfx950 -O3 -Wno-unused-result dma_lab.hip -o dma_lab
-#include "../../restrictive-hierarchical-semantic-segmentation_amd/csrc/error.hip"
+#include "../../restrictive-hierarchical-semantic-segmentation_amd/csrc/runtime.hip"
 #include "../../restrictive-hierarchical-semantic-segmentation_amd/csrc/conv.hip"
 #include <vector>
 #include <stdlib.h>

@@ -1,7 +1,7 @@
 // Where does an igemm stage spend its cycles?  Diagnostic build: the production kernel body with
 // s_memtime stamps per phase (results of this build are timing shares, never product output).
 // hipcc --offload-arch=gfx950 -O3 -I../../restrictive-hierarchical-semantic-segmentation_amd/csrc igemm_lab.hip -o igemm_lab
-#include "../../restrictive-hierarchical-semantic-segmentation_amd/csrc/error.hip"
+#include "../../restrictive-hierarchical-semantic-segmentation_amd/csrc/runtime.hip"
 #include "../../restrictive-hierarchical-semantic-segmentation_amd/csrc/conv.hip"
 #include <vector>
 #include <stdlib.h>

@@ -1,5 +1,5 @@
 // Phase stamps for the halo-patch conv kernel (diagnostic build; read the shares).
-#include "../../restrictive-hierarchical-semantic-segmentation_amd/csrc/error.hip"
+#include "../../restrictive-hierarchical-semantic-segmentation_amd/csrc/runtime.hip"
 #include "../../restrictive-hierarchical-semantic-segmentation_amd/csrc/conv.hip"
 #include <vector>
 #include <algorithm>
