@@ -156,7 +156,8 @@ int hrseg_conv_wgrad_group_ws(int n, const float* const* x, const float* const* 
  * zeroes what it returns.  "ws_canvas" counts PROBLEMS (not launches, not part of the NULL total) that a "ws" / "ws_group"
  * launch tiled as one canvas of side-by-side images, "wgrad_sp_t5" the "wgrad_sp" launches on 80 x 80 tiles ("wgrad_sp_wide": the wide-tile weight-gradient kernel, a family of its own).  The parity tests use it to prove which kernels a case ran.
  * "augment_image" / "augment_targets" (the input pipeline) and "decode_labels" (the output pipeline, 1 launch per
- * hrseg_decode_labels call) are families of their own, outside the NULL total and the convolution counts. */
+ * hrseg_decode_labels call) and "score_labels" (the scoring pipeline, 1 launch per hrseg_score_labels call) are families
+ * of their own, outside the NULL total and the convolution counts. */
 long hrseg_launch_count(const char* family, int reset);
 /* tile-plan overrides and A/B switches for the sweep tools under tools/ (value 0 = automatic plan).  Keys: igemm_wtm,
  * igemm_kc, igemm_db, igemm_ksplit, group_wtm, wgrad_pix, wgrad_db, wgrad_blocks, wgrad_group_mult,
@@ -524,6 +525,44 @@ typedef struct {
 int hrseg_decode_labels(int nlevels, const float* const* z, const int* C, const hrseg_decode_tree_t* tree,
                         const long* desc, unsigned char* labels, float* confidence, int B, int S,
                         hrseg_stream_t stream);
+
+/* ------------------------------------------------------------------ device scoring pipeline (Data/score.py)
+ * The third stage behind the input and output pipelines: a batch of predicted label maps (hrseg_decode_labels) against
+ * ground-truth label maps at the SOURCE size, both in the pixel values of class_map.csv -> per-level confusion counts in
+ * the layout hrseg_metric_vectors reads.
+ * Levels are the tree's depths in breadth-first channel order, whatever model produced the map (a flat model's leaf map
+ * is scored per hierarchy level the same way).  Limits as for the decode: nlevels <= 8, C[L] <= 16, sum C[L] <= 64.
+ * path_lut: DEVICE table [256] of uint64 built on the host from the class tree and class map: byte L of entry v is
+ * 1 + channel of the level-L node on the path from the root to the leaf whose pixel value is v, 0 when that leaf is
+ * shallower than L; the whole entry is 0 when v is no leaf's value.  (An entry that names a channel above C[L], or has no
+ * level-0 node, or a node at a level >= nlevels, counts as 0.)
+ * pred / gt: packed uint8 buffers, pdesc / gdesc their DEVICE [B][4] int64 tables (byte offset, H, W, 1): map b is a
+ * dense span of H_b * W_b bytes at its own offset in its own buffer; both tables must give the same H_b x W_b (a sample
+ * where they differ, or with H*W > 2^31, is not counted at all -- the host wrapper refuses both).  For pixel i of
+ * sample b, with g = path_lut[gt], p = path_lut[pred] and g_L / p_L byte L of them:
+ *   - g == 0: ignored[b][0] += 1 (unlabelled ground truth), nothing else is counted;
+ *   - else p == 0: ignored[b][1] += 1 (a prediction outside the class map), nothing else is counted;
+ *   - level 0: cm_0[(g_0 - 1) * C_0 + (p_0 - 1)] += 1;
+ *   - level L >= 1: K_L = C_L + 1, label 0 is the synthetic background; t = g_L, q = (g_{L-1} == p_{L-1}) ? p_L : 0;
+ *     cm_L[t * K_L + q] += 1.
+ * A prediction competes at level L only where it agreed with the ground truth at the level above: the restrictive
+ * masking of the train loop (t == -1 zeroes the prediction) applied to decoded paths.  Every level's matrix therefore
+ * sums to the number of valid pixels; hrseg_metric_vectors drops row 0 of the child levels.
+ * DELIBERATE DEVIATION from the metrics at network size (hrseg_predict_metrics): there an unlabelled pixel lands in row 0
+ * of level 0, because the arg-max of an all-zero target picks channel 0; here it is ignored and counted in `ignored`.
+ * counts: DEVICE int64 [per_image ? B : 1][sum_L K_L^2] (K_0 = C_0), levels side by side, (target, predicted), +=
+ * (accumulate a dataset total in place); ignored: DEVICE int64 [per_image ? B : 1][2], +=.  C is a HOST array.
+ * All arithmetic is integer: the result does not depend on the block order nor on the "deterministic" knob.  One launch
+ * (family "score_labels"), no workspace, no device allocation, no synchronisation.  The kernel never reads outside
+ * [offset, offset + H*W) of either buffer.  A lane counts HRSEG_SCORE_LANE_STEP consecutive pixels per step. */
+#define HRSEG_SCORE_MAX_LEVELS 8
+#define HRSEG_SCORE_MAX_CHANNELS 16
+#define HRSEG_SCORE_LANE_STEP 16
+#define HRSEG_SCORE_WAVE_STEP 1024
+#define HRSEG_SCORE_BLOCK_STEP 4096
+int hrseg_score_labels(const unsigned char* pred, const long* pdesc, const unsigned char* gt, const long* gdesc,
+                       const unsigned long long* path_lut, int nlevels, const int* C, long long* counts,
+                       long long* ignored, int B, int per_image, hrseg_stream_t stream);
 
 /* ------------------------------------------------------------------ level synthesis for flat models (evaluation side)
  * predictEval.py:85-129 get_parent_masks (parent = union of its descendant leaves, "any > 0") and :134-185

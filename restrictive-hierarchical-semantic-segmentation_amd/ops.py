@@ -689,6 +689,73 @@ def decode_labels(logits, tables, desc, desc_host, want_confidence=False):
     return labels, conf
 
 
+SCORE_MAX_LEVELS, SCORE_MAX_CHANNELS, SCORE_MAX_TOTAL = 8, 16, 64
+# pixels a lane / a wave / a block of hrseg_score_labels takes per step (HRSEG_SCORE_*_STEP of include/hrseg.h): the sizes
+# around which the kernel changes path
+SCORE_LANE_STEP, SCORE_WAVE_STEP, SCORE_BLOCK_STEP = 16, 1024, 4096
+SCORE_MAX_PIXELS = 1 << 31
+
+
+def check_score_tables(tables):
+    """the limits of hrseg_score_labels on a Data.score.ScoreTables: <= 8 levels, <= 16 channels per level, <= 64 in all,
+    and a path table whose bytes name channels of their levels (ValueError otherwise; needs no GPU)"""
+    Cs = list(tables.C)
+    if not 1 <= len(Cs) <= SCORE_MAX_LEVELS:
+        raise ValueError(f"score_labels: {len(Cs)} levels, supported 1..{SCORE_MAX_LEVELS}")
+    for L, n in enumerate(Cs):
+        if not 1 <= n <= SCORE_MAX_CHANNELS:
+            raise ValueError(f"score_labels: level {L} has {n} channels, supported 1..{SCORE_MAX_CHANNELS}")
+    if sum(Cs) > SCORE_MAX_TOTAL:
+        raise ValueError(f"score_labels: {sum(Cs)} channels over all levels, at most {SCORE_MAX_TOTAL}")
+    K = [n + (1 if L else 0) for L, n in enumerate(Cs)]
+    if list(tables.K) != K or list(tables.offsets) != [sum(k * k for k in K[:L]) for L in range(len(K))] or \
+            tables.total != sum(k * k for k in K):
+        raise ValueError("score_labels: K / offsets / total do not follow from C")
+    path = list(tables.path)
+    if len(path) != 256:
+        raise ValueError(f"score_labels: the path table has {len(path)} entries, not 256")
+    for v, e in enumerate(path):
+        if e == 0:
+            continue
+        for L in range(8):
+            c = (e >> (8 * L)) & 0xFF
+            if (c != 0 if L >= len(Cs) else (c > Cs[L] or (L == 0 and c == 0))):
+                raise ValueError(f"score_labels: path of pixel value {v} names channel {c - 1} at level {L}")
+
+
+def score_labels(pred, pdesc, pdesc_host, gt, gdesc, gdesc_host, tables, out=None, per_image=True):
+    """predicted against ground-truth label maps, both packed uint8 device buffers with [B,4] int64 descriptors (byte
+    offset, H, W, 1; device, and their host copies for the bounds checks) of equal (H, W) per sample, + a
+    Data.score.ScoreTables -> (counts [R, tables.total] int64, ignored [R, 2] int64), R = B (per_image) or 1: the level
+    matrices (target, predicted) side by side, as hrseg_score_labels states them.  out = (counts, ignored) of an earlier
+    call: both are added to.  One launch, no synchronisation."""
+    check_score_tables(tables)
+    _check_ragged(pred, pdesc, pdesc_host, (1,))
+    _check_ragged(gt, gdesc, gdesc_host, (1,))
+    prow, grow = pdesc_host.tolist(), gdesc_host.tolist()
+    if len(prow) != len(grow) or not prow:
+        raise ValueError(f"score_labels: {len(prow)} predicted maps against {len(grow)} ground-truth maps")
+    for b, ((_, H, W, _), (_, gH, gW, _)) in enumerate(zip(prow, grow)):
+        if (H, W) != (gH, gW):
+            raise ValueError(f"score_labels: sample {b}: predicted map {H}x{W}, ground truth {gH}x{gW}")
+        if H * W > SCORE_MAX_PIXELS:
+            raise ValueError(f"score_labels: sample {b}: {H}x{W} has more than 2^31 pixels")
+    B, R = len(prow), len(prow) if per_image else 1
+    if gt.device != pred.device:
+        raise ValueError("score_labels: the two buffers live on different devices")
+    if out is None:
+        counts, ignored = zeros((R, tables.total), torch.int64, pred.device), zeros((R, 2), torch.int64, pred.device)
+    else:
+        counts, ignored = out
+        for t, shape in ((counts, (R, tables.total)), (ignored, (R, 2))):
+            if t.dtype != torch.int64 or not t.is_cuda or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"score_labels: out must hold contiguous int64 device tensors of shapes {(R, tables.total)} and "
+                                 f"{(R, 2)}")
+    call("hrseg_score_labels", ptr(pred), ptr(pdesc), ptr(gt), ptr(gdesc), ptr(tables.device_lut(pred.device)), len(tables.C),
+         _lib.int_array(list(tables.C)), ptr(counts), ptr(ignored), B, int(bool(per_image)))
+    return counts, ignored
+
+
 def combine_levels(x0, x1, masks, is_union):
     """x0 [B,C0,H,W] (+ x1 [B,C1,H,W] or None), per output channel a bit mask over the C0+C1 input channels and a
     union flag -> [B,len(masks),H,W]: copy of the selected channel, or 1.0 where any selected channel is > 0"""

@@ -13,6 +13,7 @@ from __future__ import annotations
 import torch
 
 from . import ops
+from .Metrics.performance_metrics import METRIC_NAMES
 from .utils.hierarchy import TreeIndex
 
 
@@ -179,19 +180,48 @@ class Predictor:
     Eval-mode resize + normalise to args.img_size on the device (ops.augment_image), the eval-mode forward, then the
     restrictive top-down decode of the logits (Data/decode.py).  args: img_size, model_type, model_select.
     The model runs in eval mode for the call and gets its previous mode back afterwards.  keep_logits=True keeps the
-    latest call's logits (what the decode read) alive in `last_logits`; by default nothing of a batch is held."""
+    latest call's logits (what the decode read) alive in `last_logits`; by default nothing of a batch is held.
+    `scores = predictor.score(images, labels)` decodes at the ground-truth maps' own sizes instead and scores the maps
+    against them on the device (Data/score.py) -> SourceScores; the decoded maps of that call stay in `last_labels`."""
 
     def __init__(self, model, class_tree, class_map, args, want_confidence=False, keep_logits=False):
         from .Data.decode import DeviceDecode
-        self.model, self.class_tree, self.args = model, class_tree, args
+        self.model, self.class_tree, self.class_map, self.args = model, class_tree, class_map, args
+        self.scorer, self.last_labels = None, None
         self.size = int(args.img_size)
         self.decoder = DeviceDecode(class_tree, class_map, args.model_type)
         self.want_confidence = bool(want_confidence)
         self.keep_logits = bool(keep_logits)
         self.last_logits = None
 
-    @torch.no_grad()
     def __call__(self, images):
+        return self._predict(images, None)
+
+    @torch.no_grad()
+    def score(self, images, labels=None, out=None, per_image=True):
+        """images as for the call; labels: a list of uint8 HxW ground-truth maps in class_map pixel values (None: the
+        RaggedBatch's own label maps) -> SourceScores of the maps decoded at the labels' sizes"""
+        from .Data.decode import pack_images
+        from .Data.loader import RaggedBatch
+        from .Data.score import DeviceScore
+        if self.scorer is None:
+            self.scorer = DeviceScore(self.class_tree, self.class_map)
+        if labels is None:
+            if not isinstance(images, RaggedBatch) or images.label is None:
+                raise ValueError("Predictor.score: no ground-truth label maps")
+            gt = (images.label, images.ldesc, images.ldesc_host)
+        else:
+            buf, host = pack_images(labels)
+            if any(ch != 1 for _, _, _, ch in host.tolist()):
+                raise ValueError("Predictor.score: ground-truth label maps are single-channel uint8 images")
+            gt = (buf, host, host)
+        if gt[2].shape[0] != len(images):
+            raise ValueError(f"Predictor.score: {len(images)} images, {gt[2].shape[0]} label maps")
+        self.last_labels = self._predict(images, [(H, W) for _, H, W, _ in gt[2].tolist()])
+        return self.scorer.score(self.last_labels, gt, out, per_image)
+
+    @torch.no_grad()
+    def _predict(self, images, sizes):
         from . import train as T
         from .Data.decode import label_desc, pack_images
         from .Data.loader import RaggedBatch
@@ -211,7 +241,7 @@ class Predictor:
             self.model.train(was_training)
         if self.keep_logits:
             self.last_logits = output_logits
-        ldesc = label_desc([(H, W) for _, H, W, _ in desc_host.tolist()])
+        ldesc = label_desc([(H, W) for _, H, W, _ in desc_host.tolist()] if sizes is None else sizes)
         return self.decoder.decode(output_logits, ldesc, None, self.want_confidence)
 
 
@@ -229,14 +259,20 @@ def write_metrics_csv(path, accuracy, iou, dice, precision, recall, class_metric
 
 @torch.no_grad()
 def predict_loop(model, device, test_loader, args, class_tree, Accuracy, Iou, perf_measure, Precision, Recall,
-                 save_dir=None, target_paths=None, label_dir=None, class_map=None):
+                 save_dir=None, target_paths=None, label_dir=None, class_map=None, score_sources=False):
     """The per-fold body of the reference's predict() (predictEval.py:305-573) on a built model and loader: eval-mode
     forward, prediction_prep, get_metrics per batch, optional PNG dump of each batch's first image and metrics.csv.
     -> dict(accuracy, iou, dice, precision, recall, class_metrics, performance).
     label_dir (with class_map): the loader yields (data, target, sources) -- DeviceAugmentLoader(with_sources=True) -- and
     EVERY image's label map, decoded from the batch's logits at the source's own size, is written to
     <label_dir>/<basename of its target path, or its running index>.png.  target_paths then holds one path per IMAGE, and
-    save_dir names a batch's dump after the batch's first image; without label_dir it holds one path per batch, as before."""
+    save_dir names a batch's dump after the batch's first image; without label_dir it holds one path per batch, as before.
+    score_sources (with class_map, same loader): every batch's logits are also decoded at the sizes of the sources' OWN
+    label maps and scored against them on the device (Data/score.py; the decode of label_dir is reused where the sizes
+    agree).  The result gains the key "source": dict(names per tree node in breadth-first order, per_image {metric: one
+    list over the nodes per image}, total {metric: list over the nodes, from the counts summed over the dataset}, ignored
+    [unlabelled ground truth, predictions outside the class map] per image), and save_dir gets metrics_source.csv (the
+    dataset totals, one row per node).  Everything else is returned and written as without it."""
     import os
     import numpy as np
     from . import train as T
@@ -250,6 +286,15 @@ def predict_loop(model, device, test_loader, args, class_tree, Accuracy, Iou, pe
         if class_map is None:
             raise ValueError("label_dir needs the class_map (leaf pixel values)")
         decoder = DeviceDecode(class_tree, class_map, args.model_type)
+    scorer, source_decoder, scored = None, decoder, []
+    if score_sources:
+        from .Data.decode import DeviceDecode, label_desc
+        from .Data.score import DeviceScore, SourceScores
+        if class_map is None:
+            raise ValueError("score_sources needs the class_map (leaf pixel values)")
+        scorer = DeviceScore(class_tree, class_map)
+        if source_decoder is None:
+            source_decoder = DeviceDecode(class_tree, class_map, args.model_type)
     for i, batch in enumerate(test_loader):
         data, target = batch[0].to(device), batch[1].to(device)
         _, output_logits = T._model_call(model, data, args, class_tree)
@@ -269,10 +314,37 @@ def predict_loop(model, device, test_loader, args, class_tree, Accuracy, Iou, pe
             sizes = [(H, W) for _, H, W, _ in batch[2].desc_host.tolist()]
             names = [os.path.basename(target_paths[n_images + j]) if target_paths is not None else f"{n_images + j:05d}.png"
                      for j in range(len(sizes))]
-            save_label_maps(label_dir, names, decoder.decode(output_logits, label_desc(sizes)))
+            decoded = decoder.decode(output_logits, label_desc(sizes))
+            save_label_maps(label_dir, names, decoded)
             n_images += len(sizes)
+        if scorer is not None:
+            if len(batch) < 3 or batch[2].label is None:
+                raise ValueError("score_sources: the loader must yield (data, target, sources) with the sources' label maps, "
+                                 "e.g. DeviceAugmentLoader(..., with_sources=True)")
+            gt_sizes = [(H, W) for _, H, W, _ in batch[2].ldesc_host.tolist()]
+            if decoder is None or gt_sizes != sizes:
+                decoded = source_decoder.decode(output_logits, label_desc(gt_sizes))
+            scored.append(scorer.score(decoded, batch[2]))
     if save_dir is not None:
         os.makedirs(save_dir, exist_ok=True)
         write_metrics_csv(os.path.join(save_dir, "metrics.csv"), acc2, iou2, dice2, prec2, rec2, cls2)
-    return dict(accuracy=float(np.mean(acc2)), iou=float(np.mean(iou2)), dice=float(np.mean(dice2)),
-                precision=float(np.mean(prec2)), recall=float(np.mean(rec2)), class_metrics=cls2, performance=perf)
+    result = dict(accuracy=float(np.mean(acc2)), iou=float(np.mean(iou2)), dice=float(np.mean(dice2)),
+                  precision=float(np.mean(prec2)), recall=float(np.mean(rec2)), class_metrics=cls2, performance=perf)
+    if scorer is not None:
+        result["source"] = _source_summary(SourceScores(torch.cat([s.counts for s in scored]),
+                                                        torch.cat([s.ignored for s in scored]), scorer.tables))
+        if save_dir is not None:
+            tot = result["source"]["total"]
+            write_metrics_csv(os.path.join(save_dir, "metrics_source.csv"), *[tot[k] for k in METRIC_NAMES],
+                              [{k: [tot[k][c]] for k in METRIC_NAMES} for c in range(len(tot["accuracy"]))])
+    return result
+
+
+def _source_summary(scores):
+    """SourceScores of a dataset (one row per image) -> the "source" entry of predict_loop; one device-to-host copy"""
+    n = len(scores)
+    vecs = [scores.metric_vectors(b) for b in range(n)] + [scores.metric_vectors()]
+    host = torch.stack([torch.stack([v[k] for k in METRIC_NAMES]) for v in vecs]).tolist()
+    return dict(names=[x for lvl in scores.tables.names for x in lvl], images=n,
+                per_image={k: [host[b][i] for b in range(n)] for i, k in enumerate(METRIC_NAMES)},
+                total={k: host[n][i] for i, k in enumerate(METRIC_NAMES)}, ignored=scores.ignored.tolist())
