@@ -7,6 +7,7 @@
 // (P = 256/Q lanes per block; threads beyond P*Q idle).  Consecutive threads
 // read consecutive 16-byte pieces of a pixel row, so a wave covers whole rows.
 #include "common.h"
+#include "sp_arith.h"      // the pre-split activation granule: hrseg_split_f16x2 / hrseg_join_f16x2
 
 struct Lanes {
   int Q, P, cq, pl;
@@ -843,7 +844,7 @@ __global__ __launch_bounds__(256) void bn_apply_group_kernel(BnFwdG g) {
     f32x4 v = bn_affine(ld4(p.y + pix * p.ldy + 4 * L.cq), sc, sh);
     if (p.residual) {       // (residual_split: the block input is stored pre-split for its convolution readers; hi + lo is its value)
       const float* r = p.residual + pix * p.ldr + 4 * L.cq;
-      v += p.residual_split ? hrseg_join_f16x2(*reinterpret_cast<const hrseg_u32x4*>(r)) : ld4(r);
+      v += p.residual_split ? hrseg_join_f16x2(*reinterpret_cast<const u32x4*>(r)) : ld4(r);
     }
     if (p.relu) {
       // one byte per (pixel, channel quad): bit j = "channel 4q+j passed the ReLU".  With a residual the backward cannot
@@ -855,7 +856,7 @@ __global__ __launch_bounds__(256) void bn_apply_group_kernel(BnFwdG g) {
     // z_split: the tensor's only readers are fp16x2 convolutions that take their pixel operand pre-split (hrseg_conv_shape_t.
     // x_split): the granule goes out as {hi01, hi23, lo01, lo23} -- the same 16 bytes per 4 channels, the split done once here
     // (a bandwidth-bound kernel with VALU to spare) instead of by every staging wave of the readers
-    if (p.z_split) *reinterpret_cast<hrseg_u32x4*>(p.z + pix * p.ldz + 4 * L.cq) = hrseg_split_f16x2(v);
+    if (p.z_split) *reinterpret_cast<u32x4*>(p.z + pix * p.ldz + 4 * L.cq) = hrseg_split_f16x2(v);
     else st4(p.z + pix * p.ldz + 4 * L.cq, v);
   }
 }

@@ -25,7 +25,7 @@
 // This file holds the dispatch (tile plans, kernel-family choice per problem) and the convolution C ABI, nothing else:
 //  * the kernel families and their launchers live in conv_f32.hip, conv_wgrad_f32.hip, conv_sp_im2col.hip, conv_sp_patch.hip,
 //    conv_sp_pgroup.hip, conv_ws.hip, conv_wgrad_sp.hip and conv_small.hip (conv_common.h declares the launchers and the
-//    structs they take; this file does not include the kernel bodies of conv_sp.h);
+//    structs they take; this file does not include the split-precision kernel bodies);
 //  * the scratch ring and the weight-image cache live in conv_scratch.hip;
 //  * the launch counters (hrseg_count) and the tuning knobs (hrseg_g_<key>, set by hrseg_tune) are the rows of runtime.h.
 #include "conv_common.h"
@@ -161,7 +161,7 @@ static int patch_cs(const IgemmArgs& a, int wtn) {
 static long patch_tiles(const IgemmArgs& a, int wtn) {
   return (long)a.B * ceil_div(a.Ho, 8) * ceil_div(a.Wo, 16) * (a.N / (16 * wtn));
 }
-// ---- wave-specialised halo-patch path (conv_sp.h: igemm_patch_ws_body; tilings WS_WTN / WS_CS / WS_TH: conv_common.h)
+// ---- wave-specialised halo-patch path (conv_ws.hip: igemm_patch_ws_body; tilings WS_WTN / WS_CS / WS_TH: conv_common.h)
 // Its pre-split weight images live in the scratch ring or the weight-image arena (conv_scratch.hip); without a scratch
 // buffer the path is simply not taken.
 // Canvas mode of the body: the images of the batch side by side with a zero column between them, tiled as ONE image.  Taken
@@ -322,7 +322,7 @@ static int launch_patch_sp(int ns, const IgemmArgs& a_in, int wtn, int cs, hipSt
   return launch_patch_sp_kernel(ns, a, wtn, cs, flip, blocks, ntotal, st);
 }
 
-// wide-tile im2col body (conv_sp.h: igemm_spw_body): channel tile in 16-channel units, 0 = not a case for it.
+// wide-tile im2col body (conv_sp_im2col.hip: igemm_spw_body): channel tile in 16-channel units, 0 = not a case for it.
 // At least 96 output channels, a tile count that fills the chip (128-pixel tiles), and room in the scratch ring.
 static int spw_wtn(const IgemmArgs& a) {
   if (!hrseg_g_sp_wide || !scratch_usable() || a.K % 16 || a.M < 128) return 0;
@@ -342,7 +342,7 @@ static int launch_sp(int ns, const IgemmArgs& a, const SpPlan& pl, hipStream_t s
   return HRSEG_ERR_UNSUPPORTED;
 }
 
-static int sp_pieces(int precision) {    // hrseg_conv_precision -> split scheme of conv_sp.h (0: the fp32 MFMA kernels)
+static int sp_pieces(int precision) {    // hrseg_conv_precision -> split scheme of sp_arith.h (0: the fp32 MFMA kernels)
   return precision == HRSEG_CONV_BF16X3 ? 3 : precision == HRSEG_CONV_BF16X2 ? 2 : precision == HRSEG_CONV_BF16 ? 1
        : precision == HRSEG_CONV_FP16X2 ? 4 : 0;      // AUTO is resolved per problem before this is asked
 }

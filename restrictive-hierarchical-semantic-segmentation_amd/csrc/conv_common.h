@@ -2,7 +2,10 @@
 //   conv.hip          the dispatch (tile plans, kernel-family choice per problem) and the convolution C ABI
 //   conv_scratch.hip  the scratch ring and the persistent weight-image cache behind the pre-split weight images
 //   conv_f32.hip, conv_wgrad_f32.hip, conv_sp_im2col.hip, conv_sp_patch.hip, conv_sp_pgroup.hip, conv_ws.hip,
-//   conv_wgrad_sp.hip, conv_small.hip   the kernel families and their launchers (bodies of the split-precision ones: conv_sp.h)
+//   conv_wgrad_sp.hip, conv_small.hip   the kernel families and their launchers
+//   sp_arith.h        the split-precision arithmetic (piece schemes, split, products, the pre-split granule)
+//   sp_im2col.h, sp_patch.h, sp_patch_lds.h   the split-precision bodies that more than one unit instantiates; a body with one
+//                     user lives in that unit's .hip, above its launchers
 // Every launcher below is a plain function that picks the template instance for a plan the dispatcher made, and every
 // struct a launcher takes is declared here: the dispatcher does not see the kernel bodies, so editing one rebuilds its
 // family's unit only.
@@ -61,7 +64,6 @@ __device__ __forceinline__ int fdiv(int n, int d, float rcp) {
 // 115), and the conv kernels gain 10-13 % (tools/ubench/depth_lab.hip).  The descriptor's range
 // check also gives the zero padding for free: a lane outside the image uses offset 0xFFFFFFFF.
 typedef int i32x4_t __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 #define HRSEG_BUF_FLAGS 0x00020000      // raw buffer, 32-bit data format (gfx9 family word 3)
 #define HRSEG_BUF_OOB 0xFFFFFFFFu
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float* base, size_t bytes) {
@@ -73,7 +75,7 @@ __device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, unsigned vo
 }
 // ... and stores: a lane whose offset is HRSEG_BUF_OOB writes nothing (no exec-mask branch around the store)
 __device__ __forceinline__ void buf_store4(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff_bytes, const f32x4& v) {
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), r, (int)voff, soff_bytes, 0);
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (int)voff, soff_bytes, 0);
 }
 
 // swizzle of the 16-byte slot inside a 64-byte LDS row so that every 16-lane

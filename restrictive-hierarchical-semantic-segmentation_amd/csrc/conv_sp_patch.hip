@@ -1,7 +1,5 @@
 // Split-precision implicit GEMM, block-synchronous halo-patch body (3x3 stride 1): kernel instances + launcher.
-#include "conv_common.h"
-#include "conv_sp.h"
-
+#include "sp_patch.h"
 
 template <int NS>
 static int launch_patch_sp(const IgemmArgs& a, int wtn, int cs, int flip, int blocks, int ntotal, hipStream_t st) {

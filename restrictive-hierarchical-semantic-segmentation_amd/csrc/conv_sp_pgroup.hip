@@ -1,8 +1,23 @@
 // Split-precision grouped launch whose problems run either the halo-patch or the im2col body: kernel instances + launcher.
-#include "conv_common.h"
-#include "conv_sp.h"
+#include "sp_im2col.h"
+#include "sp_patch.h"
 
+// grouped launch whose problems run either body (the parallel HRNet branches: the wide high-resolution
+// branches take the halo-patch body, the small low-resolution ones the im2col body with split-K)
+template <int NS, int WTM, int WTN, int CS, int FLIP>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sp_patch_min_waves(NS, WTN, CS), 2)))
+void igemm_sp_pgroup_kernel(IgemmGroup grp) {
+  constexpr int A = SpPatchLds<NS, 8, WTN, CS>::BYTES, B = SpLds<NS, WTN>::BYTES;
+  __shared__ __attribute__((aligned(16))) unsigned char lds[A > B ? A : B];
+  int gi = 0;
+  while (gi + 1 < grp.n && (int)blockIdx.x >= grp.blk_end[gi]) ++gi;
+  const int local = blockIdx.x - (gi ? grp.blk_end[gi - 1] : 0);
+  const int tiles = grp.tiles[gi];
+  if (grp.kind[gi]) igemm_patch_sp_body<NS, 8, WTN, CS, FLIP>(grp.a[gi], lds, local, 1 << 29, tiles);   // one tile per block
+  else igemm_sp_body<NS, WTM, WTN>(grp.a[gi], lds, local % tiles, tiles, local / tiles, grp.ksplit[gi]);
+}
 
+// --------------------------------------------------------------------------- launchers
 template <int NS>
 static int launch_pgroup(const IgemmGroup& g, int wtm, int wtn, int cs, int flip, hipStream_t st) {
   const dim3 grid(g.blk_end[g.n - 1]);

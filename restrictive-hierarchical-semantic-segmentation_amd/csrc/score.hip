@@ -63,7 +63,7 @@ __device__ __forceinline__ ScoreTile score_load(const u8* __restrict__ pred, con
   const uintptr_t ga = (uintptr_t)gt + (uintptr_t)i0, fa = ga & ~(uintptr_t)3;
   const bool inside = i0 >= 0 && i0 + SCORE_LANE_STEP <= HW;
   if (inside && fa >= (uintptr_t)gt && fa + 20 <= (uintptr_t)gt + (uintptr_t)HW) {
-    const hrseg_u32x4 pv = *reinterpret_cast<const hrseg_u32x4*>(pred + i0);       // pred + i0 is 16-byte aligned
+    const u32x4 pv = *reinterpret_cast<const u32x4*>(pred + i0);       // pred + i0 is 16-byte aligned
     const unsigned* __restrict__ gw = reinterpret_cast<const unsigned*>(fa);
     const unsigned w0 = gw[0], w1 = gw[1], w2 = gw[2], w3 = gw[3], w4 = gw[4];
     const unsigned sh = (unsigned)(ga & 3);

@@ -1,5 +1,5 @@
 """torch-CPU model of the PRE-SPLIT activation format (include/hrseg.h: hrseg_bn_fwd_t.z_split writes it,
-hrseg_conv_shape_t.x_split / hrseg_bn_fwd_t.residual_split read it; csrc/common.h: hrseg_split_f16x2 / hrseg_join_f16x2).
+hrseg_conv_shape_t.x_split / hrseg_bn_fwd_t.residual_split read it; csrc/sp_arith.h: hrseg_split_f16x2 / hrseg_join_f16x2).
 
 One fp32 value x becomes two fp16 pieces:
 

@@ -1,5 +1,5 @@
-"""The split-precision convolution kernels (csrc/conv_sp.h) through the C ABI against a plain fp32 torch-CPU
-convolution, mode by mode, and the bf16-input / fp32-accumulate path of BASELINE.json configs[4] on the models.
+"""The split-precision convolution kernels (csrc/sp_arith.h; bodies: sp_im2col.h, sp_patch.h, conv_sp_*.hip, conv_ws.hip,
+conv_wgrad_sp.hip) through the C ABI against a plain fp32 torch-CPU convolution, mode by mode, and the bf16-input / fp32-accumulate path of BASELINE.json configs[4] on the models.
 
 Tolerances (relative to the reference's max magnitude), stated per mode:
   fp16x2, bf16x3 : 2e-5  -- fp32-grade: operands carry 22 / 24 significant bits, fp32 accumulation

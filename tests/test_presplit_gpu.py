@@ -1,8 +1,8 @@
 """Pre-split activations at the kernel level (include/hrseg.h: hrseg_bn_fwd_t.z_split / residual_split,
 hrseg_conv_shape_t.x_split), through the C ABI.
 
-The format has one writer and three readers, and writer and readers use the same split (csrc/common.h hrseg_split_f16x2 ==
-conv_sp.h sp_split<4, .> with scale 1), so the strongest statements available are cheap and are the ones asserted here:
+The format has one writer and three readers, and writer and readers use the same split (csrc/sp_arith.h: hrseg_split_f16x2 ==
+sp_split<4, .> with scale 1, side by side), so the strongest statements available are cheap and are the ones asserted here:
 
   writer    BatchNorm apply with z_split writes, byte for byte, split_ref.pack(z) of the fp32 tensor the same launch writes
             without the flag (tests/split_ref.py is a torch-CPU model that shares nothing with the library; it is pinned by

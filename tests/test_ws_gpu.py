@@ -1,4 +1,4 @@
-"""The wave-specialised halo-patch kernels (csrc/conv_sp.h: igemm_patch_ws_body, sp_weight_image_kernel) through
+"""The wave-specialised halo-patch kernels (csrc/conv_ws.hip: igemm_patch_ws_body, sp_weight_image_kernel) through
 the C ABI.
 
 The wave-specialised body adds up the same products in the same order as the block-synchronous halo-patch body
