@@ -907,6 +907,10 @@ extern "C" int hrseg_head_bwd(const float* f, int ldf, const float* gb, const fl
   HRSEG_CHECK_ARG(f && w && dz && dw && B > 0 && hw > 0 && F > 0 && F % 4 == 0 && F <= 1024 && Cout > 0 &&
                       Cout <= 8 && (gb == nullptr) == (dgb == nullptr),
                   "hrseg_head_bwd: bad arguments (F=%d Cout=%d)", F, Cout);
+  // the kernel moves 16 bytes at f + r*ldf + 4*cq and df + r*lddf + 4*cq: a row stride that is not a multiple of 4 floats
+  // would be a misaligned access, one below the row length an overlap
+  HRSEG_CHECK_ARG(ldf >= F && ldf % 4 == 0 && lddz >= Cout && (df == nullptr || (lddf >= F && lddf % 4 == 0)),
+                  "hrseg_head_bwd: bad row strides (ldf=%d lddz=%d lddf=%d for F=%d Cout=%d)", ldf, lddz, lddf, F, Cout);
   hipStream_t st = (hipStream_t)stream;
   long chunks = 2048 / B;
   if (chunks < 1) chunks = 1;

@@ -60,6 +60,17 @@ def test_invalid_arguments_are_reported_without_a_gpu():
     assert lib.hrseg_set_scratch(None, 0) == 0                      # detach: always fine
     assert lib.hrseg_set_scratch(ctypes.c_void_p(4096), 1024) == -1 and b"at least 1 MiB" in lib.hrseg_last_error_string()
     assert lib.hrseg_set_scratch(ctypes.c_void_p(4097), 1 << 20) == -1 and b"aligned" in lib.hrseg_last_error_string()
+    # hrseg_head_bwd moves 16 bytes per channel quad: row strides below the row length or off the 4-float grid are refused
+    # before anything is launched (placeholder pointers, never dereferenced)
+    lib.hrseg_head_bwd.argtypes = _lib.PROTOTYPES["hrseg_head_bwd"]
+    P = ctypes.c_void_p(4096)
+
+    def head_bwd(ldf=64, lddz=5, df=P, lddf=64):
+        return lib.hrseg_head_bwd(P, ldf, None, P, P, lddz, df, lddf, 0, P, P, None, 2, 143, 64, 5, None)
+    for bad in (dict(ldf=60), dict(ldf=66), dict(lddz=4), dict(lddf=60), dict(lddf=67)):
+        assert head_bwd(**bad) == -1 and b"hrseg_head_bwd: bad row strides" in lib.hrseg_last_error_string(), bad
+    assert lib.hrseg_head_bwd(P, 64, None, P, P, 5, P, 64, 0, P, P, None, 2, 143, 62, 5, None) == -1
+    assert b"hrseg_head_bwd: bad arguments" in lib.hrseg_last_error_string()
     lib.hrseg_tune.argtypes = [ctypes.c_char_p, ctypes.c_int]
     assert lib.hrseg_tune(b"igemm_wtm", 0) == 0
     assert lib.hrseg_tune(b"no_such_knob", 1) == -1 and b"unknown key" in lib.hrseg_last_error_string()

@@ -1,5 +1,7 @@
-"""Every HIP entry point against a plain fp32 torch-CPU reference of the same op (through the
-C ABI, on the GPU).  Tolerances are relative to the reference's max magnitude."""
+"""The HIP entry points against a plain fp32 torch-CPU reference of the same op (through the
+C ABI, on the GPU), one or a few shapes each.  Tolerances are relative to the reference's max magnitude.
+The sweep over the head / resize / composition / loss / consistency / AdamW kernels' templates, loops and
+flags -- and hrseg_consistency_bwd and hrseg_adamw_dev, which nothing here calls -- is tests/test_headloss_gpu.py."""
 import numpy as np
 import pytest
 import torch

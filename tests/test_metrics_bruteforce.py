@@ -88,6 +88,18 @@ def _cases():
     ps = g.random((2, 4, 7, 7)).astype(np.float32)
     ps[0, :, 0, 0] = 0.25
     out.append(("soft_probs_root", ps, out[0][2][:, :, :7, :7].copy(), False))
+    # 9 and 16 classes, root and child: the 16-wide instance of the counting kernel (C > 8), a 17 x 17 matrix for the child
+    # level.  A generator of their own, so that the cases above keep their values.
+    g2 = np.random.Generator(np.random.PCG64(2025))
+    for C, child in ((9, False), (9, True), (16, False), (16, True)):
+        B, H, W = 2, 7, 6
+        p = np.moveaxis(np.eye(C, dtype=np.float32)[g2.integers(0, C, size=(B, H, W))], -1, 1).copy()
+        t = np.moveaxis(np.eye(C, dtype=np.float32)[g2.integers(0, C, size=(B, H, W))], -1, 1).copy()
+        if child:
+            outside = g2.random((B, H, W)) < 0.35
+            p[np.broadcast_to(outside[:, None], p.shape)] = 0.0
+            t[np.broadcast_to(outside[:, None], t.shape)] = 0.0
+        out.append((f"wide{C}_{'child' if child else 'root'}", p, t, child))
     return out
 
 
