@@ -445,6 +445,32 @@ int hrseg_adamw_dev(float* p, const float* g, float* m, float* v, long n, const 
                     float* state, hrseg_stream_t stream);
 int hrseg_fill(float* p, float v, long n, hrseg_stream_t stream);
 
+/* ------------------------------------------------------------------ gradient clipping / non-finite step skip
+ * Global L2 norm of the flat gradient buffer AdamW is about to consume, torch.nn.utils.clip_grad_norm_'s
+ * coefficient from it, and an AdamW step that applies the coefficient or leaves everything alone when a gradient
+ * element is not finite.  With g the buffer and s = hyper[5] (grad_scale):
+ *   S = sum (double)g_i * (double)g_i   (fp64 from the first multiply on: no fp32 overflow or underflow)
+ *   norm = |s| * sqrt(S);  finite = isfinite(S) && isfinite(s);  coef = min(1, max_norm / (norm + 1e-6))
+ * evaluated in fp64 and stored as fp32.  max_norm = +inf gives coef == 1.0f exactly.
+ * The sum is taken over hrseg_grad_sumsq_chunks(n) chunks of hrseg_grad_sumsq_chunk_len() floats, one fp64 partial each;
+ * chunking and summation order depend on n alone, no atomics: bit-reproducible, and equal on every rank that holds
+ * the same bytes.  A launch uses at most hrseg_grad_sumsq_max_blocks() blocks (more chunks: a block takes several).
+ * Device buffers: clipcfg = {max_norm, skip_nonfinite (0 or 1)}; clip = {norm, coef, finite (0 or 1), skipped_total};
+ * partial = nchunks doubles.  hrseg_grad_clip_finalize also advances state = {step, 1-beta1^step,
+ * 1/sqrt(1-beta2^step)} by one step (what hrseg_adamw_dev does itself) -- unless skip_nonfinite is set and finite is 0:
+ * then the step is void, state stays, skipped_total goes up by one, and hrseg_adamw_dev_clip returns without touching
+ * p, m, v.  Otherwise hrseg_adamw_dev_clip is hrseg_adamw_dev's update with the gradient (g * s) * coef; with
+ * coef == 1 it is bit-identical to it.  Order per step: hrseg_grad_sumsq, hrseg_grad_clip_finalize,
+ * hrseg_adamw_dev_clip, on one stream. */
+int hrseg_grad_sumsq_chunk_len(void);
+int hrseg_grad_sumsq_max_blocks(void);
+int hrseg_grad_sumsq_chunks(long n);                    /* number of partials for n elements; -1: n out of range */
+int hrseg_grad_sumsq(const float* g, long n, double* partial, int nchunks, hrseg_stream_t stream);
+int hrseg_grad_clip_finalize(const double* partial, int nchunks, const float* hyper, const float* clipcfg,
+                             float* state, float* clip, hrseg_stream_t stream);
+int hrseg_adamw_dev_clip(float* p, const float* g, float* m, float* v, long n, const float* hyper,
+                         const float* state, const float* clipcfg, const float* clip, hrseg_stream_t stream);
+
 /* ------------------------------------------------------------------ gradient exchange (data parallelism)
  * Thin wrappers over RCCL for the one collective of the path: the in-place sum of a flat fp32 gradient
  * bucket over the ranks (replaces nn.DataParallel's reduce-add, train.py:509-510).  librccl.so is opened

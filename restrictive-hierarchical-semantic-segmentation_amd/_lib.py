@@ -115,6 +115,9 @@ PROTOTYPES = {
     "hrseg_adamw": [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _f, _f, _f, _p],
     "hrseg_adamw_dev": [_p, _p, _p, _p, _l, _p, _p, _p],
     "hrseg_fill": [_p, _f, _l, _p],
+    "hrseg_grad_sumsq": [_p, _l, _p, _i, _p],
+    "hrseg_grad_clip_finalize": [_p, _i, _p, _p, _p, _p, _p],
+    "hrseg_adamw_dev_clip": [_p, _p, _p, _p, _l, _p, _p, _p, _p, _p],
     "hrseg_encode_targets": [_p, _p, C.POINTER(C.c_int), _p, _i, _i, _l, _p],
     "hrseg_augment_image": [_p, _p, _p, _p, _i, _i, _i, _p, C.c_size_t, _p],
     "hrseg_augment_targets": [_p, _p, _p, C.POINTER(C.c_int), _p, _p, _i, _i, _i, _i, _i, _p, C.c_size_t, _p],
@@ -133,6 +136,9 @@ RAW_PROTOTYPES = {
     "hrseg_set_scratch": [_p, C.c_size_t],
     "hrseg_set_weight_image_arena": [_p, C.c_size_t, _p, C.c_size_t, _p, _p, _p, _p],
     "hrseg_augment_workspace": [_i, _i, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)],
+    "hrseg_grad_sumsq_chunk_len": [],
+    "hrseg_grad_sumsq_max_blocks": [],
+    "hrseg_grad_sumsq_chunks": [_l],
 }
 
 _lib.hrseg_last_error_string.restype = C.c_char_p
@@ -287,6 +293,24 @@ if abi_version() != ABI_VERSION:
 
 def last_error() -> str:
     return (_lib.hrseg_last_error_string() or b"").decode()
+
+
+def grad_sumsq_chunk_len() -> int:
+    """floats per fp64 partial of hrseg_grad_sumsq (a constant of the library)"""
+    return int(raw["hrseg_grad_sumsq_chunk_len"]())
+
+
+def grad_sumsq_max_blocks() -> int:
+    """most blocks one hrseg_grad_sumsq launch uses (more chunks than this: a block takes several)"""
+    return int(raw["hrseg_grad_sumsq_max_blocks"]())
+
+
+def grad_sumsq_chunks(n) -> int:
+    """number of fp64 partials hrseg_grad_sumsq writes for n elements (a function of n alone)"""
+    k = int(raw["hrseg_grad_sumsq_chunks"](int(n)))
+    if k < 0:
+        raise RuntimeError(f"hrseg_grad_sumsq_chunks failed ({k}): {last_error()}")
+    return k
 
 
 def ptr(t):

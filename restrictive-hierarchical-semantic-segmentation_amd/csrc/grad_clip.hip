@@ -1,0 +1,191 @@
+// Global-norm gradient clipping and the non-finite step skip of the fused AdamW, for gfx950.
+//
+// Three launches over the flat gradient buffer g[n] that AdamW is about to consume:
+//   1. grad_sumsq_kernel       partial[c] = sum over chunk c of (double)g_i * (double)g_i
+//   2. grad_clip_finalize_kernel  S = sum of the partials in a fixed order -> clip = {norm, coef, finite, skipped_total},
+//                              and the work of adam_tick_kernel (advance state) unless the step is void
+//   3. adamw_dev_clip_kernel   adamw_dev_kernel with gg = (g * grad_scale) * coef and an early return for a void step
+//
+// Chunk c is elements [c * GRAD_CHUNK, min(n, (c + 1) * GRAD_CHUNK)): length and count depend on n alone, never on the
+// launch grid, and within a chunk every element has a fixed place in a fixed summation tree (thread t takes the
+// 16-byte pieces t, t + 256, ... in order; xor-shuffle tree per wave; the four wave sums are added in wave order).  No
+// atomics anywhere: the result is bit-reproducible from run to run and equal on every rank that holds the same bytes,
+// whatever the "deterministic" knob says.  Every element is widened to fp64 BEFORE it is squared, so a finite fp32
+// gradient can neither overflow nor underflow the sum (|g| <= 3.4e38 -> g^2 <= 1.2e77, n <= 2^63; the smallest
+// subnormal squared is 2e-90), and S is finite exactly when every element is.
+#include "common.h"
+
+#define GRAD_CHUNK 8192          // floats per partial: 256 threads x 8 pieces of 16 bytes
+#define GRAD_MAX_BLOCKS 2048     // 256 CUs x 8 resident blocks of 256 threads; more chunks than this: a block takes several
+
+__device__ __forceinline__ f32x4 gc_ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+__device__ __forceinline__ void gc_st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
+
+__device__ __forceinline__ double sq4(double acc, f32x4 v) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const double d = (double)v[j];
+    acc = fma(d, d, acc);
+  }
+  return acc;
+}
+
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, long n,
+                                                         double* __restrict__ partial, int nchunks) {
+  __shared__ double red[4];
+  const int t = threadIdx.x;
+  for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const long lo = (long)c * GRAD_CHUNK;
+    const float* src = g + lo;
+    double acc = 0.0;
+    if (lo + GRAD_CHUNK <= n) {                   // block-uniform: eight unguarded 16-byte loads in flight per thread
+      f32x4 v[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[k] = gc_ld4(src + 4 * (t + 256 * k));
+      __builtin_amdgcn_sched_barrier(0);          // all eight loads are issued before the first one is waited for
+#pragma unroll
+      for (int k = 0; k < 8; ++k) acc = sq4(acc, v[k]);
+    } else {                                      // the last chunk: whole pieces, then a scalar tail of len % 4 elements
+      // 1 .. GRAD_CHUNK - 1, taken here as an int: as a 64-bit min(n - lo, GRAD_CHUNK) ahead of the branch the compiler's
+      // scalar select read a stale condition code and this path ran with the full length (caught by the n = 1 test)
+      const int len = (int)(n - lo);
+      const int nvec = len >> 2;
+      for (int i = t; i < nvec; i += 256) acc = sq4(acc, gc_ld4(src + 4 * i));
+      const int tail = len & 3;
+      if (t < tail) {
+        const double d = (double)src[4 * nvec + t];
+        acc = fma(d, d, acc);
+      }
+    }
+    acc = wave_sum_d(acc);
+    if ((t & 63) == 0) red[t >> 6] = acc;
+    __syncthreads();
+    if (t == 0) partial[c] = ((red[0] + red[1]) + red[2]) + red[3];
+    __syncthreads();                              // red is written again on the block's next trip
+  }
+}
+
+// hyper = {lr, beta1, beta2, eps, weight_decay, grad_scale}; clipcfg = {max_norm, skip_nonfinite};
+// state = {step, bc1, 1/sqrt(bc2)}; clip = {norm, coef, finite, skipped_total}
+__global__ __launch_bounds__(256) void grad_clip_finalize_kernel(const double* __restrict__ partial, int nchunks,
+                                                                 const float* __restrict__ hyper,
+                                                                 const float* __restrict__ clipcfg, float* state,
+                                                                 float* clip) {
+  __shared__ double red[4];
+  const int t = threadIdx.x;
+  double acc = 0.0;
+  for (int i = t; i < nchunks; i += 256) acc += partial[i];
+  acc = wave_sum_d(acc);
+  if ((t & 63) == 0) red[t >> 6] = acc;
+  __syncthreads();
+  if (t != 0) return;
+  const double S = ((red[0] + red[1]) + red[2]) + red[3];
+  const double s = (double)hyper[5];
+  const double norm = fabs(s) * sqrt(S);
+  const bool finite = isfinite(S) && isfinite(s);
+  // torch.nn.utils.clip_grad_norm_ (norm_type 2): clamp(max_norm / (norm + 1e-6), max=1.0); a NaN quotient stays NaN
+  const double q = (double)clipcfg[0] / (norm + 1e-6);
+  const double coef = (q > 1.0) ? 1.0 : q;
+  const bool is_void = (clipcfg[1] != 0.f) && !finite;
+  clip[0] = (float)norm;
+  clip[1] = (float)coef;
+  clip[2] = finite ? 1.f : 0.f;
+  if (is_void) {
+    clip[3] = clip[3] + 1.f;
+  } else {                                        // adam_tick_kernel
+    const double step = (double)state[0] + 1.0;
+    state[0] = (float)step;
+    state[1] = (float)(1.0 - pow((double)hyper[1], step));
+    state[2] = (float)(1.0 / sqrt(1.0 - pow((double)hyper[2], step)));
+  }
+}
+
+// One element group of the update.  CLIP = false is, expression by expression, the body of adamw_dev_kernel
+// (bn_elem.hip), so that a step whose coef is exactly 1 rounds exactly as that kernel does.
+template <bool CLIP>
+__device__ __forceinline__ void adamw_clip_body(float* __restrict__ p, const float* __restrict__ g,
+                                                float* __restrict__ m, float* __restrict__ v, long n4, long n, float lr,
+                                                float b1, float b2, float eps, float wd, float gscale, float coef,
+                                                float step, float rsqrt_bc2) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    f32x4 pp = gc_ld4(p + 4 * i), gg = gc_ld4(g + 4 * i) * gscale, mm = gc_ld4(m + 4 * i), vv = gc_ld4(v + 4 * i);
+    if (CLIP) gg = gg * coef;
+    pp = pp * (1.f - lr * wd);
+    mm = mm + (gg - mm) * (1.f - b1);
+    vv = vv * b2 + gg * gg * (1.f - b2);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) pp[j] -= step * mm[j] / (sqrtf(vv[j]) * rsqrt_bc2 + eps);
+    gc_st4(p + 4 * i, pp);
+    gc_st4(m + 4 * i, mm);
+    gc_st4(v + 4 * i, vv);
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n - 4 * n4)) {
+    const long i = 4 * n4 + threadIdx.x;
+    float pp = p[i] * (1.f - lr * wd), gg = g[i] * gscale;
+    if (CLIP) gg = gg * coef;
+    const float mm = m[i] + (gg - m[i]) * (1.f - b1), vv = v[i] * b2 + gg * gg * (1.f - b2);
+    p[i] = pp - step * mm / (sqrtf(vv) * rsqrt_bc2 + eps);
+    m[i] = mm;
+    v[i] = vv;
+  }
+}
+
+__global__ __launch_bounds__(256) void adamw_dev_clip_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                             float* __restrict__ m, float* __restrict__ v, long n4, long n,
+                                                             const float* __restrict__ hyper,
+                                                             const float* __restrict__ state,
+                                                             const float* __restrict__ clipcfg,
+                                                             const float* __restrict__ clip) {
+  if (clipcfg[1] != 0.f && clip[2] == 0.f) return;      // void step: p, m, v stay as they are (grid-uniform)
+  const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4], gscale = hyper[5];
+  const float step = lr / state[1], rsqrt_bc2 = state[2], coef = clip[1];
+  if (coef == 1.f) adamw_clip_body<false>(p, g, m, v, n4, n, lr, b1, b2, eps, wd, gscale, coef, step, rsqrt_bc2);
+  else adamw_clip_body<true>(p, g, m, v, n4, n, lr, b1, b2, eps, wd, gscale, coef, step, rsqrt_bc2);
+}
+
+// --------------------------------------------------------------------------- entry points
+extern "C" int hrseg_grad_sumsq_chunk_len(void) { return GRAD_CHUNK; }
+extern "C" int hrseg_grad_sumsq_max_blocks(void) { return GRAD_MAX_BLOCKS; }
+
+extern "C" int hrseg_grad_sumsq_chunks(long n) {
+  HRSEG_CHECK_ARG(n > 0 && (n + GRAD_CHUNK - 1) / GRAD_CHUNK <= 0x7fffffffL, "hrseg_grad_sumsq_chunks: n=%ld out of range", n);
+  return (int)((n + GRAD_CHUNK - 1) / GRAD_CHUNK);
+}
+
+extern "C" int hrseg_grad_sumsq(const float* g, long n, double* partial, int nchunks, hrseg_stream_t stream) {
+  HRSEG_CHECK_ARG(g && partial && n > 0, "hrseg_grad_sumsq: bad arguments");
+  HRSEG_CHECK_ARG(((uintptr_t)g % 16 == 0) && ((uintptr_t)partial % 8 == 0),
+                  "hrseg_grad_sumsq: g must be 16-byte aligned, partial 8-byte aligned");
+  HRSEG_CHECK_ARG(hrseg_grad_sumsq_chunks(n) == nchunks, "hrseg_grad_sumsq: nchunks=%d does not match n=%ld (%ld per chunk)",
+                  nchunks, n, (long)GRAD_CHUNK);
+  const int blocks = nchunks < GRAD_MAX_BLOCKS ? nchunks : GRAD_MAX_BLOCKS;
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, g, n, partial, nchunks);
+  HRSEG_LAUNCH_CHECK("grad_sumsq");
+  return 0;
+}
+
+extern "C" int hrseg_grad_clip_finalize(const double* partial, int nchunks, const float* hyper, const float* clipcfg,
+                                        float* state, float* clip, hrseg_stream_t stream) {
+  HRSEG_CHECK_ARG(partial && hyper && clipcfg && state && clip && nchunks > 0, "hrseg_grad_clip_finalize: bad arguments");
+  HRSEG_CHECK_ARG((uintptr_t)partial % 8 == 0, "hrseg_grad_clip_finalize: partial must be 8-byte aligned");
+  hipLaunchKernelGGL(grad_clip_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partial, nchunks, hyper, clipcfg,
+                     state, clip);
+  HRSEG_LAUNCH_CHECK("grad_clip_finalize");
+  return 0;
+}
+
+extern "C" int hrseg_adamw_dev_clip(float* p, const float* g, float* m, float* v, long n, const float* hyper,
+                                    const float* state, const float* clipcfg, const float* clip, hrseg_stream_t stream) {
+  HRSEG_CHECK_ARG(p && g && m && v && hyper && state && clipcfg && clip && n > 0, "hrseg_adamw_dev_clip: bad arguments");
+  HRSEG_CHECK_ARG(((uintptr_t)p % 16 == 0) && ((uintptr_t)g % 16 == 0) && ((uintptr_t)m % 16 == 0) &&
+                      ((uintptr_t)v % 16 == 0),
+                  "hrseg_adamw_dev_clip: buffers must be 16-byte aligned");
+  const long n4 = n / 4;
+  long blocks = (n4 + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(adamw_dev_clip_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4, n, hyper,
+                     state, clipcfg, clip);
+  HRSEG_LAUNCH_CHECK("adamw_dev_clip");
+  return 0;
+}

@@ -981,3 +981,26 @@ def adamw(p, g, m, v, lr, beta1, beta2, eps, wd, step, gscale=1.0):
 def adamw_dev(p, g, m, v, hyper, state):
     """graph-replayable AdamW step: hyper/state are device tensors (see hrseg.h)"""
     call("hrseg_adamw_dev", ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), ptr(hyper), ptr(state))
+
+
+def grad_sumsq(g, partial=None):
+    """fp64 partial sums of squares of the flat fp32 buffer g, one per chunk of _lib.grad_sumsq_chunk_len() elements
+    (hrseg_grad_sumsq: chunking a function of g.numel() alone, no atomics) -> partial [nchunks] float64"""
+    n = g.numel()
+    nchunks = _lib.grad_sumsq_chunks(n)
+    if partial is None:
+        partial = torch.empty(nchunks, dtype=torch.float64, device=g.device)
+    call("hrseg_grad_sumsq", ptr(g), n, ptr(partial), partial.numel())
+    return partial
+
+
+def grad_clip_finalize(partial, hyper, clipcfg, state, clip):
+    """partials -> clip = {norm, coef, finite, skipped_total}; advances AdamW's device `state` unless the step is void
+    (clipcfg = {max_norm, skip_nonfinite}; see hrseg.h)"""
+    call("hrseg_grad_clip_finalize", ptr(partial), partial.numel(), ptr(hyper), ptr(clipcfg), ptr(state), ptr(clip))
+
+
+def adamw_dev_clip(p, g, m, v, hyper, state, clipcfg, clip):
+    """adamw_dev with the gradient scaled by clip's coefficient, or nothing at all on a void step; `state` was advanced
+    by grad_clip_finalize"""
+    call("hrseg_adamw_dev_clip", ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), ptr(hyper), ptr(state), ptr(clipcfg), ptr(clip))

@@ -11,6 +11,16 @@ averaged inside the fused AdamW (grad_scale = 1/world).  BatchNorm statistics
 stay per-rank, exactly as the reference's DataParallel + SyncBatchNorm without
 a process group behaves.
 
+Gradient clipping and the non-finite step skip of FusedAdamW (max_grad_norm /
+skip_nonfinite) need no collective of their own: the norm is taken inside
+optimizer.step(), i.e. after the "end" call below has made the compute stream
+wait for the last bucket -- the place AdamW waits today -- on the buffer AdamW
+reads.  Every rank then reduces the same all-reduced bytes with the same
+chunking (a function of the buffer length alone, no atomics), so the ranks
+agree bitwise on the norm, on the coefficient and on skipping; a NaN in one
+rank's local gradient reaches every rank through the sum and voids the step
+everywhere.
+
 Bucket boundaries are the tape marks the model emits ("shared_head",
 "transition3", ...): when the reverse pass crosses mark m, every parameter
 registered at or after module m is final, so [offset(m), previous boundary) goes

@@ -30,9 +30,22 @@ from .utils.hierarchy import get_classes  # noqa: F401  (API: train.get_classes)
 class FusedAdamW(torch.optim.Optimizer):
     """torch.optim.AdamW semantics (reference train.py:513-516: lr only, defaults
     betas=(0.9,0.999), eps=1e-8, weight_decay=0.01) as ONE kernel over the model's flat
-    parameter / gradient buffers.  ``grad_scale`` folds the 1/world_size of DDP."""
+    parameter / gradient buffers.  ``grad_scale`` folds the 1/world_size of DDP.
 
-    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+    Two options, both off by default (the step then makes exactly the calls it made without them):
+    ``max_grad_norm``: torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm) before the update -- the gradient AdamW
+    consumes is multiplied by min(1, max_grad_norm / (norm + 1e-6)), norm = the global L2 norm of that gradient
+    (grad_scale included; under data parallelism: of the averaged gradient).  Gradients live in the flat buffer, not in
+    ``p.grad``, so torch's function cannot be used with this package; the threshold goes here instead.  It is read from
+    device memory by the kernels: assigning ``optimizer.max_grad_norm = x`` between steps takes effect on the next
+    step, recorded tape or captured graph included (None <-> a number switches the path and re-records).
+    ``skip_nonfinite``: a step whose gradient holds a NaN or an infinity is void -- parameters, moments and the step
+    count stay bitwise as they were and ``skipped_steps`` goes up by one.
+    Either option makes the step three launches (sum of squares, finalize + step count, update); ``grad_stats`` is the
+    device tensor {norm, coef, finite, skipped_total} of the latest step."""
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None,
+                 skip_nonfinite=False):
         if isinstance(lr, (list, tuple)):          # the reference passes eval("[1e-4]")
             lr = lr[0]
         self.model = model
@@ -41,13 +54,54 @@ class FusedAdamW(torch.optim.Optimizer):
         self._hyper = self._state = self._hyper_host = None
         self._step = 0
         self.grad_scale = 1.0
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError(f"FusedAdamW: max_grad_norm={max_grad_norm} must be positive (None: no clipping)")
+        self.max_grad_norm = max_grad_norm
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._clipcfg = self._clipcfg_host = self._partial = None
+        self.grad_stats = None              # device {norm, coef, finite, skipped_total} once the clipping path has run
+        self.last_grad_norm = None          # set by train_epoch from the step's one readback
+        self.last_step_skipped = False
+
+    @property
+    def clip_path(self):
+        """does step() take the three-launch path (norm, finalize, update with verdict)?"""
+        return self.max_grad_norm is not None or self.skip_nonfinite
+
+    @property
+    def skipped_steps(self):
+        """void steps so far, read from the device counter (a device->host sync, like state_dict)"""
+        return 0 if self.grad_stats is None else int(self.grad_stats[3].item())
+
+    def _sync_clip(self, device, numel):
+        """the clipping path's device buffers: clipcfg = {max_norm, skip} follows the host values like _hyper does"""
+        from . import _lib
+        host = (float("inf") if self.max_grad_norm is None else float(self.max_grad_norm), float(self.skip_nonfinite))
+        if self._clipcfg is None or self._clipcfg.device != device:
+            self._clipcfg = torch.tensor(host, dtype=torch.float32, device=device)
+            self._clipcfg_host = host
+            skipped = 0.0 if self.grad_stats is None else float(self.grad_stats[3].item())
+            self.grad_stats = torch.tensor([0.0, 1.0, 1.0, skipped], dtype=torch.float32, device=device)
+        elif host != self._clipcfg_host:
+            self._clipcfg.copy_(torch.tensor(host, dtype=torch.float32))
+            self._clipcfg_host = host
+        if numel and (self._partial is None or self._partial.device != device or
+                      self._partial.numel() != _lib.grad_sumsq_chunks(numel)):
+            self._partial = torch.empty(_lib.grad_sumsq_chunks(numel), dtype=torch.float64, device=device)
 
     def _sync_hyper(self, device):
         """device copies of the scalars (read by the kernel, so a captured graph sees updates)"""
         g = self.param_groups[0]
         host = (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
                 float(g["weight_decay"]), float(self.grad_scale))
+        if self.clip_path:
+            flat = getattr(self.model, "_flat", None)
+            self._sync_clip(device, 0 if flat is None else flat.numel)
         if self._hyper is None or self._hyper.device != device:
+            if self._hyper is not None and self._state is not None:
+                # moved to another device: the device counter is the truth (void steps and graph replays do not
+                # advance the host's count the same way)
+                self._step = int(self._state[0].item())
             self._hyper = torch.tensor(host, dtype=torch.float32, device=device)
             self._state = torch.tensor([float(self._step), 0.0, 0.0], dtype=torch.float32, device=device)
             self._hyper_host = host
@@ -64,7 +118,15 @@ class FusedAdamW(torch.optim.Optimizer):
         if not torch.cuda.is_current_stream_capturing():
             self._sync_hyper(flat.data.device)
         self._step += 1
-        ops.adamw_dev(flat.data, flat.grad, self._m, self._v, self._hyper, self._state)
+        if self.clip_path:
+            if self._partial is None or self._partial.device != flat.data.device:     # (only while capturing without a warm-up)
+                self._sync_clip(flat.data.device, flat.numel)
+            ops.grad_sumsq(flat.grad, self._partial)
+            ops.grad_clip_finalize(self._partial, self._hyper, self._clipcfg, self._state, self.grad_stats)
+            ops.adamw_dev_clip(flat.data, flat.grad, self._m, self._v, self._hyper, self._state, self._clipcfg,
+                               self.grad_stats)
+        else:
+            ops.adamw_dev(flat.data, flat.grad, self._m, self._v, self._hyper, self._state)
         if hasattr(self.model, "notify_parameters_changed"):
             self.model.notify_parameters_changed()
 
@@ -82,6 +144,8 @@ class FusedAdamW(torch.optim.Optimizer):
         if self._m is None or self._m.numel() != flat.numel or self._m.device != flat.data.device:
             self._m = torch.zeros_like(flat.data)
             self._v = torch.zeros_like(flat.data)
+        if self.clip_path:
+            self._sync_clip(flat.data.device, flat.numel)
         return flat
 
     def state_dict(self):
@@ -122,7 +186,7 @@ class FusedAdamW(torch.optim.Optimizer):
                 flat.view_of(self._v, p).copy_(st["exp_avg_sq"].to(self._v.device))
                 step = max(step, int(float(st["step"])))
         self._step = step
-        self._hyper = None                                # rebuilt (with the loaded step) on the next step
+        self._hyper = self._state = None                  # rebuilt (with the loaded step) on the next step
 
 
 def save_checkpoint(path, model, optimizer, epoch, loss, test_measure_mean=None, test_measure_std=None):
@@ -357,6 +421,7 @@ class TapedTrainStep:
         from . import _lib
         self._lib = _lib
         self.model, self.optimizer, self.args = model, optimizer, args
+        self.clip_path = bool(getattr(optimizer, "clip_path", False))      # fixed for the life of the recording
         m = _unwrap(model)
         for ce_fn, dice_fn in lossFuncts:
             if not (isinstance(ce_fn, losses.CrossEntropyLoss) and isinstance(dice_fn, losses.SoftDiceLoss)):
@@ -489,7 +554,20 @@ class TapedTrainStep:
         o = self.out
         parts = [v.double() for v in o["outs"] if v is not None] + [c[0].reshape(-1) for c in o["cons"]] + \
                 [torch.stack([sd[1] for sd in self.seed]).double(), o["vec"].reshape(-1).double()]
+        if self.clip_path:                   # {norm, finite, skipped_total} of the step's gradient ride at the end
+            gs = self.optimizer.grad_stats
+            parts += [gs[0:1].double(), gs[2:4].double()]
         return torch.cat(parts)
+
+    N_GRAD_STATS = 3
+
+    def grad_stats(self, host):
+        """host list of `_packed()` -> {"norm", "finite", "skipped_total"} of the step's gradient, or None when the
+        optimizer's clipping path is off (the packed vector then has no such entries)"""
+        if not self.clip_path:
+            return None
+        norm, finite, skipped = host[len(host) - self.N_GRAD_STATS:]
+        return {"norm": float(norm), "finite": bool(finite), "skipped_total": int(skipped)}
 
     def unpack(self, host):
         """host list of `_packed()` -> (loss, per-level CE+Dice list, metric rows [5][sum C]) with the arithmetic of
@@ -517,7 +595,7 @@ class TapedTrainStep:
                 total = np.float32(total + part)
                 count += ngroups
             loss = np.float32(loss + np.float32(total / np.float32(count)))
-        vec = host[i:]
+        vec = host[i:len(host) - (self.N_GRAD_STATS if self.clip_path else 0)]
         n = len(vec) // len(METRIC_NAMES)
         return float(loss), levels, [vec[k * n:(k + 1) * n] for k in range(len(METRIC_NAMES))]
 
@@ -546,7 +624,8 @@ def taped_step_for(model, optimizer, lossFuncts, args, class_tree, data, target,
            bool(getattr(m, "dedup_passes", False)), bool(getattr(m, "sequential_passes", False)),
            bool(getattr(m, "sync_bn", False)), _lib.deterministic(), _lib.tune_generation(), id(m._grad_hook),
            dist.is_available() and dist.is_initialized() and dist.get_world_size(), m.training,
-           tuple(tuple(float(v) for v in w) for w in args.level_weights))
+           tuple(tuple(float(v) for v in w) for w in args.level_weights),
+           bool(getattr(optimizer, "clip_path", False)))       # the path, not the threshold: that lives on the device
     cache = m.__dict__.setdefault("_hr_tapes", {})
     step = cache.get(key)
     if step is not None:
@@ -590,6 +669,7 @@ def train_epoch(model, device, train_loader, optimizer, epoch, lossFuncts, args,
             host = packed.tolist()                   # the only device->host copy of the step
             n_extra = len(METRIC_NAMES) * sum(args.num_classes) if multi else 0
             loss_value, levels, per = taped.unpack(host[:len(host) - n_extra])
+            stats = taped.grad_stats(host[:len(host) - n_extra])
             if multi:
                 tail, n = host[len(host) - n_extra:], sum(args.num_classes)
                 per = [tail[i * n:(i + 1) * n] for i in range(len(METRIC_NAMES))]
@@ -605,12 +685,25 @@ def train_epoch(model, device, train_loader, optimizer, epoch, lossFuncts, args,
                 from .parallel import all_reduce_confusion
                 cms = all_reduce_confusion(cms)          # metrics of the global batch, as on the reference's GPU 0
             vec = _metric_vectors(cms)
-            # the only device->host copy of the step: loss + every per-class metric
-            host = torch.cat([loss.reshape(1)] + [vec[k] for k in METRIC_NAMES]).tolist()
+            # the only device->host copy of the step: loss + every per-class metric (+ the gradient's norm and verdict)
+            gs = optimizer.grad_stats if getattr(optimizer, "clip_path", False) else None
+            host = torch.cat([loss.reshape(1)] + [vec[k] for k in METRIC_NAMES] + ([] if gs is None else [gs])).tolist()
+            stats = None
+            if gs is not None:
+                host, (norm, _, finite, skipped) = host[:-4], host[-4:]
+                stats = {"norm": float(norm), "finite": bool(finite), "skipped_total": int(skipped)}
             n = len(host[1:]) // len(METRIC_NAMES)
             _append_metrics(vec, accuracy, IoU, dice, precision, recall, clssMetrics,
                             host=[host[1 + i * n:1 + (i + 1) * n] for i in range(len(METRIC_NAMES))])
-        loss_accumulator.append(host[0])
+        skipped = False
+        if stats is not None:
+            skipped = bool(optimizer.skip_nonfinite) and not stats["finite"]
+            optimizer.last_grad_norm, optimizer.last_step_skipped = stats["norm"], skipped
+        if skipped:      # the step was void: its loss (NaN as a rule) stays out of the epoch's mean
+            print("\nTrain Epoch: {} batch {}: non-finite gradient (loss {}), step skipped ({} so far); left out of the "
+                  "average loss".format(epoch, batch_idx + 1, host[0], stats["skipped_total"]))
+        else:
+            loss_accumulator.append(host[0])
         last = batch_idx + 1 == n_batches
         print("\rTrain Epoch: {} [{}/{} ({:.1f}%)]\t{}: {:.6f}\tTime: {:.6f}".format(
             epoch, (batch_idx + 1) * len(data), len(train_loader.dataset), 100.0 * (batch_idx + 1) / n_batches,
