@@ -362,6 +362,39 @@ int hrseg_head_fwd(const float* f, int ldf, const float* gb, const float* w, con
 int hrseg_head_bwd(const float* f, int ldf, const float* gb, const float* w, const float* dz,
                    int lddz, float* df, int lddf, int df_accumulate, float* dw, float* dbias,
                    float* dgb, int B, long hw, int F, int Cout, hrseg_stream_t stream);
+/* The level heads on the UN-NORMALISED output of the layer in front of them (the HRNet shared head, models.py:614): where a
+ * conv + BatchNorm + ReLU output z = max(y * scale + shift, 0) has no residual and the level heads are its only readers,
+ * neither z nor its gradient has to exist in memory.  hrseg_head_bn_fwd is hrseg_head_fwd reading y (row stride ldy) and the
+ * BatchNorm's coef ([mean, rstd, scale, shift][F], hrseg_bn_fwd_t.coef after the finalize phase); it evaluates the expression
+ * of the BatchNorm apply phase on load, so the logits are the bits hrseg_bn_fwd_group + hrseg_head_fwd give. */
+int hrseg_head_bn_fwd(const float* y, int ldy, const float* coef, const float* gb, const float* w, const float* bias,
+                      float* z, int ldz, int B, long hw, int F, int Cout, hrseg_stream_t stream);
+/* Backward of the same region in two passes over y.  y holds nseg (1..8) equal segments of B samples of hw pixels (the
+ * batched level passes); segment s has its own head: w[s] [Cout[s]][F], FiLM pair gb[s] [B][2F] or NULL, logit gradient
+ * dzl[s] [B*hw][lddzl[s]].  With f = max(y * scale + shift, 0), u = sum_c W[c][:] dzl[pix][c] and g = (f > 0) ? gamma * u : 0:
+ *   hrseg_head_bn_bwd_reduce, segments [seg0, seg0 + nsegs): what hrseg_head_bwd accumulates (dw[s], dbias[s] +=, dgb[s] +=
+ *     when gb[s] != NULL; atomics, not offered in deterministic mode: HRSEG_ERR_UNSUPPORTED) AND the BatchNorm backward's
+ *     partial sums of g and g * xhat in the layout and summation order of hrseg_bn_bwd_group's reduce phase with nseg
+ *     segments (chunks [s * nchunks / nseg, (s + 1) * nchunks / nseg) belong to segment s); resets dy_absmax.  A level whose
+ *     logit gradient depends on another level's dgb (FiLM) is launched after it: one call per level, or one for all.
+ *   then hrseg_bn_bwd_group_phases(..., phases 2) on the same partial / nchunks / nseg: totals, dgamma, dbeta (unchanged).
+ *   hrseg_head_bn_bwd_apply, all segments: recomputes g and writes dy = scale * (g - mean g - xhat * mean g xhat), raising
+ *     dy_absmax as hrseg_bn_bwd_group's apply phase does.
+ * The zero fill of the feature gradient, hrseg_head_bwd's write of it and the two reads of it by the BatchNorm backward
+ * are gone.  partial: (nchunks + nseg) * 2 * F doubles; nchunks a multiple of nseg. */
+#define HRSEG_HEAD_BN_MAX_SEG 8
+typedef struct {
+  const float* y; int ldy; const float* coef;
+  int F, nseg, B; long hw;
+  double* partial; int nchunks;
+  float* dy_absmax;                                  /* optional, 64 floats, as hrseg_bn_bwd_t.dy_absmax */
+  float* dy; int lddy;                               /* out of the apply pass: [nseg*B*hw][F]            */
+  const float* gb[HRSEG_HEAD_BN_MAX_SEG]; const float* w[HRSEG_HEAD_BN_MAX_SEG];
+  const float* dzl[HRSEG_HEAD_BN_MAX_SEG]; int lddzl[HRSEG_HEAD_BN_MAX_SEG]; int Cout[HRSEG_HEAD_BN_MAX_SEG];
+  float* dw[HRSEG_HEAD_BN_MAX_SEG]; float* dbias[HRSEG_HEAD_BN_MAX_SEG]; float* dgb[HRSEG_HEAD_BN_MAX_SEG];
+} hrseg_head_bn_t;
+int hrseg_head_bn_bwd_reduce(const hrseg_head_bn_t* p, int seg0, int nsegs, hrseg_stream_t stream);
+int hrseg_head_bn_bwd_apply(const hrseg_head_bn_t* p, hrseg_stream_t stream);
 /* logits resize: NHWC low-res [B,Hi,Wi,C<=16] -> NCHW [B,C,Ho,Wo] bilinear
  * (F.interpolate at models.py:757,766,776) and its transpose */
 int hrseg_logits_up_fwd(const float* in, int ldin, int B, int Hi, int Wi, int C, float* out, int Ho,

@@ -172,7 +172,8 @@ class _Run:
         if self.shared_tape and n > 0:
             lv0 = self.levels[0]
             root = self.batched_feats if self.batched_feats is not None else lv0["feats"]
-            if root.grad is not None:
+            fused = m._head_bn_finish(root, self.levels)      # heads fused into the layer's BatchNorm backward: dy is ready
+            if root.grad is not None or fused:
                 lv0["rec"].backward(m._grad_hook)
             else:
                 lv0["rec"].tape.clear()
@@ -300,8 +301,11 @@ class _EngineModel(nn.Module):
             xin = None
             if batched:
                 if shared is None:
+                    # HRSEG_HEAD_BN_FUSE=0 (A/B switch, read per call): the layer in front of the heads keeps its own BatchNorm
+                    # apply / backward launches and the heads read and write the normalised tensor and its gradient
                     rec = Recorder(self.training, record, self._flat, bn_repeat=n_levels, bn_segments=n_levels, prec=prec,
-                                   sync=self._bn_sync(), wpersist=wpersist)
+                                   sync=self._bn_sync(), wpersist=wpersist,
+                                   defer_head=os.environ.get("HRSEG_HEAD_BN_FUSE", "1") != "0")
                     # the image batch stacked L times (library copy kernels: no ATen launch on the path, so a launch
                     # tape of the step is complete)
                     stack = torch.empty((n_levels * Bn, x.shape[2], x.shape[3], x.shape[1]), dtype=torch.float32,
@@ -311,7 +315,10 @@ class _EngineModel(nn.Module):
                     xx = Act(stack, needs_grad=False)
                     shared, shared_rec = self._backbone(rec, xx), rec
                     run.batched_feats = shared
-                feats, rec = Act(shared.data[L * Bn:(L + 1) * Bn]), shared_rec
+                if getattr(shared, "deferred", False):
+                    feats, rec = shared.slice(L * Bn, (L + 1) * Bn), shared_rec      # (y rows + coef: nothing is materialised)
+                else:
+                    feats, rec = Act(shared.data[L * Bn:(L + 1) * Bn]), shared_rec
                 feats.slot = L               # its gradient is rows [L*B, (L+1)*B) of the stacked feature gradient
             elif shared is None:
                 rec = Recorder(self.training, record, self._flat, bn_repeat=n_levels if dedup else 1, prec=prec,
@@ -405,7 +412,10 @@ class _EngineModel(nn.Module):
             lin = film.mlp[1]
             cond = ops.gap_nchw(p_prev)
             gb = ops.film_linear_fwd(cond, lin.weight._hr_store, lin.bias._hr_store)
-        zl = ops.head_fwd(feats.data, gb, w._hr_store, b._hr_store, cout=head.out_channels)
+        if getattr(feats, "deferred", False):       # the layer's BatchNorm + ReLU evaluated on load (engine.DeferredAct)
+            zl = ops.head_bn_fwd(feats.y, feats.coef, gb, w._hr_store, b._hr_store, cout=head.out_channels)
+        else:
+            zl = ops.head_fwd(feats.data, gb, w._hr_store, b._hr_store, cout=head.out_channels)
         if (zl.shape[1], zl.shape[2]) != tuple(size):
             z = ops.logits_up_fwd(zl, size[0], size[1], self.align_corners)
         else:
@@ -413,6 +423,48 @@ class _EngineModel(nn.Module):
         lv = dict(feats=feats, head=head, film=film, cond=cond, gb=gb, z=z, low=(zl.shape[1], zl.shape[2]),
                   hw=size[0] * size[1])
         return z, lv
+
+    def _head_bn_state(self, stacked, nseg):
+        """scratch of the fused head + BatchNorm backward of one step, kept on the deferred activation"""
+        st = stacked.fused
+        if st is None:
+            y = stacked.y
+            F, npix = y.shape[3], y.shape[0] * y.shape[1] * y.shape[2]
+            nch = ops.head_bn_chunks(npix, F, nseg)
+            prec = _lib.CONV_PRECISION[self.conv_dtype]
+            want_gmax = prec in (_lib.CONV_PRECISION["fp16x2"], _lib.CONV_PRECISION["auto"])
+            st = stacked.fused = dict(
+                nseg=nseg, nchunks=nch, heads=[None] * nseg, dy=None,
+                partial=torch.empty((nch + nseg) * 2 * F, dtype=torch.float64, device=y.device),
+                gmax=torch.empty((1, 64), dtype=torch.float32, device=y.device) if want_gmax else None)
+        return st
+
+    def _head_bn_finish(self, root, levels):
+        """after every level's head backward: finalize (unchanged kernel) + second pass -> the layer's dy, left on the
+        deferred activation for its conv_bn closure.  A level nothing flowed into contributes a zero logit gradient."""
+        st = getattr(root, "fused", None)
+        if st is None:
+            return False
+        if not root.deferred or root.grad is not None:
+            raise RuntimeError("hrseg_amd: the fused head backward started on an activation that was materialised since")
+        for s, h in enumerate(st["heads"]):
+            if h is None:
+                lv = levels[s]
+                head, feats = lv["head"], lv["feats"]
+                B, H, W, _ = feats.y.shape
+                dzl = ops.zeros((B, H, W, head.out_channels), torch.float32, root.y.device)
+                dgb = ops.zeros(lv["gb"].shape, torch.float32, root.y.device) if lv["gb"] is not None else None
+                st["heads"][s] = dict(gb=lv["gb"], w=head.weight._hr_store, dzl=dzl, cout=head.out_channels,
+                                      dw=head.weight._hr_gstore, dbias=head.bias._hr_gstore, dgb=dgb)
+                ops.head_bn_bwd_reduce(root.y, root.coef, st["nseg"], st["partial"], st["nchunks"], st["heads"], seg0=s,
+                                       nsegs=1, dy_absmax=st["gmax"])
+        bn = self._head_bn_layer()
+        ops.bn_bwd_finalize(root.y, root.coef, st["nseg"], st["partial"], st["nchunks"], bn.weight._hr_gstore,
+                            bn.bias._hr_gstore)
+        st["dy"] = ops.head_bn_bwd_apply(root.y, root.coef, st["nseg"], st["partial"], st["nchunks"], st["heads"],
+                                         dy_absmax=st["gmax"])
+        st["heads"] = None
+        return True
 
     def _head_backward(self, lv, dz):
         """dz (NCHW, full res) -> gradients of head / FiLM; seeds feats.grad; returns the
@@ -425,7 +477,17 @@ class _EngineModel(nn.Module):
             dzl = ops.nchw_to_nhwc(dz)
         dgb = ops.zeros(lv["gb"].shape, torch.float32, lv["gb"].device) if film is not None else None
         stacked = lv.get("stacked")
-        if stacked is not None:          # batched passes: this level's rows of the stacked feature gradient
+        if stacked is not None and getattr(stacked, "deferred", False) and stacked.grad is None:
+            # first pass of the fused backward for this level's segment: dW / dbias / dgb as head_bwd, and the BatchNorm
+            # partial sums of the feature gradient that is never stored.  One launch per level: level L-1's logit gradient
+            # depends on this level's dgb (FiLM), so the levels cannot share a launch.
+            st = self._head_bn_state(stacked, len(self.levels))
+            seg = feats.slot
+            st["heads"][seg] = dict(gb=lv["gb"], w=head.weight._hr_store, dzl=dzl, cout=head.out_channels,
+                                    dw=head.weight._hr_gstore, dbias=head.bias._hr_gstore, dgb=dgb)
+            ops.head_bn_bwd_reduce(stacked.y, stacked.coef, st["nseg"], st["partial"], st["nchunks"], st["heads"], seg0=seg,
+                                   nsegs=1, dy_absmax=st["gmax"])
+        elif stacked is not None:          # batched passes: this level's rows of the stacked feature gradient
             if stacked.grad is None:
                 stacked.grad = ops.zeros(stacked.data.shape, torch.float32, stacked.data.device)
             Bn = feats.data.shape[0]
@@ -857,7 +919,11 @@ class HighResolutionNet(_EngineModel):
                 ys = mod.run(rec, ys)
         rec.mark("shared_head")
         cat = rec.upsample_concat(ys, self.align_corners)
-        return rec.conv_bn(cat, self.shared_head[0], self.shared_head[1], relu=True)
+        # the level heads are this tensor's only readers: where the recorder allows it they take it un-normalised (defer)
+        return rec.conv_bn(cat, self.shared_head[0], self.shared_head[1], relu=True, defer=True)
+
+    def _head_bn_layer(self):
+        return self.shared_head[1]
 
     def forward(self, x):
         return self._forward_impl(x)

@@ -54,6 +54,13 @@ class BnBwd(C.Structure):
                 ("dres_accumulate", _i), ("npix", _l), ("C", _i), ("partial", _p), ("nchunks", _i), ("dy_absmax", _p), ("nseg", _i), ("relu_mask", _p), ("sum_ranks", _i)]
 
 
+class HeadBn(C.Structure):
+    """hrseg_head_bn_t"""
+    _fields_ = [("y", _p), ("ldy", _i), ("coef", _p), ("F", _i), ("nseg", _i), ("B", _i), ("hw", _l), ("partial", _p),
+                ("nchunks", _i), ("dy_absmax", _p), ("dy", _p), ("lddy", _i), ("gb", _p * 8), ("w", _p * 8), ("dzl", _p * 8),
+                ("lddzl", _i * 8), ("Cout", _i * 8), ("dw", _p * 8), ("dbias", _p * 8), ("dgb", _p * 8)]
+
+
 class DecodeTree(C.Structure):
     """hrseg_decode_tree_t"""
     _fields_ = [("first_child", (_i * 16) * 8), ("n_children", (_i * 16) * 8), ("pixel_val", (_i * 16) * 8), ("root_softmax", _i)]
@@ -97,6 +104,9 @@ PROTOTYPES = {
     "hrseg_film_linear_bwd": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _p],
     "hrseg_head_fwd": [_p, _i, _p, _p, _p, _p, _i, _i, _l, _i, _i, _p],
     "hrseg_head_bwd": [_p, _i, _p, _p, _p, _i, _p, _i, _i, _p, _p, _p, _i, _l, _i, _i, _p],
+    "hrseg_head_bn_fwd": [_p, _i, _p, _p, _p, _p, _p, _i, _i, _l, _i, _i, _p],
+    "hrseg_head_bn_bwd_reduce": [C.POINTER(HeadBn), _i, _i, _p],
+    "hrseg_head_bn_bwd_apply": [C.POINTER(HeadBn), _p],
     "hrseg_logits_up_fwd": [_p, _i, _i, _i, _i, _i, _p, _i, _i, _i, _p],
     "hrseg_logits_up_bwd": [_p, _i, _i, _i, _i, _p, _i, _i, _i, _i, _p],
     "hrseg_sigmoid_fwd": [_p, _p, _l, _p],

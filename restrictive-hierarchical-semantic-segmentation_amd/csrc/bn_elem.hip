@@ -33,14 +33,6 @@ static int elem_grid(long npix, int C) {
   for (long pix = (long)blockIdx.x * (L).P + (L).pl; pix < (npix); pix += (long)gridDim.x * (L).P)
 
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-// y*scale + shift with ONE rounding per element: the forward pass and the backward pass's recomputed
-// ReLU mask must evaluate the identical expression
-__device__ __forceinline__ f32x4 bn_affine(f32x4 y, f32x4 sc, f32x4 sh) {
-  f32x4 v;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) v[j] = __builtin_fmaf(y[j], sc[j], sh[j]);
-  return v;
-}
 __device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 
 // C > 1024 is not supported by the quad mapping (Q must be <= 256): the widest
@@ -963,6 +955,233 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_group_kernel(BnBwdG g, int e
   }
 }
 
+// =========================================================================== level heads fused into the BatchNorm backward
+// The layer in front of the level heads (HRNet shared head: conv -> BatchNorm -> ReLU, no residual, the heads its only readers):
+// its normalised output f and the heads' feature gradient g are functions of y and of at most 8 logit-gradient values per pixel,
+// so the backward runs as two passes over y (hrseg.h, hrseg_head_bn_t) instead of fill + head_bwd + reduce + apply over f / g.
+//
+// First pass = head_bwd_kernel's accumulations + stats_body's backward sums, on stats_body's chunks and in its per-thread pixel
+// order (thread (cq, pl) walks lo + pl, lo + pl + P, ...; four pixels per trip), so the BatchNorm partials are the ones
+// bn_bwd_reduce_group_kernel computes from the stored g.  A chunk may cross a sample boundary inside its segment: the FiLM pair
+// and the dgb accumulators are per sample, so a thread flushes them (atomics) when its pixel sequence enters the next sample.
+template <int CO>
+__global__ __launch_bounds__(256) void head_bn_bwd_reduce_kernel(hrseg_head_bn_t a, int chunk0) {
+  __shared__ double red[256 * 8];
+  const int C = a.F;
+  const Lanes L = make_lanes(C);
+  const int chunk = chunk0 + blockIdx.x;
+  const int cps = a.nchunks / a.nseg, seg = chunk / cps;
+  const long hw = a.hw, seg_pix = (long)a.B * hw;
+  const long per = (seg_pix + cps - 1) / cps;
+  const long seg_base = seg * seg_pix;
+  const long lo = seg_base + (long)(chunk - seg * cps) * per;
+  const long seg_end = seg_base + seg_pix;
+  const long hi = (lo + per < seg_end) ? lo + per : seg_end;
+  // the |dy| slots the apply pass raises with atomicMax start from zero (as bn_bwd_reduce_group_kernel)
+  if (blockIdx.x == 0 && threadIdx.x < 64 && a.dy_absmax) a.dy_absmax[threadIdx.x] = 0.f;
+  const float* __restrict__ gb = a.gb[seg];
+  const float* __restrict__ w = a.w[seg];
+  const float* __restrict__ dzl = a.dzl[seg];
+  const int lddz = a.lddzl[seg], Cout = a.Cout[seg];
+  float* dgb = a.dgb[seg];
+  f32x4 s = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
+  f32x4 a_dw[CO], a_dg = {0.f, 0.f, 0.f, 0.f}, a_db = {0.f, 0.f, 0.f, 0.f};
+  float a_bias[CO];
+#pragma unroll
+  for (int c = 0; c < CO; ++c) {
+    a_dw[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    a_bias[c] = 0.f;
+  }
+  if (L.active && lo + L.pl < hi) {
+    const f32x4 mean = ld4(a.coef + 4 * L.cq), rstd = ld4(a.coef + C + 4 * L.cq);
+    const f32x4 sc = ld4(a.coef + 2 * C + 4 * L.cq), sh = ld4(a.coef + 3 * C + 4 * L.cq);
+    f32x4 wq[CO];
+#pragma unroll
+    for (int c = 0; c < CO; ++c) wq[c] = (c < Cout) ? ld4(w + c * C + 4 * L.cq) : f32x4{0.f, 0.f, 0.f, 0.f};
+    long b = (lo + L.pl - seg_base) / hw;           // sample of the thread's current pixel, bnd = first pixel of the next one
+    long bnd = seg_base + (b + 1) * hw;
+    f32x4 gam = {1.f, 1.f, 1.f, 1.f}, bet = {0.f, 0.f, 0.f, 0.f};
+    if (gb) {
+      gam = ld4(gb + (size_t)b * 2 * C + 4 * L.cq);
+      bet = ld4(gb + (size_t)b * 2 * C + C + 4 * L.cq);
+    }
+    auto flush_dgb = [&]() {
+      if (dgb) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          atomicAdd(dgb + (size_t)b * 2 * C + 4 * L.cq + j, a_dg[j]);
+          atomicAdd(dgb + (size_t)b * 2 * C + C + 4 * L.cq + j, a_db[j]);
+        }
+      }
+    };
+    // pixels per trip, all loads issued before the first use.  The launch has one block per chunk (a wave per SIMD at 256 chunks),
+    // and unlike stats_body only ONE 16-byte stream per pixel: eight pixels in flight where the registers allow it (the per-thread
+    // order of the additions does not depend on U)
+    constexpr int U = CO <= 4 ? 8 : 4;
+    for (long pix0 = lo + L.pl; pix0 < hi; pix0 += (long)U * L.P) {
+      f32x4 yv[U];
+      float g[U][CO];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const long pix = pix0 + (long)u * L.P;
+        const bool ok = pix < hi;
+        yv[u] = ok ? ld4(a.y + pix * a.ldy + 4 * L.cq) : mean;
+#pragma unroll
+        for (int c = 0; c < CO; ++c) g[u][c] = (ok && c < Cout) ? dzl[(pix - seg_base) * lddz + c] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const long pix = pix0 + (long)u * L.P;
+        if (pix >= hi) break;
+        while (pix >= bnd) {                        // the sequence entered the next sample: its FiLM pair, its dgb rows
+          flush_dgb();
+          a_dg = f32x4{0.f, 0.f, 0.f, 0.f};
+          a_db = f32x4{0.f, 0.f, 0.f, 0.f};
+          ++b;
+          bnd += hw;
+          if (gb) {
+            gam = ld4(gb + (size_t)b * 2 * C + 4 * L.cq);
+            bet = ld4(gb + (size_t)b * 2 * C + C + 4 * L.cq);
+          }
+        }
+        const f32x4 zc = bn_affine(yv[u], sc, sh);
+        f32x4 fv;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) fv[j] = fmaxf(zc[j], 0.f);
+        // head_bwd_kernel's `one`, with f recomputed
+        const f32x4 fm = fv * gam + bet;
+        f32x4 uu = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < CO; ++c) {
+          uu += wq[c] * g[u][c];
+          a_dw[c] += fm * g[u][c];
+          if (L.cq == 0) a_bias[c] += g[u][c];
+        }
+        a_dg += fv * uu;
+        a_db += uu;
+        // stats_body's backward sums of the gradient head_bwd_kernel would have stored (gam * u), masked by the ReLU
+        f32x4 gv = gam * uu;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) gv[j] = zc[j] > 0.f ? gv[j] : 0.f;
+        const f32x4 xh = (yv[u] - mean) * rstd;
+        s += gv;
+        s2 += gv * xh;
+      }
+    }
+    flush_dgb();
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    red[threadIdx.x * 8 + j] = s[j];
+    red[threadIdx.x * 8 + 4 + j] = s2[j];
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < C; c += 256) {
+    double sa = 0.0, sb = 0.0;
+    for (int pl = 0; pl < L.P; ++pl) {
+      const int t = pl * L.Q + (c >> 2);
+      sa += red[t * 8 + (c & 3)];
+      sb += red[t * 8 + 4 + (c & 3)];
+    }
+    a.partial[((size_t)chunk * 2 + 0) * C + c] = sa;
+    a.partial[((size_t)chunk * 2 + 1) * C + c] = sb;
+  }
+  // dW / dbias: reduce over the pixel lanes of the block, then one atomic per (channel, output) -- as head_bwd_kernel
+  float* fred = reinterpret_cast<float*>(red);
+  float* dw = a.dw[seg];
+  float* dbias = a.dbias[seg];
+  auto reduce_add = [&](float v, float* dst) {
+    __syncthreads();
+    fred[threadIdx.x] = v;
+    __syncthreads();
+    if (L.active && L.pl == 0) {
+      float t = 0.f;
+      for (int q = 0; q < L.P; ++q) t += fred[q * L.Q + L.cq];
+      atomicAdd(dst, t);
+    }
+  };
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int c = 0; c < CO; ++c)
+      if (c < Cout) reduce_add(a_dw[c][j], dw + c * C + 4 * (L.active ? L.cq : 0) + j);
+  if (dbias) {
+#pragma unroll
+    for (int c = 0; c < CO; ++c)
+      if (c < Cout) {
+        __syncthreads();
+        fred[threadIdx.x] = (L.active && L.cq == 0) ? a_bias[c] : 0.f;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+          float t = 0.f;
+          for (int q = 0; q < L.P; ++q) t += fred[q * L.Q];
+          atomicAdd(dbias + c, t);
+        }
+      }
+  }
+}
+
+// Second pass: bn_bwd_apply_group_kernel with g recomputed from y and the logit gradient instead of read from memory.
+template <int CO>
+__global__ __launch_bounds__(256) void head_bn_bwd_apply_kernel(hrseg_head_bn_t a) {
+  const int C = a.F;
+  const Lanes L = make_lanes(C);
+  float amax = 0.f;
+  if (L.active) {                 // (no early return: every lane takes part in the max reduction below)
+    const double* totals = a.partial + (size_t)a.nchunks * 2 * C;
+    const f32x4 mean = ld4(a.coef + 4 * L.cq), rstd = ld4(a.coef + C + 4 * L.cq), scale = ld4(a.coef + 2 * C + 4 * L.cq);
+    const f32x4 shift = ld4(a.coef + 3 * C + 4 * L.cq);
+    const long hw = a.hw, seg_pix = (long)a.B * hw;
+    const float inv = (float)(1.0 / (double)seg_pix);
+    for (int seg = 0; seg < a.nseg; ++seg) {
+      f32x4 mg, mgx;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        mg[j] = (float)(totals[(size_t)seg * 2 * C + 4 * L.cq + j]) * inv;
+        mgx[j] = (float)(totals[(size_t)seg * 2 * C + C + 4 * L.cq + j]) * inv;
+      }
+      const float* __restrict__ gb = a.gb[seg];
+      const float* __restrict__ w = a.w[seg];
+      const float* __restrict__ dzl = a.dzl[seg];
+      const int lddz = a.lddzl[seg], Cout = a.Cout[seg];
+      f32x4 wq[CO];
+#pragma unroll
+      for (int c = 0; c < CO; ++c) wq[c] = (c < Cout) ? ld4(w + c * C + 4 * L.cq) : f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int b = 0; b < a.B; ++b) {
+        const f32x4 gam = gb ? ld4(gb + (size_t)b * 2 * C + 4 * L.cq) : f32x4{1.f, 1.f, 1.f, 1.f};
+        const long r0 = (long)b * hw, r1 = r0 + hw;           // rows of this sample inside its segment
+        for (long r = r0 + (long)blockIdx.x * L.P + L.pl; r < r1; r += (long)gridDim.x * L.P) {
+          const long pix = seg * seg_pix + r;
+          const f32x4 yv = ld4(a.y + pix * a.ldy + 4 * L.cq);
+          f32x4 uu = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int c = 0; c < CO; ++c) uu += wq[c] * ((c < Cout) ? dzl[r * lddz + c] : 0.f);
+          f32x4 gg = gam * uu;
+          const f32x4 zz = bn_affine(yv, scale, shift);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) gg[j] = zz[j] > 0.f ? gg[j] : 0.f;
+          const f32x4 xh = (yv - mean) * rstd;
+          const f32x4 dyv = scale * (gg - mg - xh * mgx);
+          st4(a.dy + pix * a.lddy + 4 * L.cq, dyv);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) amax = fmaxf(amax, fabsf(dyv[j]));
+        }
+      }
+    }
+  }
+  if (a.dy_absmax) {
+    __shared__ float wmax[4];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = amax;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const float m = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+      if (m > 0.f) atomicMax(reinterpret_cast<unsigned*>(a.dy_absmax) + (blockIdx.x & 63), __float_as_uint(m));
+    }
+  }
+}
+
 // =========================================================================== C ABI
 static long chunk_size(long npix, int nchunks) { return (npix + nchunks - 1) / nchunks; }
 
@@ -1332,5 +1551,50 @@ extern "C" int hrseg_bn_bwd_group_phases(int n, const hrseg_bn_bwd_t* probs, int
     hipLaunchKernelGGL(bn_bwd_apply_group_kernel, dim3(end), dim3(256), 0, st, g, eval_mode);
     HRSEG_LAUNCH_CHECK("bn_bwd_apply_group");
   }
+  return 0;
+}
+
+static int check_head_bn(const hrseg_head_bn_t* p, const char* who, int seg0, int nsegs) {
+  HRSEG_CHECK_ARG(p, "%s: NULL problem", who);
+  if (int e = check_c(p->F, who)) return e;
+  HRSEG_CHECK_ARG(p->y && p->coef && p->partial && p->B > 0 && p->hw > 0 && p->nseg >= 1 && p->nseg <= HRSEG_HEAD_BN_MAX_SEG &&
+                      p->nchunks > 0 && p->nchunks % p->nseg == 0 && p->ldy >= p->F && p->ldy % 4 == 0,
+                  "%s: bad arguments (F=%d nseg=%d nchunks=%d ldy=%d)", who, p->F, p->nseg, p->nchunks, p->ldy);
+  HRSEG_CHECK_ARG(seg0 >= 0 && nsegs >= 1 && seg0 + nsegs <= p->nseg, "%s: segments [%d, %d) of %d", who, seg0, seg0 + nsegs, p->nseg);
+  for (int s = seg0; s < seg0 + nsegs; ++s) {
+    HRSEG_CHECK_ARG(p->w[s] && p->dzl[s] && p->Cout[s] > 0 && p->Cout[s] <= 8 && p->lddzl[s] >= p->Cout[s],
+                    "%s: segment %d: bad head (Cout=%d lddzl=%d)", who, s, p->Cout[s], p->lddzl[s]);
+  }
+  return 0;
+}
+
+extern "C" int hrseg_head_bn_bwd_reduce(const hrseg_head_bn_t* p, int seg0, int nsegs, hrseg_stream_t stream) {
+  if (int e = check_head_bn(p, "hrseg_head_bn_bwd_reduce", seg0, nsegs)) return e;
+  if (hrseg_g_deterministic) {
+    hrseg_set_error("hrseg_head_bn_bwd_reduce: not offered in deterministic mode (atomic sums); use hrseg_head_bwd + hrseg_bn_bwd_group");
+    return HRSEG_ERR_UNSUPPORTED;
+  }
+  int comax = 0;
+  for (int s = seg0; s < seg0 + nsegs; ++s) {
+    HRSEG_CHECK_ARG(p->dw[s] && (p->gb[s] == nullptr) == (p->dgb[s] == nullptr), "hrseg_head_bn_bwd_reduce: segment %d: dw is required, dgb goes with gb", s);
+    comax = p->Cout[s] > comax ? p->Cout[s] : comax;
+  }
+  const int cps = p->nchunks / p->nseg;
+  if (comax <= 4) hipLaunchKernelGGL(head_bn_bwd_reduce_kernel<4>, dim3(nsegs * cps), dim3(256), 0, (hipStream_t)stream, *p, seg0 * cps);
+  else hipLaunchKernelGGL(head_bn_bwd_reduce_kernel<8>, dim3(nsegs * cps), dim3(256), 0, (hipStream_t)stream, *p, seg0 * cps);
+  HRSEG_LAUNCH_CHECK("head_bn_bwd_reduce");
+  return 0;
+}
+
+extern "C" int hrseg_head_bn_bwd_apply(const hrseg_head_bn_t* p, hrseg_stream_t stream) {
+  if (int e = check_head_bn(p, "hrseg_head_bn_bwd_apply", 0, p ? p->nseg : 1)) return e;
+  HRSEG_CHECK_ARG(p->dy && p->lddy >= p->F && p->lddy % 4 == 0, "hrseg_head_bn_bwd_apply: bad dy (lddy=%d)", p->lddy);
+  int comax = 0;
+  for (int s = 0; s < p->nseg; ++s) comax = p->Cout[s] > comax ? p->Cout[s] : comax;
+  const long npix = (long)p->nseg * p->B * p->hw;
+  const int grid = elem_grid(npix, p->F);
+  if (comax <= 4) hipLaunchKernelGGL(head_bn_bwd_apply_kernel<4>, dim3(grid), dim3(256), 0, (hipStream_t)stream, *p);
+  else hipLaunchKernelGGL(head_bn_bwd_apply_kernel<8>, dim3(grid), dim3(256), 0, (hipStream_t)stream, *p);
+  HRSEG_LAUNCH_CHECK("head_bn_bwd_apply");
   return 0;
 }

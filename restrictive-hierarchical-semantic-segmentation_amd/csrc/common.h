@@ -55,3 +55,12 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+
+// BatchNorm's y*scale + shift with ONE rounding per element: the forward pass, the backward pass's recomputed ReLU mask and
+// the level heads that read the un-normalised tensor (hrseg_head_bn_*) must evaluate the identical expression
+__device__ __forceinline__ f32x4 bn_affine(f32x4 y, f32x4 sc, f32x4 sh) {
+  f32x4 v;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) v[j] = __builtin_fmaf(y[j], sc[j], sh[j]);
+  return v;
+}

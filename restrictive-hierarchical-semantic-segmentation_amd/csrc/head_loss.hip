@@ -96,8 +96,12 @@ __global__ void film_linear_bwd_kernel(const float* cond, const float* wl, const
 // --------------------------------------------------------------------------- head forward
 // z[pix][c] = sum_k W[c][k] (f[pix][k] g[b][k] + be[b][k]) + bias[c].  Effective per-sample
 // weights W*g and bias + W.be are built in LDS; LP lanes share one pixel row.
-template <int LP, int CO>
+// BN: `f` is the un-normalised output y of the convolution in front of the BatchNorm + ReLU whose result the head reads, and
+// `coef` that BatchNorm's [mean, rstd, scale, shift][F]: a feature is max(bn_affine(y, scale, shift), 0) on load -- the value
+// bn_apply_group_kernel would have stored, so the logits are the same bits without the normalised tensor ever being written.
+template <int LP, int CO, bool BN>
 __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__ f, int ldf,
+                                                       const float* __restrict__ coef,
                                                        const float* __restrict__ gb, const float* __restrict__ w,
                                                        const float* __restrict__ bias, float* __restrict__ z, int ldz,
                                                        long hw, int F, int Cout) {
@@ -146,6 +150,15 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__
         const int q = sub + j * LP;
         wr[j][c] = (q < Q) ? *reinterpret_cast<const f32x4*>(weff + c * F + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
       }
+    f32x4 bsc[3], bsh[3];       // BN: scale / shift of the lane's channel groups (zero beyond Q: max(fma(0, 0, 0), 0) = 0)
+    if (BN) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        const int q = sub + j * LP;
+        bsc[j] = (q < Q) ? *reinterpret_cast<const f32x4*>(coef + 2 * F + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
+        bsh[j] = (q < Q) ? *reinterpret_cast<const f32x4*>(coef + 3 * F + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    }
     for (long pix = (long)blockIdx.x * PPB + pg; pix < hw; pix += (long)gridDim.x * PPB) {
       const float* row = f + ((size_t)b * hw + pix) * ldf;
       f32x4 v[3];
@@ -153,6 +166,14 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__
       for (int j = 0; j < 3; ++j) {
         const int q = sub + j * LP;
         v[j] = (q < Q) ? *reinterpret_cast<const f32x4*>(row + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+      if (BN) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+          v[j] = bn_affine(v[j], bsc[j], bsh[j]);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[j][e] = fmaxf(v[j][e], 0.f);
+        }
       }
       float acc[CO];
 #pragma unroll
@@ -180,7 +201,12 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__
 #pragma unroll
     for (int c = 0; c < CO; ++c) acc[c] = 0.f;
     for (int q = sub; q < Q; q += LP) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(row + 4 * q);
+      f32x4 v = *reinterpret_cast<const f32x4*>(row + 4 * q);
+      if (BN) {
+        v = bn_affine(v, *reinterpret_cast<const f32x4*>(coef + 2 * F + 4 * q), *reinterpret_cast<const f32x4*>(coef + 3 * F + 4 * q));
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+      }
 #pragma unroll
       for (int c = 0; c < CO; ++c) {
         const f32x4 ww = *reinterpret_cast<const f32x4*>(weff + c * F + 4 * q);
@@ -878,11 +904,11 @@ extern "C" int hrseg_film_linear_bwd(const float* cond, const float* wl, const f
   return 0;
 }
 
-extern "C" int hrseg_head_fwd(const float* f, int ldf, const float* gb, const float* w, const float* bias, float* z,
-                              int ldz, int B, long hw, int F, int Cout, hrseg_stream_t stream) {
+static int head_fwd_launch(const char* who, const float* f, int ldf, const float* coef, const float* gb, const float* w,
+                           const float* bias, float* z, int ldz, int B, long hw, int F, int Cout, hrseg_stream_t stream) {
   HRSEG_CHECK_ARG(f && w && z && B > 0 && hw > 0 && F > 0 && F % 4 == 0 && Cout > 0 && Cout <= 8 && ldf >= F &&
                       ldf % 4 == 0 && ldz >= Cout,
-                  "hrseg_head_fwd: bad arguments (F=%d Cout=%d)", F, Cout);
+                  "%s: bad arguments (F=%d Cout=%d)", who, F, Cout);
   hipStream_t st = (hipStream_t)stream;
   const int co = Cout <= 4 ? 4 : 8;
   const size_t smem = (size_t)(co * F + co) * sizeof(float);
@@ -891,14 +917,31 @@ extern "C" int hrseg_head_fwd(const float* f, int ldf, const float* gb, const fl
   const long cap = (2048 + B - 1) / B < 64 ? 64 : (2048 + B - 1) / B;      // ~2048 blocks in all: the per-block set-up is paid once per CU slot
   if (blocks > cap) blocks = cap;
   dim3 grid((int)blocks, B);
-#define HF(LP_, CO_) hipLaunchKernelGGL((head_fwd_kernel<LP_, CO_>), grid, dim3(256), smem, st, f, ldf, gb, w, bias, z, ldz, hw, F, Cout)
+#define HF(LP_, CO_)                                                                                                              \
+  do {                                                                                                                            \
+    if (coef) hipLaunchKernelGGL((head_fwd_kernel<LP_, CO_, true>), grid, dim3(256), smem, st, f, ldf, coef, gb, w, bias, z, ldz, \
+                                 hw, F, Cout);                                                                                    \
+    else hipLaunchKernelGGL((head_fwd_kernel<LP_, CO_, false>), grid, dim3(256), smem, st, f, ldf, coef, gb, w, bias, z, ldz, hw, \
+                            F, Cout);                                                                                             \
+  } while (0)
   if (lp == 16 && co == 4) HF(16, 4);
   else if (lp == 16) HF(16, 8);
   else if (co == 4) HF(64, 4);
   else HF(64, 8);
 #undef HF
-  HRSEG_LAUNCH_CHECK("head_fwd");
+  HRSEG_LAUNCH_CHECK(who);
   return 0;
+}
+
+extern "C" int hrseg_head_fwd(const float* f, int ldf, const float* gb, const float* w, const float* bias, float* z,
+                              int ldz, int B, long hw, int F, int Cout, hrseg_stream_t stream) {
+  return head_fwd_launch("hrseg_head_fwd", f, ldf, nullptr, gb, w, bias, z, ldz, B, hw, F, Cout, stream);
+}
+
+extern "C" int hrseg_head_bn_fwd(const float* y, int ldy, const float* coef, const float* gb, const float* w, const float* bias,
+                                 float* z, int ldz, int B, long hw, int F, int Cout, hrseg_stream_t stream) {
+  HRSEG_CHECK_ARG(coef, "hrseg_head_bn_fwd: coef is required (hrseg_head_fwd reads a normalised tensor)");
+  return head_fwd_launch("hrseg_head_bn_fwd", y, ldy, coef, gb, w, bias, z, ldz, B, hw, F, Cout, stream);
 }
 
 extern "C" int hrseg_head_bwd(const float* f, int ldf, const float* gb, const float* w, const float* dz, int lddz,

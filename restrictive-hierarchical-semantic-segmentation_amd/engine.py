@@ -73,6 +73,40 @@ class Act:
         return self.data.shape
 
 
+class DeferredAct(Act):
+    """Output of a conv + BatchNorm + ReLU layer (no residual) whose apply phase has not run: it carries the convolution output
+    `y` and the BatchNorm's `coef`.  The level heads read those directly (ops.head_bn_fwd) and their backward hands the layer its
+    `dy` (Models/models.py, _head_bn_*), so the normalised tensor and its gradient never exist.  Anyone else who asks for
+    `.data` gets the materialised tensor -- the apply phase on the same coefficients, once -- and the layer is an ordinary one
+    from then on (`deferred` False).  `rows`: a view of rows [lo, hi) of `parent` (one level pass of the stacked batch)."""
+    __slots__ = ("y", "coef", "_z", "_apply", "parent", "rows", "fused")
+
+    def __init__(self, y, coef, apply=None, parent=None, rows=None):
+        self.y, self.coef, self._z, self._apply = y, coef, None, apply
+        self.parent, self.rows = parent, rows
+        self.grad, self.needs_grad, self.split = None, True, False
+        self.fused = None            # the fused backward's state: dict(dy, gmax, ...) once the heads ran it
+
+    @property
+    def shape(self):                 # (Act.shape reads .data: asking for the shape must not materialise the tensor)
+        return self.y.shape
+
+    @property
+    def deferred(self):
+        return (self.parent._z if self.parent is not None else self._z) is None
+
+    @property
+    def data(self):
+        if self.parent is not None:
+            return self.parent.data[self.rows[0]:self.rows[1]]
+        if self._z is None:
+            self._z = self._apply()
+        return self._z
+
+    def slice(self, lo, hi):
+        return DeferredAct(self.y[lo:hi], self.coef, parent=self, rows=(lo, hi))
+
+
 class FlatParams:
     """All parameters of a module as views of one flat fp32 buffer (+ a flat gradient).
 
@@ -188,7 +222,11 @@ class FlatParams:
 class Recorder:
     """Forward launcher + tape of backward closures for ONE model forward."""
 
-    def __init__(self, training, record, flat=None, bn_repeat=1, bn_segments=1, prec=0, sync=None, fold=None, wpersist=False):
+    def __init__(self, training, record, flat=None, bn_repeat=1, bn_segments=1, prec=0, sync=None, fold=None, wpersist=False,
+                 defer_head=False):
+        # the caller's promise that the level heads are the only readers of a conv_bn(..., defer=True) output and can take it
+        # un-normalised; deterministic mode and synchronised BatchNorm keep the separate launches
+        self.defer_head = bool(defer_head) and training and record and sync is None and not _lib.deterministic() and not _EXPERIMENT
         self.wpersist = bool(wpersist) and flat is not None      # weights of the flat buffers have cached images (hrseg.h w_persistent)
         self.fold = fold                 # inference: (conv, bn) -> (folded weight, folded bias), or None = BN as its own launches
         self.sync = sync                 # process group for cross-rank BatchNorm statistics (opt-in sync_bn), else None
@@ -240,11 +278,11 @@ class Recorder:
         act.grad = g
 
     # ------------------------------------------------------------------ conv + BN (+residual) (+ReLU)
-    def conv_bn(self, x, conv, bn, relu, residual=None, out=None, split_for=None):
+    def conv_bn(self, x, conv, bn, relu, residual=None, out=None, split_for=None, defer=False):
         return self.conv_bn_group([(x, conv, bn, residual)], relu, outs=[out],
-                                  split_for=[split_for] if split_for is not None else None)[0]
+                                  split_for=[split_for] if split_for is not None else None, defer=defer)[0]
 
-    def conv_bn_group(self, items, relu, outs=None, single_reader=False, split_for=None, split_level=1):
+    def conv_bn_group(self, items, relu, outs=None, single_reader=False, split_for=None, split_level=1, defer=False):
         """... split_for: one convolution per item that is the ONLY reader of that item's output (conv1 -> conv2 of a block).
         Where the library will run those readers on the kernels that take a pre-split pixel operand (hrseg_conv_x_split_ok:
         wave-specialised forward + nine-tap weight gradient, fp16x2 arithmetic) the BatchNorm apply writes the output
@@ -318,7 +356,17 @@ class Recorder:
                          out=outs[i] if outs is not None else None, z_split=z_split,
                          partial=stats[i] if stats is not None else None)
                     for i, ((x, conv, bn, res), y) in enumerate(zip(items, ys))]
-        if _EXPERIMENT and self.training and self.sync is None:
+        defer = (defer and self.defer_head and n == 1 and relus[0] and items[0][3] is None and not z_split
+                 and (outs is None or outs[0] is None) and not _lib.deterministic())
+        if defer:
+            # statistics + finalize only; the apply phase runs on demand (DeferredAct.data).  `out` = y satisfies the library's
+            # argument check, nothing is written there
+            coef0 = ops.bn_fwd_group([dict(bn_items[0], out=ys[0])], True, phases=2 if stats is not None else 3)[0][1]
+
+            def apply_now(item=bn_items[0]):
+                return ops.bn_fwd_group([dict(item, coef=coef0, partial=None)], True, phases=4)[0][0]
+            zc = None
+        elif _EXPERIMENT and self.training and self.sync is None:
             phases = 7
             if "skip_apply1" in _EXPERIMENT and single_reader:
                 phases &= ~4
@@ -329,15 +377,19 @@ class Recorder:
                 zc = [(y, c) for y, (_, c) in zip(ys, zc)]
         else:
             zc = ops.bn_fwd_group(bn_items, self.training, sync=self.sync, phases=6 if stats is not None else 7)
-        zs = [Act(z, split=z_split) for z, _ in zc]
-        if not self.record:
-            return zs
-        coefs = [c for _, c in zc]
+        if defer:
+            zs, coefs = [DeferredAct(ys[0], coef0, apply=apply_now)], [coef0]
+        else:
+            zs = [Act(z, split=z_split) for z, _ in zc]
+            if not self.record:
+                return zs
+            coefs = [c for _, c in zc]
         eval_mode = not self.training
 
         want_gmax = self.prec in (_lib.CONV_PRECISION["fp16x2"], _lib.CONV_PRECISION["auto"])
 
-        def bwd():
+        def bn_backward():
+            """-> (dys, gmax_all, gmaxs): the BatchNorm backward of the group (three launches)"""
             bw = []
             # fp16x2: the BN backward records max|dy| per problem; the data / weight gradients scale dy by it
             gmax_all = torch.empty((n, 64), dtype=torch.float32, device=ys[0].device) if want_gmax else None    # reset by bn_bwd
@@ -358,7 +410,16 @@ class Recorder:
                                dgamma=bn.weight._hr_gstore,
                                dbeta=bn.bias._hr_gstore, dres=dres, dres_accumulate=dres_acc, nseg=self.bn_segments,
                                dy_absmax=gmaxs[i]))
-            dys = ops.bn_bwd_group(bw, eval_mode, sync=self.sync)
+            return ops.bn_bwd_group(bw, eval_mode, sync=self.sync), gmax_all, gmaxs
+
+        def bwd():
+            fused = zs[0].fused if defer else None
+            if fused is not None:        # the level heads ran this layer's BatchNorm backward with their own: dy is there
+                zs[0].fused = None
+                dys, gmax_all = [fused["dy"]], fused["gmax"]
+                gmaxs = [gmax_all[0] if gmax_all is not None else None]
+            else:
+                dys, gmax_all, gmaxs = bn_backward()
             # the weight gradient is issued on the side stream BEFORE the data gradient of the same layer (issuing it behind,
             # so that it would run beside the next BatchNorm backward, measured 55.9 vs 53.8 ms per step)
             def weight_gradients():

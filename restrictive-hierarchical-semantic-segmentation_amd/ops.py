@@ -350,7 +350,9 @@ def bn_fwd_group(items, training, sync=None, phases=7):
         z = it.get("out")
         if z is None:
             z = torch.empty(y.shape, dtype=torch.float32, device=y.device)
-        coef = torch.empty(4 * Cn, dtype=torch.float32, device=y.device)
+        coef = it.get("coef")                       # given: the apply phase alone, on coefficients an earlier call finalized
+        if coef is None:
+            coef = torch.empty(4 * Cn, dtype=torch.float32, device=y.device)
         res = it.get("residual")
         a.y, a.ldy, a.npix, a.C = ptr(y), _ld(y), npix, Cn
         a.gamma, a.beta = ptr(it["gamma"]), ptr(it["beta"])
@@ -819,6 +821,73 @@ def head_bwd(f, gb, w, dz, dw, dbias, dgb, want_df=True, df=None, df_accumulate=
     call("hrseg_head_bwd", ptr(f), _ld(f), ptr(gb), ptr(w), ptr(dz), _ld(dz), ptr(df), _ld(df) if df is not None else 0,
          int(df_accumulate), ptr(dw), ptr(dbias), ptr(dgb), B, H * W, F, Cout)
     return df
+
+
+def head_bn_fwd(y, coef, gb, w, bias, cout=None):
+    """head_fwd on the un-normalised conv output y of the BatchNorm + ReLU layer in front of the heads (coef: that BatchNorm's
+    [4][F]); the same logits as bn_fwd_group's apply phase + head_fwd, without the normalised tensor (hrseg_head_bn_fwd)"""
+    B, H, W, F = y.shape
+    Cout = cout if cout is not None else w.shape[0]
+    z = empty_nhwc(B, H, W, Cout, y)
+    call("hrseg_head_bn_fwd", ptr(y), _ld(y), ptr(coef), ptr(gb), ptr(w), ptr(bias), ptr(z), Cout, B, H * W, F, Cout)
+    return z
+
+
+def head_bn_chunks(npix, F, nseg):
+    """pixel chunks of the fused head + BatchNorm backward: bn_bwd_group's, so that the partial sums are the same ones"""
+    nch = _nchunks(npix, F)
+    return max(nseg, nch // nseg * nseg) if nseg > 1 else nch
+
+
+def _head_bn_struct(y, coef, nseg, partial, nchunks, heads, dy=None, dy_absmax=None):
+    """heads: per segment dict(gb, w, dzl, cout, dw, dbias, dgb) or None (a segment this call does not touch)"""
+    NB, H, W, F = y.shape
+    assert NB % nseg == 0 and len(heads) == nseg and partial.numel() >= (nchunks + nseg) * 2 * F
+    a = _lib.HeadBn()
+    a.y, a.ldy, a.coef = ptr(y), _ld(y), ptr(coef)
+    a.F, a.nseg, a.B, a.hw = F, nseg, NB // nseg, H * W
+    a.partial, a.nchunks, a.dy_absmax = ptr(partial), int(nchunks), ptr(dy_absmax)
+    a.dy, a.lddy = ptr(dy), (_ld(dy) if dy is not None else 0)
+    for s, h in enumerate(heads):
+        if h is None:
+            continue
+        dzl = h["dzl"]
+        assert dzl.shape[0] * dzl.shape[1] * dzl.shape[2] == a.B * a.hw
+        a.gb[s], a.w[s], a.dzl[s], a.lddzl[s], a.Cout[s] = ptr(h.get("gb")), ptr(h["w"]), ptr(dzl), _ld(dzl), int(h["cout"])
+        a.dw[s], a.dbias[s], a.dgb[s] = ptr(h.get("dw")), ptr(h.get("dbias")), ptr(h.get("dgb"))
+    return a
+
+
+def head_bn_bwd_reduce(y, coef, nseg, partial, nchunks, heads, seg0=0, nsegs=None, dy_absmax=None):
+    """first pass of the fused backward for segments [seg0, seg0 + nsegs) (hrseg_head_bn_bwd_reduce): dw / dbias / dgb of their
+    heads accumulate, the BatchNorm partial sums of their chunks are written"""
+    nsegs = nseg - seg0 if nsegs is None else nsegs
+    hs = [h if seg0 <= s < seg0 + nsegs else None for s, h in enumerate(heads)]
+    a = _head_bn_struct(y, coef, nseg, partial, nchunks, hs, dy_absmax=dy_absmax)
+    call("hrseg_head_bn_bwd_reduce", C.byref(a), int(seg0), int(nsegs))
+
+
+def bn_bwd_finalize(y, coef, nseg, partial, nchunks, dgamma, dbeta):
+    """the unchanged finalize phase of bn_bwd_group alone (totals per segment behind the partials, dgamma / dbeta +=)"""
+    arr = (_lib.BnBwd * 1)()
+    a = arr[0]
+    F = y.shape[3]
+    # hrseg_bn_bwd_group_phases checks dz / y / dy of every problem whatever the phases; phase 2 (finalize) reads `partial` and
+    # writes the totals, dgamma and dbeta only.  A finalize-only call relies on that: y stands in for dz and dy, untouched
+    a.dz, a.lddz, a.y, a.ldy, a.coef = ptr(y), _ld(y), ptr(y), _ld(y), ptr(coef)     # (dz / dy: unused by this phase, non-NULL)
+    a.dy, a.lddy = ptr(y), _ld(y)
+    a.dgamma, a.dbeta = ptr(dgamma), ptr(dbeta)
+    a.npix, a.C, a.partial, a.nchunks, a.nseg, a.sum_ranks = _npix(y), F, ptr(partial), int(nchunks), nseg, 1
+    call("hrseg_bn_bwd_group_phases", 1, arr, 0, 2)
+
+
+def head_bn_bwd_apply(y, coef, nseg, partial, nchunks, heads, dy=None, dy_absmax=None):
+    """second pass (hrseg_head_bn_bwd_apply): -> dy of the layer's convolution output"""
+    if dy is None:
+        dy = torch.empty(y.shape, dtype=torch.float32, device=y.device)
+    a = _head_bn_struct(y, coef, nseg, partial, nchunks, heads, dy=dy, dy_absmax=dy_absmax)
+    call("hrseg_head_bn_bwd_apply", C.byref(a))
+    return dy
 
 
 def logits_up_fwd(z, Ho, Wo, align_corners=True):
