@@ -156,8 +156,9 @@ int hrseg_conv_wgrad_group_ws(int n, const float* const* x, const float* const* 
  * zeroes what it returns.  "ws_canvas" counts PROBLEMS (not launches, not part of the NULL total) that a "ws" / "ws_group"
  * launch tiled as one canvas of side-by-side images, "wgrad_sp_t5" the "wgrad_sp" launches on 80 x 80 tiles ("wgrad_sp_wide": the wide-tile weight-gradient kernel, a family of its own).  The parity tests use it to prove which kernels a case ran.
  * "augment_image" / "augment_targets" (the input pipeline) and "decode_labels" (the output pipeline, 1 launch per
- * hrseg_decode_labels call) and "score_labels" (the scoring pipeline, 1 launch per hrseg_score_labels call) are families
- * of their own, outside the NULL total and the convolution counts. */
+ * hrseg_decode_labels call) and "score_labels" (the scoring pipeline, 1 launch per hrseg_score_labels call), "decode_views"
+ * and "flip_views" (test-time augmentation, 1 launch per hrseg_decode_views / hrseg_flip_views call) are families of their
+ * own, outside the NULL total and the convolution counts. */
 long hrseg_launch_count(const char* family, int reset);
 /* tile-plan overrides and A/B switches for the sweep tools under tools/ (value 0 = automatic plan).  Keys: igemm_wtm,
  * igemm_kc, igemm_db, igemm_ksplit, group_wtm, wgrad_pix, wgrad_db, wgrad_blocks, wgrad_group_mult,
@@ -584,6 +585,42 @@ typedef struct {
 int hrseg_decode_labels(int nlevels, const float* const* z, const int* C, const hrseg_decode_tree_t* tree,
                         const long* desc, unsigned char* labels, float* confidence, int B, int S,
                         hrseg_stream_t stream);
+
+/* ------------------------------------------------------------------ test-time augmentation (predictEval.TestTimeAugment)
+ * hrseg_decode_views: the decode above on the MEAN logit of an ensemble of views.  A view v is one set of per-level logits
+ * z_v[L] of shape [B, C[L], S_v, S_v] (fp32 NCHW) plus flags f_v in {0, HRSEG_VIEW_HFLIP, HRSEG_VIEW_VFLIP, both}: the
+ * network saw the image mirrored along x and/or y (and resized to S_v).  S and flags are HOST arrays of nviews entries, z a
+ * HOST array of nviews * nlevels DEVICE pointers, view-major (z[v * nlevels + L]).  For output pixel (y, x) of sample b
+ * (H_b x W_b from desc):
+ *   1. per view, the row and column taps and weights follow from the output coordinate exactly as in hrseg_decode_labels
+ *      (scale S_v / H_b, torch align_corners=False); on a flipped axis the kernel reads source index S_v - 1 - i where it
+ *      would have read i, with the same weights: torch.flip of the view's logits followed by F.interpolate(bilinear,
+ *      align_corners=False).  The 2 x 2 blend rounds exactly as hrseg_decode_labels rounds it (the same multiplies and
+ *      fused multiply-adds in the same order): r_v;
+ *   2. mean logit m = ((r_0 + r_1) + ... + r_{V-1}) * (1.0f / V): fp32 round-to-nearest adds in view order, one multiply,
+ *      no contraction; with V = 1 this is r_0 bit for bit, and the call returns what hrseg_decode_labels returns;
+ *   3. steps 2-5 of hrseg_decode_labels unchanged on m: arg-max over level 0, top-down through the child group of the
+ *      chosen node only, leaf pixel value, optional confidence sigmoid(m_0[c_0]) * prod_L softmax_group(m_L)[c_L]
+ *      (root_softmax as there).
+ * In probability terms a group's soft-max of the mean logit is the normalised geometric mean of the views' group
+ * soft-maxes; the decoded path is still always a path of the tree.
+ * Limits: 1 <= nviews <= HRSEG_DECODE_MAX_VIEWS, flags[v] in 0..3, 1 <= S[v] <= 32768, and every limit and alignment rule
+ * of hrseg_decode_labels; each violation is refused with a message before anything is launched.  Only the groups on the
+ * decoded path are fetched (V x 4 taps per channel).  1 launch, counted under the family "decode_views" (never under
+ * "decode_labels"), outside the NULL total; no workspace, no device allocation, no synchronisation. */
+#define HRSEG_DECODE_MAX_VIEWS 8
+#define HRSEG_VIEW_HFLIP 1
+#define HRSEG_VIEW_VFLIP 2
+int hrseg_decode_views(int nviews, const int* S, const int* flags, int nlevels, const float* const* z, const int* C,
+                       const hrseg_decode_tree_t* tree, const long* desc, unsigned char* labels, float* confidence,
+                       int B, hrseg_stream_t stream);
+/* The network inputs of all flip views of one scale: out [nviews * B, C, H, W], block v is x [B, C, H, W] mirrored as
+ * flags[v] says (HOST array; 0: a plain copy).  An exact copy of bits, float4 moves where W % 4 == 0 and both tensors are
+ * 16-byte aligned.  The blocks then go through ONE eval-mode forward of batch nviews * B (eval-mode BatchNorm uses the
+ * running statistics: samples do not interact).  nviews <= HRSEG_DECODE_MAX_VIEWS, fewer than 2^31 output elements.
+ * 1 launch, family "flip_views", outside the NULL total. */
+int hrseg_flip_views(const float* x, float* out, int nviews, const int* flags, int B, int C, int H, int W,
+                     hrseg_stream_t stream);
 
 /* ------------------------------------------------------------------ device scoring pipeline (Data/score.py)
  * The third stage behind the input and output pipelines: a batch of predicted label maps (hrseg_decode_labels) against

@@ -8,7 +8,10 @@ model's own probabilities and the decoded path is always a path of the tree -- w
 per-level arg-max does not guarantee.  The logits are resampled bilinearly (F.interpolate, align_corners=False) to each
 image's own H x W inside the kernel; no full-size fp32 tensor exists at any point.
 
-The tables are built on the host without a GPU; only `decode` launches.
+`decode_views` does the same on the mean logit of several views of the batch (mirrored and/or rescaled network inputs:
+test-time augmentation, predictEval.TestTimeAugment), still in one launch (csrc/decode_views.hip).
+
+The tables are built on the host without a GPU; only `decode` / `decode_views` launch.
 """
 from __future__ import annotations
 
@@ -136,6 +139,26 @@ class DeviceDecode:
     def decode_sizes(self, output_logits, sizes, want_confidence=False) -> RaggedLabels:
         """decode to a densely packed batch of the given [(H, W), ...]"""
         return self.decode(output_logits, label_desc(sizes), None, want_confidence)
+
+    def decode_views(self, views, desc, desc_host=None, want_confidence=False) -> RaggedLabels:
+        """test-time augmentation: `views` is a list of (output_logits, flags), each the logits of the same batch as the
+        network saw it mirrored by flags (0, ops.VIEW_HFLIP, ops.VIEW_VFLIP or both) and resized to the view's own
+        S_v x S_v; the mean logit of the views (each flipped back and resampled to the image's size) is decoded as
+        `decode` decodes one set of logits.  One launch (csrc/decode_views.hip)."""
+        require_gpu()
+        views = [(([z] if torch.is_tensor(z) else list(z)), f) for z, f in views]
+        if desc_host is None:
+            if desc.is_cuda:
+                raise ValueError("a device descriptor table needs its host copy (desc_host)")
+            desc_host = desc
+        if views and views[0][0]:
+            desc = desc.to(views[0][0][0].device, non_blocking=True)
+        labels, conf = ops.decode_views(views, self.tables, desc, desc_host, want_confidence)
+        return RaggedLabels(labels, conf, desc, desc_host)
+
+    def decode_views_sizes(self, views, sizes, want_confidence=False) -> RaggedLabels:
+        """decode_views to a densely packed batch of the given [(H, W), ...]"""
+        return self.decode_views(views, label_desc(sizes), None, want_confidence)
 
 
 def pack_images(images):

@@ -132,6 +132,9 @@ PROTOTYPES = {
     "hrseg_augment_image": [_p, _p, _p, _p, _i, _i, _i, _p, C.c_size_t, _p],
     "hrseg_augment_targets": [_p, _p, _p, C.POINTER(C.c_int), _p, _p, _i, _i, _i, _i, _i, _p, C.c_size_t, _p],
     "hrseg_decode_labels": [_i, _p, C.POINTER(C.c_int), C.POINTER(DecodeTree), _p, _p, _p, _i, _i, _p],
+    "hrseg_decode_views": [_i, C.POINTER(C.c_int), C.POINTER(C.c_int), _i, _p, C.POINTER(C.c_int), C.POINTER(DecodeTree), _p, _p, _p,
+                           _i, _p],
+    "hrseg_flip_views": [_p, _p, _i, C.POINTER(C.c_int), _i, _i, _i, _i, _p],
     "hrseg_score_labels": [_p, _p, _p, _p, _p, _i, C.POINTER(C.c_int), _p, _p, _i, _i, _p],
     "hrseg_combine_levels": [_p, _i, _p, _i, _p, _p, _p, _i, _i, _l, _p],
     "hrseg_weight_images_refresh": [_p],
@@ -227,7 +230,7 @@ _deterministic = False
 def launch_count(family=None, reset=False) -> int:
     """launches issued so far by kernel family (hrseg_launch_count; None = all convolution families; the input
     pipeline counts under "augment_image" / "augment_targets", the output pipeline under "decode_labels", the scoring
-    pipeline under "score_labels")"""
+    pipeline under "score_labels", test-time augmentation under "decode_views" / "flip_views")"""
     return int(_lib.hrseg_launch_count(None if family is None else family.encode(), int(reset)))
 
 

@@ -22,37 +22,14 @@
 //
 // The tree (<= 8 levels x 16 channels, one packed dword per node) and the level pointers are kernel arguments; the
 // block copies the node table to LDS once because lanes index it with their own channel.
-#include "common.h"
+#include "decode_common.h"
 
-typedef unsigned char u8;
-
-#define DEC_TPB 256
-#define DEC_PX 4                                  // pixels per lane: one dword of labels
-#define DEC_ROWS (DEC_TPB / HRSEG_WAVE)           // rows per tile: one per wave
-#define DEC_TILE_W (HRSEG_WAVE * DEC_PX)
-#define DEC_NODES (HRSEG_DECODE_MAX_LEVELS * HRSEG_DECODE_MAX_CHANNELS)
-
-// node dword: bits 0-7 first child channel at the next level, 8-15 child count (0 = leaf), 16-23 leaf pixel value
 struct DecodeArgs {
   const float* z[HRSEG_DECODE_MAX_LEVELS];
   int C[HRSEG_DECODE_MAX_LEVELS];
-  unsigned node[DEC_NODES];
+  unsigned node[DEC_NODES];                       // one packed dword per node (decode_common.h)
   int nlevels, root_softmax;
 };
-
-// torch upsample_bilinear2d (align_corners=False) source taps and weights of one output coordinate
-struct DecLin { int i0, i1; float l0, l1; };
-__device__ __forceinline__ DecLin dec_lin(int dst, float scale, int in) {
-  float real = __fsub_rn(__fmul_rn(scale, (float)dst + 0.5f), 0.5f);
-  if (real < 0.f) real = 0.f;
-  DecLin r;
-  r.i0 = min((int)real, in - 1);
-  const float lam = fminf(fmaxf(real - (float)r.i0, 0.f), 1.f);
-  r.i1 = r.i0 + (r.i0 < in - 1 ? 1 : 0);
-  r.l1 = lam;
-  r.l0 = 1.f - lam;
-  return r;
-}
 
 template <bool CONF>
 __global__ __launch_bounds__(DEC_TPB) void decode_labels_kernel(DecodeArgs a, const long long* __restrict__ desc,
@@ -170,45 +147,17 @@ extern "C" int hrseg_decode_labels(int nlevels, const float* const* z, const int
                                    hrseg_stream_t stream) {
   HRSEG_CHECK_ARG(z && C && tree && desc && labels && B > 0 && B <= 65535 && S > 0 && S <= 32768,
                   "hrseg_decode_labels: bad arguments");
-  HRSEG_CHECK_ARG(nlevels >= 1 && nlevels <= HRSEG_DECODE_MAX_LEVELS, "hrseg_decode_labels: nlevels=%d not in 1..%d", nlevels,
-                  HRSEG_DECODE_MAX_LEVELS);
   HRSEG_CHECK_ARG(((uintptr_t)labels & 3) == 0 && ((uintptr_t)confidence & 15) == 0,
                   "hrseg_decode_labels: labels must be 4-byte and confidence 16-byte aligned");
   DecodeArgs a;
-  int total = 0;
+  if (const int rc = dec_pack_tree("hrseg_decode_labels", nlevels, C, tree, a.node, a.C)) return rc;
   for (int L = 0; L < HRSEG_DECODE_MAX_LEVELS; ++L) {
-    a.z[L] = nullptr;
-    a.C[L] = 0;
+    HRSEG_CHECK_ARG(L >= nlevels || z[L], "hrseg_decode_labels: level %d has no logits", L);
+    a.z[L] = L < nlevels ? z[L] : nullptr;
   }
-  for (int i = 0; i < DEC_NODES; ++i) a.node[i] = 0;
-  for (int L = 0; L < nlevels; ++L) {
-    HRSEG_CHECK_ARG(C[L] >= 1 && C[L] <= HRSEG_DECODE_MAX_CHANNELS, "hrseg_decode_labels: C[%d]=%d not in 1..%d", L, C[L],
-                    HRSEG_DECODE_MAX_CHANNELS);
-    HRSEG_CHECK_ARG(z[L], "hrseg_decode_labels: level %d has no logits", L);
-    a.z[L] = z[L];
-    a.C[L] = C[L];
-    total += C[L];
-  }
-  HRSEG_CHECK_ARG(total <= 64, "hrseg_decode_labels: %d channels over all levels, at most 64", total);
-  for (int L = 0; L < nlevels; ++L)
-    for (int c = 0; c < C[L]; ++c) {
-      const int first = tree->first_child[L][c], kids = tree->n_children[L][c], pv = tree->pixel_val[L][c];
-      if (kids == 0) {
-        HRSEG_CHECK_ARG(pv >= 0 && pv <= 255, "hrseg_decode_labels: leaf (level %d, channel %d) has pixel value %d", L, c, pv);
-        a.node[L * HRSEG_DECODE_MAX_CHANNELS + c] = (unsigned)pv << 16;
-      } else {
-        HRSEG_CHECK_ARG(L + 1 < nlevels && kids > 0 && first >= 0 && first + kids <= C[L + 1],
-                        "hrseg_decode_labels: children [%d, %d) of (level %d, channel %d) are not channels of the next level", first,
-                        first + kids, L, c);
-        a.node[L * HRSEG_DECODE_MAX_CHANNELS + c] = (unsigned)first | ((unsigned)kids << 8);
-      }
-    }
   a.nlevels = nlevels;
   a.root_softmax = tree->root_softmax ? 1 : 0;
-  // every sample gets the same number of striding blocks (its size is known on the device only): about 8192 in all
-  int per_sample = 8192 / B;
-  per_sample = per_sample < 1 ? 1 : (per_sample > 1024 ? 1024 : per_sample);
-  const dim3 grid((unsigned)per_sample, (unsigned)B);
+  const dim3 grid((unsigned)dec_blocks_per_sample(B), (unsigned)B);
   if (confidence)
     hipLaunchKernelGGL(decode_labels_kernel<true>, grid, dim3(DEC_TPB), 0, (hipStream_t)stream, a, (const long long*)desc, labels,
                        confidence, S);

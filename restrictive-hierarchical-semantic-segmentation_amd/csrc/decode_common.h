@@ -1,0 +1,68 @@
+// What the two decode kernels share (decode.hip: one view, decode_views.hip: the mean logit of several views): the tile
+// shape, the bilinear taps of one output coordinate and the host-side validation and packing of the tree.
+#pragma once
+#include "common.h"
+
+typedef unsigned char u8;
+
+#define DEC_TPB 256
+#define DEC_PX 4                                  // pixels per lane: one dword of labels
+#define DEC_ROWS (DEC_TPB / HRSEG_WAVE)           // rows per tile: one per wave
+#define DEC_TILE_W (HRSEG_WAVE * DEC_PX)
+#define DEC_NODES (HRSEG_DECODE_MAX_LEVELS * HRSEG_DECODE_MAX_CHANNELS)
+
+// torch upsample_bilinear2d (align_corners=False) source taps and weights of one output coordinate.  The source
+// coordinate is ONE fused multiply-add, written out (it is what the compiler made of scale * (dst + 0.5) - 0.5 in
+// decode_labels_kernel all along) so that both kernels round it alike wherever the call is inlined.
+struct DecLin { int i0, i1; float l0, l1; };
+__device__ __forceinline__ DecLin dec_lin(int dst, float scale, int in) {
+#pragma clang fp contract(off)
+  float real = __builtin_fmaf(scale, (float)dst + 0.5f, -0.5f);
+  if (real < 0.f) real = 0.f;
+  DecLin r;
+  r.i0 = min((int)real, in - 1);
+  const float lam = fminf(fmaxf(real - (float)r.i0, 0.f), 1.f);
+  r.i1 = r.i0 + (r.i0 < in - 1 ? 1 : 0);
+  r.l1 = lam;
+  r.l0 = 1.f - lam;
+  return r;
+}
+
+// Checks nlevels, C and the tree against the limits of include/hrseg.h and packs one dword per node into node[DEC_NODES]
+// (bits 0-7 first child channel at the next level, 8-15 child count (0 = leaf), 16-23 leaf pixel value) and the channel
+// counts into Cout[HRSEG_DECODE_MAX_LEVELS].  `who` is the entry point's name in the messages.
+static inline int dec_pack_tree(const char* who, int nlevels, const int* C, const hrseg_decode_tree_t* tree, unsigned* node,
+                                int* Cout) {
+  HRSEG_CHECK_ARG(nlevels >= 1 && nlevels <= HRSEG_DECODE_MAX_LEVELS, "%s: nlevels=%d not in 1..%d", who, nlevels,
+                  HRSEG_DECODE_MAX_LEVELS);
+  int total = 0;
+  for (int L = 0; L < HRSEG_DECODE_MAX_LEVELS; ++L) Cout[L] = 0;
+  for (int i = 0; i < DEC_NODES; ++i) node[i] = 0;
+  for (int L = 0; L < nlevels; ++L) {
+    HRSEG_CHECK_ARG(C[L] >= 1 && C[L] <= HRSEG_DECODE_MAX_CHANNELS, "%s: C[%d]=%d not in 1..%d", who, L, C[L],
+                    HRSEG_DECODE_MAX_CHANNELS);
+    Cout[L] = C[L];
+    total += C[L];
+  }
+  HRSEG_CHECK_ARG(total <= 64, "%s: %d channels over all levels, at most 64", who, total);
+  for (int L = 0; L < nlevels; ++L)
+    for (int c = 0; c < C[L]; ++c) {
+      const int first = tree->first_child[L][c], kids = tree->n_children[L][c], pv = tree->pixel_val[L][c];
+      if (kids == 0) {
+        HRSEG_CHECK_ARG(pv >= 0 && pv <= 255, "%s: leaf (level %d, channel %d) has pixel value %d", who, L, c, pv);
+        node[L * HRSEG_DECODE_MAX_CHANNELS + c] = (unsigned)pv << 16;
+      } else {
+        HRSEG_CHECK_ARG(L + 1 < nlevels && kids > 0 && first >= 0 && first + kids <= C[L + 1],
+                        "%s: children [%d, %d) of (level %d, channel %d) are not channels of the next level", who, first,
+                        first + kids, L, c);
+        node[L * HRSEG_DECODE_MAX_CHANNELS + c] = (unsigned)first | ((unsigned)kids << 8);
+      }
+    }
+  return 0;
+}
+
+// every sample gets the same number of striding blocks (its size is known on the device only): about 8192 in all
+static inline int dec_blocks_per_sample(int B) {
+  const int per_sample = 8192 / B;
+  return per_sample < 1 ? 1 : (per_sample > 1024 ? 1024 : per_sample);
+}

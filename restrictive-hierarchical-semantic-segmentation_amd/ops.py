@@ -691,6 +691,78 @@ def decode_labels(logits, tables, desc, desc_host, want_confidence=False):
     return labels, conf
 
 
+DECODE_MAX_VIEWS, DECODE_MAX_SIZE = 8, 32768
+VIEW_HFLIP, VIEW_VFLIP = 1, 2
+
+
+def _check_view_flags(what, flags):
+    flags = [int(f) for f in flags]
+    if not 1 <= len(flags) <= DECODE_MAX_VIEWS:
+        raise ValueError(f"{what}: {len(flags)} views, supported 1..{DECODE_MAX_VIEWS}")
+    for v, f in enumerate(flags):
+        if not 0 <= f <= 3:
+            raise ValueError(f"{what}: view {v} has flags {f}, supported 0..3 (HFLIP = 1, VFLIP = 2)")
+    return flags
+
+
+def flip_views(x, flags):
+    """x [B,C,H,W] fp32 (device) + one flag word per view (0, VIEW_HFLIP, VIEW_VFLIP or both) -> [len(flags)*B,C,H,W]:
+    block v is x mirrored as flags[v] says, bit for bit (the network inputs of the flip views of one scale, for ONE
+    eval-mode forward).  One launch, no synchronisation."""
+    flags = _check_view_flags("flip_views", flags)
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_cuda:
+        raise ValueError(f"flip_views: x must be a [B,C,H,W] fp32 device tensor, got {tuple(x.shape)} {x.dtype} on {x.device}")
+    B, Cn, H, W = x.shape
+    if min(B, Cn, H, W) < 1 or len(flags) * x.numel() >= 1 << 31:
+        raise ValueError(f"flip_views: {len(flags)} views of {tuple(x.shape)}: empty, or 2^31 output elements or more")
+    x = _c(x)
+    out = torch.empty((len(flags) * B, Cn, H, W), dtype=torch.float32, device=x.device)
+    call("hrseg_flip_views", ptr(x), ptr(out), len(flags), _lib.int_array(flags), B, Cn, H, W)
+    return out
+
+
+def decode_views(views, tables, desc, desc_host, want_confidence=False):
+    """decode_labels on the mean logit of an ensemble: views = [(per-level logits [B,C_L,S_v,S_v] fp32 device tensors, or one
+    tensor; flags), ...] with flags 0, VIEW_HFLIP, VIEW_VFLIP or both (the network saw the image mirrored), the sizes
+    S_v free per view -> (packed uint8 labels, packed fp32 confidence or None) exactly as decode_labels returns them.
+    Contiguous batch slices z[v*B:(v+1)*B] of one batched forward are read in place.  One launch, no synchronisation."""
+    views = [(([z] if torch.is_tensor(z) else list(z)), f) for z, f in views]
+    flags = _check_view_flags("decode_views", [f for _, f in views])
+    check_decode_tables(tables)
+    B = views[0][0][0].shape[0] if views[0][0] and views[0][0][0].dim() == 4 else -1
+    sizes = []
+    for v, (logits, _) in enumerate(views):
+        if len(logits) != len(tables.C):
+            raise ValueError(f"decode_views: view {v} has {len(logits)} logit levels for a {len(tables.C)}-level table")
+        if logits[0].dim() != 4:
+            raise ValueError(f"decode_views: view {v}, level 0 logits of shape {tuple(logits[0].shape)}, expected 4 dimensions")
+        if logits[0].shape[0] != B:
+            raise ValueError(f"decode_views: view {v} has batch size {logits[0].shape[0]}, view 0 has {B}")
+        S = logits[0].shape[2]
+        if not 1 <= S <= DECODE_MAX_SIZE:
+            raise ValueError(f"decode_views: view {v} has size {S}, supported 1..{DECODE_MAX_SIZE}")
+        for L, z in enumerate(logits):
+            if z.dim() != 4 or tuple(z.shape) != (B, tables.C[L], S, S):
+                raise ValueError(f"decode_views: view {v}, level {L} logits of shape {tuple(z.shape)}, expected "
+                                 f"{(B, tables.C[L], S, S)}")
+            if not z.is_cuda or z.dtype != torch.float32:
+                raise ValueError(f"decode_views: view {v}, level {L}: logits must be fp32 device tensors")
+        sizes.append(S)
+    if desc.dtype != torch.int64 or not desc.is_cuda or desc.dim() != 2 or not tuple(desc.shape) == tuple(desc_host.shape) == (B, 4):
+        raise ValueError(f"decode_views: the descriptor tables must be [{B},4] int64, one on the device and its host copy")
+    rows = desc_host.tolist()
+    n = sum(H * W for _, H, W, _ in rows)
+    for off, H, W, ch in rows:
+        if ch != 1 or H < 1 or W < 1 or off < 0 or off + H * W > n:
+            raise ValueError(f"ragged descriptor (offset {off}, {H}x{W}, {ch} channels) does not fit a {n}-byte label buffer")
+    flat = [_c(z) for logits, _ in views for z in logits]
+    labels = torch.empty(n, dtype=torch.uint8, device=flat[0].device)
+    conf = torch.empty(n, dtype=torch.float32, device=flat[0].device) if want_confidence else None
+    call("hrseg_decode_views", len(views), _lib.int_array(sizes), _lib.int_array(flags), len(tables.C), _lib.ptr_array(flat),
+         _lib.int_array(list(tables.C)), C.byref(_decode_tree_struct(tables)), ptr(desc), ptr(labels), ptr(conf), B)
+    return labels, conf
+
+
 SCORE_MAX_LEVELS, SCORE_MAX_CHANNELS, SCORE_MAX_TOTAL = 8, 16, 64
 # pixels a lane / a wave / a block of hrseg_score_labels takes per step (HRSEG_SCORE_*_STEP of include/hrseg.h): the sizes
 # around which the kernel changes path

@@ -174,6 +174,38 @@ def save_label_maps(save_dir, names, ragged_labels):
     return paths
 
 
+class TestTimeAugment:
+    """Flip and multi-scale ensembling at inference (the reference's HRNet configuration names it TEST.FLIP_TEST /
+    TEST.MULTI_SCALE / TEST.SCALE_LIST): the views a Predictor averages.  `views(size)` -> the ordered list of
+    (S, flags): scale-major in the order given, S = int(round(size * scale)); within a scale the flags run 0, HFLIP,
+    VFLIP, HFLIP|VFLIP as enabled (ops.VIEW_HFLIP = 1, ops.VIEW_VFLIP = 2).  At most ops.DECODE_MAX_VIEWS views."""
+    __test__ = False        # (not a test class, whatever its name starts with)
+
+    def __init__(self, hflip=True, vflip=False, scales=(1.0,)):
+        self.hflip, self.vflip = bool(hflip), bool(vflip)
+        self.scales = tuple(float(s) for s in scales)
+        if not self.scales:
+            raise ValueError("TestTimeAugment: no scales")
+        if any(not s > 0.0 or s == float("inf") for s in self.scales):
+            raise ValueError(f"TestTimeAugment: scales {self.scales} must be positive")
+        if len(set(self.scales)) != len(self.scales):
+            raise ValueError(f"TestTimeAugment: duplicate scale in {self.scales}")
+        self.flags = [f for f in (0, ops.VIEW_HFLIP, ops.VIEW_VFLIP, ops.VIEW_HFLIP | ops.VIEW_VFLIP)
+                      if (self.hflip or not f & ops.VIEW_HFLIP) and (self.vflip or not f & ops.VIEW_VFLIP)]
+        if len(self.scales) * len(self.flags) > ops.DECODE_MAX_VIEWS:
+            raise ValueError(f"TestTimeAugment: {len(self.scales)} scales x {len(self.flags)} flips are more than "
+                             f"{ops.DECODE_MAX_VIEWS} views")
+
+    def views(self, size):
+        out = []
+        for scale in self.scales:
+            S = int(round(int(size) * scale))
+            if not 1 <= S <= ops.DECODE_MAX_SIZE:
+                raise ValueError(f"TestTimeAugment: scale {scale} of size {size} gives {S}, supported 1..{ops.DECODE_MAX_SIZE}")
+            out.extend((S, f) for f in self.flags)
+        return out
+
+
 class Predictor:
     """Deployment-side inference: `labels = Predictor(model, class_tree, class_map, args)(images)` with a list of ragged
     uint8 HxW / HxWx3 sources (or a RaggedBatch) -> RaggedLabels, one label map per source at the source's own size.
@@ -182,9 +214,13 @@ class Predictor:
     The model runs in eval mode for the call and gets its previous mode back afterwards.  keep_logits=True keeps the
     latest call's logits (what the decode read) alive in `last_logits`; by default nothing of a batch is held.
     `scores = predictor.score(images, labels)` decodes at the ground-truth maps' own sizes instead and scores the maps
-    against them on the device (Data/score.py) -> SourceScores; the decoded maps of that call stay in `last_labels`."""
+    against them on the device (Data/score.py) -> SourceScores; the decoded maps of that call stay in `last_labels`.
+    tta=TestTimeAugment(...): per scale one eval-mode resize to S, ops.flip_views and ONE forward of all the scale's
+    flip views as a batch (eval-mode BatchNorm uses the running statistics: samples do not interact), then one
+    decode of the mean logit over all views (Data.DeviceDecode.decode_views); keep_logits=True then keeps
+    `last_view_logits`, the list of (logits, flags) the decode read.  tta=None: exactly the calls described above."""
 
-    def __init__(self, model, class_tree, class_map, args, want_confidence=False, keep_logits=False):
+    def __init__(self, model, class_tree, class_map, args, want_confidence=False, keep_logits=False, tta=None):
         from .Data.decode import DeviceDecode
         self.model, self.class_tree, self.class_map, self.args = model, class_tree, class_map, args
         self.scorer, self.last_labels = None, None
@@ -193,6 +229,9 @@ class Predictor:
         self.want_confidence = bool(want_confidence)
         self.keep_logits = bool(keep_logits)
         self.last_logits = None
+        self.tta, self.last_view_logits = tta, None
+        if tta is not None:
+            tta.views(self.size)                    # refuses sizes the decode cannot take before any image is seen
 
     def __call__(self, images):
         return self._predict(images, None)
@@ -234,14 +273,28 @@ class Predictor:
         src, desc = src.to(device, non_blocking=True), desc.to(device, non_blocking=True)
         was_training = self.model.training
         self.model.eval()
+        views = []
         try:
-            x = ops.augment_image(src, desc, desc_host, None, self.size, False)
-            _, output_logits = T._model_call(self.model, x, self.args, self.class_tree)
+            if self.tta is None:
+                x = ops.augment_image(src, desc, desc_host, None, self.size, False)
+                _, output_logits = T._model_call(self.model, x, self.args, self.class_tree)
+            else:
+                B, flags = desc_host.shape[0], self.tta.flags
+                for S, _ in self.tta.views(self.size)[::len(flags)]:                    # one forward per scale
+                    x = ops.augment_image(src, desc, desc_host, None, S, False)
+                    if flags != [0]:
+                        x = ops.flip_views(x, flags)
+                    _, z = T._model_call(self.model, x, self.args, self.class_tree)
+                    z = [z] if torch.is_tensor(z) else list(z)
+                    views.extend(([a[i * B:(i + 1) * B] for a in z], f) for i, f in enumerate(flags))
         finally:
             self.model.train(was_training)
+        ldesc = label_desc([(H, W) for _, H, W, _ in desc_host.tolist()] if sizes is None else sizes)
+        if self.tta is not None:
+            self.last_view_logits = views if self.keep_logits else None
+            return self.decoder.decode_views(views, ldesc, None, self.want_confidence)
         if self.keep_logits:
             self.last_logits = output_logits
-        ldesc = label_desc([(H, W) for _, H, W, _ in desc_host.tolist()] if sizes is None else sizes)
         return self.decoder.decode(output_logits, ldesc, None, self.want_confidence)
 
 

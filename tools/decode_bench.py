@@ -5,7 +5,14 @@ HBM peak), with and without the confidence, (2) the same labels composed from st
 level, argmax, where, a LUT gather) timed the same way in the same process -- the yardstick --, (3) the host time of
 one predictEval.Predictor call (sources -> label maps) on the flagship hierarchical HRNet.
 
-    python tools/decode_bench.py [--batches 60] [--skip-predictor]
+    python tools/decode_bench.py [--batches 60] [--skip-predictor] [--views N]
+
+--views N (1..4) adds test-time augmentation at the same geometry: N flip views (flags 0, H, V, H|V) of 620x620 logits,
+(4) the median device time of the fused ops.decode_views, with and without the confidence, (5) beside it N x the median
+of the single-view ops.decode_labels on the same inputs (that kernel does not change with this option: the figure is the
+taps' cost in N separate launches, each of which also writes the labels), (6) the stock-torch composition of the same
+ensemble: flip every view back, F.interpolate every level to the source size, mean, then arg-max, where and the LUT
+gather as in (2) (hrseg_decode_labels takes square logits, so it cannot stand in for that last step at 1400x2900).
 
 The events bracket ops.decode_labels as a whole (descriptor check, two allocations, the launch), so a median may hold
 a host gap.  Kernel durations without it: run the same command under `rocprofv3 --kernel-trace --stats -- python ...`
@@ -60,11 +67,70 @@ def timed(fn, n, warmup=5):
     return ts
 
 
+def bench_views(a, dec, z, desc, host, B, S, H, W, timed, out):
+    """N flip views of the 620 -> 1400x2900 batch: fused decode_views vs N single-view launches vs stock torch"""
+    from hrseg_amd import ops
+    device = z[0].device
+    Cs = dec.tables.C
+    dims = {0: [], 1: [-1], 2: [-2], 3: [-2, -1]}
+    views = []
+    for f in range(a.views):                     # view f: its own logits, as the network would return them for a mirrored input
+        zv = smooth_logits(B, Cs, S, 10 + f, device)
+        views.append(([torch.flip(t, dims[f]).contiguous() if dims[f] else t for t in zv], f))
+
+    def fused(conf=False):
+        out["vlabels"], out["vconf"] = ops.decode_views(views, dec.tables, desc, host, conf)
+
+    def single(conf=False):
+        out["labels"], out["conf"] = ops.decode_labels(views[0][0], dec.tables, desc, host, conf)
+
+    n = a.batches
+    # alternate the fused and the single-view launches so that both see the same machine state
+    tf, ts1, tfc, ts1c = [], [], [], []
+    for _ in range(4):
+        tf += timed(fused, n // 4 or 1)
+        ts1 += timed(single, n // 4 or 1)
+        tfc += timed(lambda: fused(True), n // 4 or 1)
+        ts1c += timed(lambda: single(True), n // 4 or 1)
+    res = dict(views=a.views,
+               decode_views_ms_median=round(statistics.median(tf), 4), decode_views_ms_min=round(min(tf), 4),
+               decode_views_with_confidence_ms_median=round(statistics.median(tfc), 4),
+               single_view_ms_median=round(statistics.median(ts1), 4),
+               n_single_view_launches_ms=round(a.views * statistics.median(ts1), 4),
+               n_single_view_launches_with_confidence_ms=round(a.views * statistics.median(ts1c), 4),
+               views_bytes_per_batch=a.views * B * S * S * 4 * sum(Cs) + B * H * W)
+    res["fused_over_n_single"] = round(res["decode_views_ms_median"] / res["n_single_view_launches_ms"], 3)
+
+    # stock torch: the mean logit at source size (flip, interpolate, add, scale per level), then arg-max / where / LUT as above
+    parent = [c for c, k in enumerate(dec.tables.n_children[0]) if k][0]
+    lut = torch.tensor([v if v >= 0 else 0 for v in dec.tables.pixel_val[0]] + dec.tables.pixel_val[1], dtype=torch.uint8, device=device)
+
+    def stock_views():
+        arg = []
+        for L in range(len(Cs)):
+            acc = None
+            for zv, f in views:
+                r = F.interpolate(torch.flip(zv[L], dims[f]) if dims[f] else zv[L], size=(H, W), mode="bilinear", align_corners=False)
+                acc = r if acc is None else acc + r
+            arg.append((acc * (1.0 / len(views))).argmax(1))
+        out["slabels"] = lut[torch.where(arg[0] == parent, arg[1] + Cs[0], arg[0])]
+
+    tt = timed(stock_views, max(n // 6, 5), warmup=2)
+    fused()
+    res.update(stock_torch_views_ms_median=round(statistics.median(tt), 4),
+               views_speedup_over_stock=round(statistics.median(tt) / statistics.median(tf), 2),
+               views_labels_differing_from_stock=int((out["vlabels"].reshape(B, H, W) != out["slabels"]).sum()))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, default=60)
     ap.add_argument("--skip-predictor", action="store_true")
+    ap.add_argument("--views", type=int, default=0, help="also time the fused decode of N flip views (1..4)")
     a = ap.parse_args()
+    if not 0 <= a.views <= 4:
+        ap.error("--views takes 1..4 (the four flips of one scale)")
     from hrseg_amd import ops
     from hrseg_amd.Data import DeviceDecode
     from hrseg_amd.Data.decode import label_desc
@@ -112,6 +178,10 @@ def main():
                stock_torch_ms_median=round(mst, 4), stock_torch_ms_min=round(min(tt), 4), speedup_over_stock=round(mst / ms, 2),
                labels_differing_from_stock=differ, pixels=B * H * W)
     log(json.dumps(res))
+
+    if a.views:
+        res.update(bench_views(a, dec, z, desc, host, B, S, H, W, timed, out))
+        log(json.dumps(res))
 
     if not a.skip_predictor:
         from hrseg_amd import predictEval as PE
