@@ -157,7 +157,8 @@ int hrseg_conv_wgrad_group_ws(int n, const float* const* x, const float* const* 
  * launch tiled as one canvas of side-by-side images, "wgrad_sp_t5" the "wgrad_sp" launches on 80 x 80 tiles ("wgrad_sp_wide": the wide-tile weight-gradient kernel, a family of its own).  The parity tests use it to prove which kernels a case ran.
  * "augment_image" / "augment_targets" (the input pipeline) and "decode_labels" (the output pipeline, 1 launch per
  * hrseg_decode_labels call) and "score_labels" (the scoring pipeline, 1 launch per hrseg_score_labels call), "decode_views"
- * and "flip_views" (test-time augmentation, 1 launch per hrseg_decode_views / hrseg_flip_views call) are families of their
+ * and "flip_views" (test-time augmentation, 1 launch per hrseg_decode_views / hrseg_flip_views call), "window_crops" and
+ * "decode_windows" (sliding-window inference, 1 launch per hrseg_window_crops / hrseg_decode_windows call) are families of their
  * own, outside the NULL total and the convolution counts. */
 long hrseg_launch_count(const char* family, int reset);
 /* tile-plan overrides and A/B switches for the sweep tools under tools/ (value 0 = automatic plan).  Keys: igemm_wtm,
@@ -621,6 +622,54 @@ int hrseg_decode_views(int nviews, const int* S, const int* flags, int nlevels, 
  * 1 launch, family "flip_views", outside the NULL total. */
 int hrseg_flip_views(const float* x, float* out, int nviews, const int* flags, int B, int C, int H, int W,
                      hrseg_stream_t stream);
+
+/* ------------------------------------------------------------------ sliding-window inference (predictEval.SlidingWindow)
+ * The network runs on overlapping S x S windows of a CANVAS of each image and the windows' logits are blended where they
+ * overlap.  The canvas Hc x Wc (Hc, Wc >= S) exists as arithmetic only: no canvas-size tensor is ever allocated.
+ * Both entry points read the same two DEVICE tables (the caller keeps host copies and validates on them):
+ *   wdesc [B][8] int64: Hc, Wc, ny, nx, n0, offset of the image's origins in `origins`, two spare entries (0);
+ *   origins int32: per image, at its offset, ny row origins ys[0..ny) then nx column origins xs[0..nx).
+ * Along an axis of canvas length n the origins are strictly increasing, the first is 0, the last is n - S, consecutive
+ * ones are at most S apart (every canvas coordinate is covered) and origins[k + 3] >= origins[k] + S (by at most
+ * HRSEG_WINDOW_MAX_COVER = 3 of them); ny, nx <= HRSEG_WINDOW_MAX_ORIGINS.  The windows of image m are the tensor product
+ * ys x xs, row-major, numbered n0 + a * nx + b; all numbers lie in [0, nwindows).
+ *
+ * hrseg_window_crops: x [nwindows,3,S,S] fp32.  Element (i, j) of window (a, b) of image m is the eval-mode value of
+ * hrseg_augment_image at canvas pixel (ys[a] + i, xs[b] + j) of a resize of source m (ragged uint8, desc as for
+ * hrseg_augment_image) to Hc x Wc: torch bilinear taps (align_corners=False) with scales H_m / Hc and W_m / Wc, then
+ * (v - 0.5) / 0.5; a one-channel source is replicated.  With Hc = Wc = S and one window the call is hrseg_augment_image
+ * (train == 0) bit for bit.  1 launch, family "window_crops", outside the NULL total; no workspace.
+ *
+ * hrseg_decode_windows: z: HOST array of nlevels DEVICE pointers, level L is [nwindows, C[L], S, S] fp32; profile: DEVICE
+ * array of S strictly positive fp32 blend weights (the same along both axes).  For output pixel (y, x) of image m, whose
+ * size H_m x W_m comes from desc (it need not be the canvas size):
+ *   1. canvas taps and weights: torch bilinear taps of y at scale Hc / H_m in a source of Hc rows, of x at Wc / W_m in Wc
+ *      columns -- the function and the rounding of hrseg_decode_labels; at H_m == Hc the tap is y with weight 1;
+ *   2. blended logit of channel k at a canvas pixel (r, c): A = the origins a with ys[a] <= r < ys[a] + S in ascending
+ *      order, Bc likewise for the columns, wy_a = profile[r - ys[a]], wx_b = profile[c - xs[b]].  In fp32, every operation
+ *      rounded to nearest and none contracted:
+ *        t_ab = (wy_a * wx_b) * z[n0 + a * nx + b][k][r - ys[a]][c - xs[b]]
+ *        num  = the t_ab added one by one, a ascending and within a the b ascending, starting FROM the first (not from 0)
+ *        sy   = the wy_a added in ascending order from the first, sx likewise
+ *        g    = num / (sy * sx)                                            (IEEE division)
+ *      One covering window with an all-ones profile gives (1 * 1) * z / (1 * 1) = z bit for bit;
+ *   3. the 2 x 2 blend of g at the four canvas taps, along x first, with the multiplies and fused multiply-adds of
+ *      hrseg_decode_labels in the same order.  A tap whose weight is 0 is not fetched: 0 takes its place;
+ *   4. steps 2-5 of hrseg_decode_labels unchanged: arg-max over level 0, top-down through the chosen node's child group
+ *      only, leaf pixel value, optional confidence (root_softmax as there).
+ * One window per image (Hc = Wc = S) with an all-ones profile therefore returns what hrseg_decode_labels returns, bit for
+ * bit.  Only the channels on the decoded path are fetched (up to 4 taps x 9 windows each), with 64-bit offsets into z.
+ * Refused with a message before anything is launched: NULL pointers (confidence may be NULL), B outside 1..65535,
+ * S outside 1..32768, nwindows < B, and every limit and alignment rule of hrseg_decode_labels on nlevels, C, the tree,
+ * labels and confidence.  1 launch, family "decode_windows" (never "decode_labels"), outside the NULL total; no
+ * workspace, no device allocation, no synchronisation. */
+#define HRSEG_WINDOW_MAX_ORIGINS 64
+#define HRSEG_WINDOW_MAX_COVER 3
+int hrseg_window_crops(const unsigned char* src, const long* desc, const long* wdesc, const int* origins, float* x,
+                       int B, int S, int nwindows, hrseg_stream_t stream);
+int hrseg_decode_windows(int nlevels, const float* const* z, const int* C, const hrseg_decode_tree_t* tree,
+                         const long* wdesc, const int* origins, const float* profile, const long* desc,
+                         unsigned char* labels, float* confidence, int B, int S, int nwindows, hrseg_stream_t stream);
 
 /* ------------------------------------------------------------------ device scoring pipeline (Data/score.py)
  * The third stage behind the input and output pipelines: a batch of predicted label maps (hrseg_decode_labels) against

@@ -1,5 +1,5 @@
 from .dataset import TargetEncoder  # noqa: F401
 from .loader import DeviceAugmentLoader, PngPairDataset, RaggedBatch, ragged_collate  # noqa: F401
 from .augment import DeviceAugment  # noqa: F401
-from .decode import DeviceDecode, RaggedLabels  # noqa: F401
+from .decode import DeviceDecode, RaggedLabels, WindowPlan, plan_windows, window_profile  # noqa: F401
 from .score import DeviceScore, SourceScores, build_score_tables  # noqa: F401

@@ -11,9 +11,15 @@ image's own H x W inside the kernel; no full-size fp32 tensor exists at any poin
 `decode_views` does the same on the mean logit of several views of the batch (mirrored and/or rescaled network inputs:
 test-time augmentation, predictEval.TestTimeAugment), still in one launch (csrc/decode_views.hip).
 
-The tables are built on the host without a GPU; only `decode` / `decode_views` launch.
+`decode_windows` decodes the logits of overlapping network-size windows of each image (sliding-window inference,
+predictEval.SlidingWindow), blended where they overlap, in one launch and without a canvas-size tensor (csrc/windows.hip);
+`plan_windows` lays the windows out on the host.
+
+The tables are built on the host without a GPU; only `decode` / `decode_views` / `decode_windows` launch.
 """
 from __future__ import annotations
+
+import math
 
 import numpy as np
 import torch
@@ -92,6 +98,68 @@ def label_desc(sizes) -> torch.Tensor:
     return torch.tensor(rows, dtype=torch.int64).reshape(-1, 4)
 
 
+def window_origins(n, S, stride):
+    """origins of the windows of size S along a canvas axis of length n >= S: [0] where n == S, else
+    ceil((n - S) / stride) + 1 origins min(i * stride, n - S) -- the last window is shifted back to end at the edge"""
+    n, S, stride = int(n), int(S), int(stride)
+    if n < S or stride < 1:
+        raise ValueError(f"window_origins: axis of {n} for windows of {S}, stride {stride}")
+    if n == S:
+        return [0]
+    return [min(i * stride, n - S) for i in range(-(-(n - S) // stride) + 1)]
+
+
+def window_profile(S, blend="hann"):
+    """the blend weight of a window's rows and columns, S strictly positive fp32 entries: "hann" =
+    float32(0.5 - 0.5 cos(2 pi (i + 0.5) / S)) evaluated in fp64, "uniform" = all ones"""
+    S = int(S)
+    if blend == "uniform":
+        return torch.ones(S, dtype=torch.float32)
+    if blend != "hann":
+        raise ValueError(f"window_profile: blend '{blend}', supported 'hann' and 'uniform'")
+    i = torch.arange(S, dtype=torch.float64)
+    return (0.5 - 0.5 * torch.cos(2.0 * math.pi * (i + 0.5) / S)).to(torch.float32)
+
+
+class WindowPlan:
+    """The windows of a batch as hrseg_window_crops / hrseg_decode_windows read them (include/hrseg.h), on the host:
+    `wdesc` [B,8] int64 (Hc, Wc, ny, nx, n0, offset of the image's origins, 0, 0), `origins` int32 (per image ny row origins
+    then nx column origins), `nwindows`, `S`.  Any tables that pass ops.check_window_plan are accepted, not only
+    `plan_windows`'."""
+
+    def __init__(self, wdesc, origins, nwindows, S):
+        self.wdesc = torch.as_tensor(wdesc, dtype=torch.int64).reshape(-1, 8)
+        self.origins = torch.as_tensor(origins, dtype=torch.int32).reshape(-1)
+        self.nwindows, self.S = int(nwindows), int(S)
+
+    def __len__(self):
+        return self.wdesc.shape[0]
+
+    def canvas(self, m):
+        return tuple(self.wdesc[m, :2].tolist())
+
+    def axes(self, m):
+        """(row origins, column origins) of image m"""
+        _, _, ny, nx, _, oo, _, _ = self.wdesc[m].tolist()
+        o = self.origins[oo:oo + ny + nx].tolist()
+        return o[:ny], o[ny:]
+
+    def first_window(self, m):
+        return int(self.wdesc[m, 4])
+
+
+def plan_windows(canvases, S, stride) -> WindowPlan:
+    """[(Hc, Wc), ...] -> the WindowPlan of window_origins along both axes of every canvas: the windows of an image are the
+    tensor product rows x columns, row-major, numbered from the image's n0 on"""
+    rows, org, n0 = [], [], 0
+    for Hc, Wc in canvases:
+        ys, xs = window_origins(Hc, S, stride), window_origins(Wc, S, stride)
+        rows.append([int(Hc), int(Wc), len(ys), len(xs), n0, len(org), 0, 0])
+        org += ys + xs
+        n0 += len(ys) * len(xs)
+    return WindowPlan(torch.tensor(rows, dtype=torch.int64).reshape(-1, 8), torch.tensor(org, dtype=torch.int32), n0, S)
+
+
 class RaggedLabels:
     """A decoded batch: `labels` packed uint8 (device), `confidence` packed fp32 (device) or None, `desc` [B,4] int64
     (device) and `desc_host` (byte offset, H, W, 1)."""
@@ -159,6 +227,25 @@ class DeviceDecode:
     def decode_views_sizes(self, views, sizes, want_confidence=False) -> RaggedLabels:
         """decode_views to a densely packed batch of the given [(H, W), ...]"""
         return self.decode_views(views, label_desc(sizes), None, want_confidence)
+
+    def decode_windows(self, output_logits, plan, profile, desc, desc_host=None, want_confidence=False) -> RaggedLabels:
+        """sliding-window inference: `output_logits` are the logits of the plan's N windows ([N,C_L,S,S] per level, window
+        order of the WindowPlan), `profile` the blend weights (`window_profile`); the windows' blend on each image's canvas is
+        resampled to the wanted sizes and decoded as `decode` decodes one set of logits.  One launch (csrc/windows.hip)."""
+        require_gpu()
+        logits = [output_logits] if torch.is_tensor(output_logits) else list(output_logits)
+        if desc_host is None:
+            if desc.is_cuda:
+                raise ValueError("a device descriptor table needs its host copy (desc_host)")
+            desc_host = desc
+        if logits and torch.is_tensor(logits[0]):
+            desc = desc.to(logits[0].device, non_blocking=True)
+        labels, conf = ops.decode_windows(logits, self.tables, plan, profile, desc, desc_host, want_confidence)
+        return RaggedLabels(labels, conf, desc, desc_host)
+
+    def decode_windows_sizes(self, output_logits, plan, profile, sizes, want_confidence=False) -> RaggedLabels:
+        """decode_windows to a densely packed batch of the given [(H, W), ...]"""
+        return self.decode_windows(output_logits, plan, profile, label_desc(sizes), None, want_confidence)
 
 
 def pack_images(images):

@@ -135,6 +135,8 @@ PROTOTYPES = {
     "hrseg_decode_views": [_i, C.POINTER(C.c_int), C.POINTER(C.c_int), _i, _p, C.POINTER(C.c_int), C.POINTER(DecodeTree), _p, _p, _p,
                            _i, _p],
     "hrseg_flip_views": [_p, _p, _i, C.POINTER(C.c_int), _i, _i, _i, _i, _p],
+    "hrseg_window_crops": [_p, _p, _p, _p, _p, _i, _i, _i, _p],
+    "hrseg_decode_windows": [_i, _p, C.POINTER(C.c_int), C.POINTER(DecodeTree), _p, _p, _p, _p, _p, _p, _i, _i, _i, _p],
     "hrseg_score_labels": [_p, _p, _p, _p, _p, _i, C.POINTER(C.c_int), _p, _p, _i, _i, _p],
     "hrseg_combine_levels": [_p, _i, _p, _i, _p, _p, _p, _i, _i, _l, _p],
     "hrseg_weight_images_refresh": [_p],
@@ -230,7 +232,8 @@ _deterministic = False
 def launch_count(family=None, reset=False) -> int:
     """launches issued so far by kernel family (hrseg_launch_count; None = all convolution families; the input
     pipeline counts under "augment_image" / "augment_targets", the output pipeline under "decode_labels", the scoring
-    pipeline under "score_labels", test-time augmentation under "decode_views" / "flip_views")"""
+    pipeline under "score_labels", test-time augmentation under "decode_views" / "flip_views", sliding-window inference
+    under "window_crops" / "decode_windows")"""
     return int(_lib.hrseg_launch_count(None if family is None else family.encode(), int(reset)))
 
 

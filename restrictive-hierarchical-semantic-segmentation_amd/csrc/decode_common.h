@@ -1,5 +1,6 @@
-// What the two decode kernels share (decode.hip: one view, decode_views.hip: the mean logit of several views): the tile
-// shape, the bilinear taps of one output coordinate and the host-side validation and packing of the tree.
+// What the decode kernels share (decode.hip: one view, decode_views.hip: the mean logit of several views, windows.hip: the
+// blend of overlapping windows): the tile shape, the bilinear taps of one output coordinate, the arithmetic of a channel step and the
+// host-side validation and packing of the tree.
 #pragma once
 #include "common.h"
 
@@ -26,6 +27,34 @@ __device__ __forceinline__ DecLin dec_lin(int dst, float scale, int in) {
   r.l1 = lam;
   r.l0 = 1.f - lam;
   return r;
+}
+
+// The float arithmetic of a channel step, shared by decode_views.hip and windows.hip (contraction off: every unit rounds alike).
+// the 2 x 2 blend of one logit: along x first (taps p.0 / p.1 with weights lx0 / lx1), then along y
+__device__ __forceinline__ float dec_blend2(float p0, float p1, float l0, float l1) {      // one axis of it
+#pragma clang fp contract(off)
+  return __builtin_fmaf(p0, l0, p1 * l1);
+}
+__device__ __forceinline__ float dec_blend(float p00, float p01, float p10, float p11, float lx0, float lx1, float ly0, float ly1) {
+  return dec_blend2(dec_blend2(p00, p01, lx0, lx1), dec_blend2(p10, p11, lx0, lx1), ly0, ly1);
+}
+
+// one channel (index k, logit v) of a group's online arg-max and soft-max denominator
+__device__ __forceinline__ void dec_step(float v, int k, bool want_sum, float& best, float& sum, int& arg) {
+#pragma clang fp contract(off)
+  if (v > best) {                                           // strict: the lowest index wins ties (torch.argmax)
+    if (want_sum) sum = __builtin_fmaf(sum, expf(best - v), 1.f);
+    best = v;
+    arg = k;
+  } else if (want_sum) {
+    sum += v == best ? 1.f : expf(v - best);                // equal also covers -inf against -inf (no NaN)
+  }
+}
+
+// a group's confidence factor: its soft-max at the winner, or the sigmoid of the winner (level 0 of a tree model)
+__device__ __forceinline__ float dec_factor(bool want_sum, float best, float sum) {
+#pragma clang fp contract(off)
+  return want_sum ? 1.f / sum : 1.f / (1.f + expf(-best));
 }
 
 // Checks nlevels, C and the tree against the limits of include/hrseg.h and packs one dword per node into node[DEC_NODES]

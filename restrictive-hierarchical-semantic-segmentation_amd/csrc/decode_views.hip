@@ -25,30 +25,6 @@
 // one unflipped view is hrseg_decode_labels bit for bit and flipped copies of one logit set are too (tests/test_decode_views_gpu.py).
 #pragma clang fp contract(off)
 
-// the 2 x 2 blend of one logit: along x first (taps p.0 / p.1 with weights lx0 / lx1), then along y
-__device__ __forceinline__ float dec_blend(float p00, float p01, float p10, float p11, float lx0, float lx1, float ly0, float ly1) {
-  const float t0 = __builtin_fmaf(p00, lx0, p01 * lx1);
-  const float t1 = __builtin_fmaf(p10, lx0, p11 * lx1);
-  return __builtin_fmaf(t0, ly0, t1 * ly1);
-}
-
-// one channel (index k, logit v) of a group's online arg-max and soft-max denominator
-__device__ __forceinline__ void dec_step(float v, int k, bool want_sum, float& best, float& sum, int& arg) {
-  if (v > best) {                                           // strict: the lowest index wins ties (torch.argmax)
-    if (want_sum) sum = __builtin_fmaf(sum, expf(best - v), 1.f);
-    best = v;
-    arg = k;
-  } else if (want_sum) {
-    sum += v == best ? 1.f : expf(v - best);                // equal also covers -inf against -inf (no NaN)
-  }
-}
-
-// a group's confidence factor: its soft-max at the winner, or the sigmoid of the winner (level 0 of a tree model)
-__device__ __forceinline__ float dec_factor(bool want_sum, float best, float sum) {
-  return want_sum ? 1.f / sum : 1.f / (1.f + expf(-best));
-}
-
-
 #define DEC_VIEWS HRSEG_DECODE_MAX_VIEWS
 
 struct DecodeViewsArgs {

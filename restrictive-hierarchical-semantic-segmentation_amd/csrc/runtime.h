@@ -9,7 +9,8 @@
 // "ws_canvas" counts PROBLEMS laid out as a canvas inside ws / ws_group launches, "wgrad_sp_t5" the "wgrad_sp" launches that
 // used 80 x 80 tiles, the augment families (augment.hip) are the input pipeline's, "decode_labels" (decode.hip) the output
 // pipeline's, "score_labels" (score.hip) the scoring pipeline's, "decode_views" / "flip_views" (decode_views.hip) the
-// test-time-augmentation decode's and its input mirroring's.
+// test-time-augmentation decode's and its input mirroring's, "window_crops" / "decode_windows" (windows.hip) sliding-window
+// inference's crops and blend-decode.
 #define HRSEG_FAMILIES(X)                   \
   X(WS, "ws", 1)                            \
   X(WS_GROUP, "ws_group", 1)                \
@@ -34,7 +35,9 @@
   X(DECODE_LABELS, "decode_labels", 0)      \
   X(SCORE_LABELS, "score_labels", 0)        \
   X(DECODE_VIEWS, "decode_views", 0)        \
-  X(FLIP_VIEWS, "flip_views", 0)
+  X(FLIP_VIEWS, "flip_views", 0)          \
+  X(WINDOW_CROPS, "window_crops", 0)      \
+  X(DECODE_WINDOWS, "decode_windows", 0)
 #define HRSEG_X(id, name, conv) CNT_##id,
 enum { HRSEG_FAMILIES(HRSEG_X) CNT_N };
 #undef HRSEG_X

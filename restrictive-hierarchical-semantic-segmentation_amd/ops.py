@@ -763,6 +763,121 @@ def decode_views(views, tables, desc, desc_host, want_confidence=False):
     return labels, conf
 
 
+WINDOW_MAX_ORIGINS, WINDOW_MAX_COVER = 64, 3
+
+
+def check_window_axis(what, origins, n, S):
+    """the rules of include/hrseg.h on the window origins along one canvas axis of length n (ValueError otherwise)"""
+    o = [int(v) for v in origins]
+    if not 1 <= len(o) <= WINDOW_MAX_ORIGINS:
+        raise ValueError(f"{what}: {len(o)} window origins, supported 1..{WINDOW_MAX_ORIGINS}")
+    if o[0] != 0 or o[-1] != n - S:
+        raise ValueError(f"{what}: window origins {o[0]}..{o[-1]} do not run from 0 to {n} - {S}")
+    for k in range(1, len(o)):
+        if not o[k - 1] < o[k] <= o[k - 1] + S:
+            raise ValueError(f"{what}: window origins {o[k - 1]}, {o[k]} are not increasing in steps of at most {S}")
+    for k in range(len(o) - WINDOW_MAX_COVER):
+        if o[k + WINDOW_MAX_COVER] < o[k] + S:
+            raise ValueError(f"{what}: more than {WINDOW_MAX_COVER} windows cover coordinate {o[k + WINDOW_MAX_COVER]}")
+
+
+def check_window_plan(what, plan, B, S):
+    """a Data.decode.WindowPlan (or anything with its host tables `wdesc` [B,8] int64, `origins` int32, `nwindows`, `S`)
+    against the rules of include/hrseg.h for B images and windows of S x S (ValueError otherwise; needs no GPU)"""
+    if not 1 <= int(S) <= DECODE_MAX_SIZE:
+        raise ValueError(f"{what}: window size {S}, supported 1..{DECODE_MAX_SIZE}")
+    if int(plan.S) != int(S):
+        raise ValueError(f"{what}: the plan was made for windows of {plan.S}, not {S}")
+    wdesc, origins, N = plan.wdesc, plan.origins, int(plan.nwindows)
+    if not (torch.is_tensor(wdesc) and wdesc.dtype == torch.int64 and not wdesc.is_cuda and tuple(wdesc.shape) == (B, 8)):
+        raise ValueError(f"{what}: the window table must be a [{B},8] int64 host tensor")
+    if not (torch.is_tensor(origins) and origins.dtype == torch.int32 and not origins.is_cuda and origins.dim() == 1):
+        raise ValueError(f"{what}: the window origins must be a 1-D int32 host tensor")
+    if N < B:
+        raise ValueError(f"{what}: {N} windows for {B} images")
+    org = origins.tolist()
+    for m, (Hc, Wc, ny, nx, n0, oo, _, _) in enumerate(wdesc.tolist()):
+        if Hc < S or Wc < S:
+            raise ValueError(f"{what}: image {m} has a {Hc}x{Wc} canvas, smaller than a window of {S}")
+        if not (1 <= ny <= WINDOW_MAX_ORIGINS and 1 <= nx <= WINDOW_MAX_ORIGINS):
+            raise ValueError(f"{what}: image {m} has {ny}x{nx} windows, supported 1..{WINDOW_MAX_ORIGINS} per axis")
+        if oo < 0 or oo + ny + nx > len(org):
+            raise ValueError(f"{what}: the origins of image {m} ([{oo}, {oo + ny + nx})) lie outside the table of {len(org)}")
+        if n0 < 0 or n0 + ny * nx > N:
+            raise ValueError(f"{what}: windows [{n0}, {n0 + ny * nx}) of image {m} are not inside the {N} windows")
+        check_window_axis(f"{what}: image {m} rows", org[oo:oo + ny], Hc, S)
+        check_window_axis(f"{what}: image {m} columns", org[oo + ny:oo + ny + nx], Wc, S)
+
+
+def _window_tables(plan, device):
+    """the plan's two tables on the device (copied on every call, as the decode tables are read afresh on every call)"""
+    return plan.wdesc.to(device), plan.origins.to(device)
+
+
+def window_crops(src, desc, desc_host, plan, S):
+    """packed uint8 sources + [B,4] descriptors (device, and their host copy) + a window plan -> x [N,3,S,S] fp32: window n
+    is the eval-mode resize of its image to the plan's canvas, cut at the window's origin (what augment_image(..., False)
+    gives where the canvas is one window).  One launch, no synchronisation."""
+    _check_ragged(src, desc, desc_host, (1, 3))
+    B = desc.shape[0]
+    check_window_plan("window_crops", plan, B, S)
+    wdesc, origins = _window_tables(plan, src.device)
+    x = torch.empty((int(plan.nwindows), 3, S, S), dtype=torch.float32, device=src.device)
+    call("hrseg_window_crops", ptr(src), ptr(desc), ptr(wdesc), ptr(origins), ptr(x), B, int(S), int(plan.nwindows))
+    return x
+
+
+def check_window_profile(what, profile, S):
+    """the blend profile: S finite, strictly positive fp32 weights (validated on the host: a device tensor is copied back)"""
+    if not (torch.is_tensor(profile) and profile.dtype == torch.float32 and tuple(profile.shape) == (S,)):
+        raise ValueError(f"{what}: the blend profile must be a fp32 tensor of {S} entries")
+    host = profile.detach().cpu()
+    if not bool((torch.isfinite(host) & (host > 0)).all()):
+        raise ValueError(f"{what}: the blend profile must be finite and strictly positive")
+
+
+def decode_windows(logits, tables, plan, profile, desc, desc_host, want_confidence=False):
+    """decode_labels on the blend of overlapping windows: per-level logits [N,C_L,S,S] of the plan's N windows (fp32 device
+    tensors, or one tensor), a Data.decode.WindowPlan, the blend profile (S positive fp32 weights) and [B,4] label
+    descriptors of the wanted sizes -> (packed uint8 labels, packed fp32 confidence or None) as decode_labels returns
+    them.  No canvas-size tensor is built.  One launch, no synchronisation."""
+    logits = [logits] if torch.is_tensor(logits) else list(logits)
+    check_decode_tables(tables)
+    if len(logits) != len(tables.C):
+        raise ValueError(f"decode_windows: {len(logits)} logit levels for a {len(tables.C)}-level table")
+    if logits[0].dim() != 4:
+        raise ValueError(f"decode_windows: level 0 logits of shape {tuple(logits[0].shape)}, expected 4 dimensions")
+    N, S = logits[0].shape[0], logits[0].shape[2]
+    for L, z in enumerate(logits):
+        if z.dim() != 4 or tuple(z.shape) != (N, tables.C[L], S, S):
+            raise ValueError(f"decode_windows: level {L} logits of shape {tuple(z.shape)}, expected {(N, tables.C[L], S, S)}")
+        if not z.is_cuda or z.dtype != torch.float32:
+            raise ValueError(f"decode_windows: level {L}: logits must be fp32 device tensors")
+    if not torch.is_tensor(desc_host) or desc_host.dim() != 2 or desc_host.shape[1] != 4:
+        raise ValueError("decode_windows: the host descriptor table must be [B,4] int64")
+    B = desc_host.shape[0]
+    if desc.dtype != torch.int64 or not desc.is_cuda or tuple(desc.shape) != (B, 4):
+        raise ValueError(f"decode_windows: the descriptor tables must be [{B},4] int64, one on the device and its host copy")
+    check_window_plan("decode_windows", plan, B, S)
+    if int(plan.nwindows) != N:
+        raise ValueError(f"decode_windows: logits of {N} windows for a plan of {plan.nwindows}")
+    check_window_profile("decode_windows", profile, S)
+    rows = desc_host.tolist()
+    n = sum(H * W for _, H, W, _ in rows)
+    for off, H, W, ch in rows:
+        if ch != 1 or H < 1 or W < 1 or off < 0 or off + H * W > n:
+            raise ValueError(f"ragged descriptor (offset {off}, {H}x{W}, {ch} channels) does not fit a {n}-byte label buffer")
+    logits = [_c(z) for z in logits]
+    device = logits[0].device
+    wdesc, origins = _window_tables(plan, device)
+    profile = _c(profile.to(device))
+    labels = torch.empty(n, dtype=torch.uint8, device=device)
+    conf = torch.empty(n, dtype=torch.float32, device=device) if want_confidence else None
+    call("hrseg_decode_windows", len(logits), _lib.ptr_array(logits), _lib.int_array(list(tables.C)),
+         C.byref(_decode_tree_struct(tables)), ptr(wdesc), ptr(origins), ptr(profile), ptr(desc), ptr(labels), ptr(conf), B, S, N)
+    return labels, conf
+
+
 SCORE_MAX_LEVELS, SCORE_MAX_CHANNELS, SCORE_MAX_TOTAL = 8, 16, 64
 # pixels a lane / a wave / a block of hrseg_score_labels takes per step (HRSEG_SCORE_*_STEP of include/hrseg.h): the sizes
 # around which the kernel changes path

@@ -10,6 +10,8 @@ prediction prep, metrics, the PNG dump and metrics.csv -- is below; only the CLI
 """
 from __future__ import annotations
 
+import math
+
 import torch
 
 from . import ops
@@ -206,6 +208,49 @@ class TestTimeAugment:
         return out
 
 
+class SlidingWindow:
+    """Tiled inference at (or near) the sources' own resolution: the network runs on overlapping network-size windows of a
+    canvas of each image and the windows' logits are blended where they overlap (include/hrseg.h, sliding-window inference).
+    `plan(sizes, S)` lays the windows out on the host (Data.decode.WindowPlan; no GPU):
+      canvas of an image (H, W): Hc = max(S, int(round(H * scale))), Wc likewise -- an image smaller than a window is
+        enlarged to one;
+      stride = S - floor(overlap * S) with 0 <= overlap <= 0.5, so stride >= ceil(S / 2) and every canvas row or column is
+        covered by at least 1 and at most 3 windows per axis (at most two regular origins lie in any half-open span of
+        length S, plus the last window, which is shifted back to end at the edge);
+      blend: "hann" (weights 0.5 - 0.5 cos(2 pi (i + 0.5) / S), strictly positive in fp32) or "uniform" (a plain mean).
+    window_batch: windows per eval-mode forward of a Predictor."""
+
+    def __init__(self, overlap=0.5, scale=1.0, blend="hann", window_batch=8):
+        self.overlap, self.scale, self.blend, self.window_batch = float(overlap), float(scale), blend, int(window_batch)
+        if not 0.0 <= self.overlap <= 0.5:
+            raise ValueError(f"SlidingWindow: overlap {overlap} not in 0..0.5")
+        if not (self.scale > 0.0 and self.scale != float("inf")):
+            raise ValueError(f"SlidingWindow: scale {scale} must be positive")
+        if blend not in ("hann", "uniform"):
+            raise ValueError(f"SlidingWindow: blend '{blend}', supported 'hann' and 'uniform'")
+        if self.window_batch < 1:
+            raise ValueError(f"SlidingWindow: window_batch {window_batch} must be at least 1")
+
+    def stride(self, S):
+        return int(S) - int(math.floor(self.overlap * int(S)))
+
+    def canvas(self, H, W, S):
+        return max(int(S), int(round(H * self.scale))), max(int(S), int(round(W * self.scale)))
+
+    def profile(self, S):
+        from .Data.decode import window_profile
+        return window_profile(S, self.blend)
+
+    def plan(self, sizes, S):
+        from .Data.decode import plan_windows
+        S = int(S)
+        if not 1 <= S <= ops.DECODE_MAX_SIZE:
+            raise ValueError(f"SlidingWindow: window size {S}, supported 1..{ops.DECODE_MAX_SIZE}")
+        plan = plan_windows([self.canvas(H, W, S) for H, W in sizes], S, self.stride(S))
+        ops.check_window_plan("SlidingWindow", plan, len(plan), S)       # (e.g. more than 64 windows along an axis)
+        return plan
+
+
 class Predictor:
     """Deployment-side inference: `labels = Predictor(model, class_tree, class_map, args)(images)` with a list of ragged
     uint8 HxW / HxWx3 sources (or a RaggedBatch) -> RaggedLabels, one label map per source at the source's own size.
@@ -218,9 +263,14 @@ class Predictor:
     tta=TestTimeAugment(...): per scale one eval-mode resize to S, ops.flip_views and ONE forward of all the scale's
     flip views as a batch (eval-mode BatchNorm uses the running statistics: samples do not interact), then one
     decode of the mean logit over all views (Data.DeviceDecode.decode_views); keep_logits=True then keeps
-    `last_view_logits`, the list of (logits, flags) the decode read.  tta=None: exactly the calls described above."""
+    `last_view_logits`, the list of (logits, flags) the decode read.  tta=None: exactly the calls described above.
+    window=SlidingWindow(...): the windows are planned from the source sizes, cut by ONE ops.window_crops launch, run
+    through eval-mode forwards of `window_batch` windows at a time (the last chunk shorter; eval-mode BatchNorm: windows do
+    not interact) and their per-level logits, gathered into [N,C_L,S,S], are blended and decoded by ONE
+    Data.DeviceDecode.decode_windows launch at the sizes asked for; keep_logits=True then keeps `last_window_logits` =
+    (logits, plan).  window=None: exactly the calls described above.  window together with tta is refused."""
 
-    def __init__(self, model, class_tree, class_map, args, want_confidence=False, keep_logits=False, tta=None):
+    def __init__(self, model, class_tree, class_map, args, want_confidence=False, keep_logits=False, tta=None, window=None):
         from .Data.decode import DeviceDecode
         self.model, self.class_tree, self.class_map, self.args = model, class_tree, class_map, args
         self.scorer, self.last_labels = None, None
@@ -232,6 +282,12 @@ class Predictor:
         self.tta, self.last_view_logits = tta, None
         if tta is not None:
             tta.views(self.size)                    # refuses sizes the decode cannot take before any image is seen
+        self.window, self.last_window_logits = window, None
+        if window is not None:
+            if tta is not None:
+                raise ValueError("Predictor: window together with tta is not supported")
+            self.window_profile = window.profile(self.size)
+            window.plan([], self.size)              # refuses a window size the decode cannot take before any image is seen
 
     def __call__(self, images):
         return self._predict(images, None)
@@ -273,9 +329,17 @@ class Predictor:
         src, desc = src.to(device, non_blocking=True), desc.to(device, non_blocking=True)
         was_training = self.model.training
         self.model.eval()
-        views = []
+        views, plan = [], None
         try:
-            if self.tta is None:
+            if self.window is not None:
+                plan = self.window.plan([(H, W) for _, H, W, _ in desc_host.tolist()], self.size)
+                x = ops.window_crops(src, desc, desc_host, plan, self.size)
+                chunks = []
+                for i in range(0, plan.nwindows, self.window.window_batch):
+                    _, z = T._model_call(self.model, x[i:i + self.window.window_batch], self.args, self.class_tree)
+                    chunks.append([z] if torch.is_tensor(z) else list(z))
+                output_logits = [torch.cat(level) if len(level) > 1 else level[0] for level in zip(*chunks)]
+            elif self.tta is None:
                 x = ops.augment_image(src, desc, desc_host, None, self.size, False)
                 _, output_logits = T._model_call(self.model, x, self.args, self.class_tree)
             else:
@@ -290,6 +354,9 @@ class Predictor:
         finally:
             self.model.train(was_training)
         ldesc = label_desc([(H, W) for _, H, W, _ in desc_host.tolist()] if sizes is None else sizes)
+        if self.window is not None:
+            self.last_window_logits = (output_logits, plan) if self.keep_logits else None
+            return self.decoder.decode_windows(output_logits, plan, self.window_profile, ldesc, None, self.want_confidence)
         if self.tta is not None:
             self.last_view_logits = views if self.keep_logits else None
             return self.decoder.decode_views(views, ldesc, None, self.want_confidence)
