@@ -506,6 +506,28 @@ int hrseg_grad_clip_finalize(const double* partial, int nchunks, const float* hy
 int hrseg_adamw_dev_clip(float* p, const float* g, float* m, float* v, long n, const float* hyper,
                          const float* state, const float* clipcfg, const float* clip, hrseg_stream_t stream);
 
+/* ------------------------------------------------------------------ weight EMA (exponential moving average)
+ * A shadow e[n] of the flat parameter buffer, advanced once per optimizer step in fp32:
+ *   t = s - s0 - 1;  eff = warmup ? min(d, (1 + t) / (10 + t)) : d;  alpha = 1 - eff;  e = e + (p' - e) * alpha
+ * p' = the parameter AFTER this step's AdamW update, s = state[0] after this step's tick, and the device buffer
+ * emacfg = {d = decay, warmup (0 or 1), s0 = the value of state[0] when averaging began}: t counts the updates already
+ * done, taken from AdamW's own step counter (a void step advances neither).  The product and the sum are one fused
+ * multiply-add, fma(p' - e, alpha, e), in every kernel below, so they agree bit for bit.
+ * hrseg_adamw_dev_ema is hrseg_adamw_dev (state advanced by one step) and hrseg_adamw_dev_clip_ema is hrseg_adamw_dev_clip
+ * (state advanced by hrseg_grad_clip_finalize; a void step leaves e untouched as well) with the line above appended per
+ * element: p, m, v come out bit-identical to those entry points, e costs one more 16-byte load and store per four
+ * elements and no launch.  hrseg_ema_update is the line alone, for a p that has its step behind it.  hrseg_swap
+ * exchanges the contents of two flat fp32 buffers that do not overlap (the shadow and the parameters: addresses held
+ * elsewhere stay valid).  Every buffer 16-byte aligned; e a buffer of its own. */
+int hrseg_adamw_dev_ema(float* p, const float* g, float* m, float* v, float* e, long n, const float* hyper,
+                        float* state, const float* emacfg, hrseg_stream_t stream);
+int hrseg_adamw_dev_clip_ema(float* p, const float* g, float* m, float* v, float* e, long n, const float* hyper,
+                             const float* state, const float* clipcfg, const float* clip, const float* emacfg,
+                             hrseg_stream_t stream);
+int hrseg_ema_update(float* e, const float* p, long n, const float* state, const float* emacfg,
+                     hrseg_stream_t stream);
+int hrseg_swap(float* a, float* b, long n, hrseg_stream_t stream);
+
 /* ------------------------------------------------------------------ gradient exchange (data parallelism)
  * Thin wrappers over RCCL for the one collective of the path: the in-place sum of a flat fp32 gradient
  * bucket over the ranks (replaces nn.DataParallel's reduce-add, train.py:509-510).  librccl.so is opened

@@ -128,6 +128,10 @@ PROTOTYPES = {
     "hrseg_grad_sumsq": [_p, _l, _p, _i, _p],
     "hrseg_grad_clip_finalize": [_p, _i, _p, _p, _p, _p, _p],
     "hrseg_adamw_dev_clip": [_p, _p, _p, _p, _l, _p, _p, _p, _p, _p],
+    "hrseg_adamw_dev_ema": [_p, _p, _p, _p, _p, _l, _p, _p, _p, _p],
+    "hrseg_adamw_dev_clip_ema": [_p, _p, _p, _p, _p, _l, _p, _p, _p, _p, _p, _p],
+    "hrseg_ema_update": [_p, _p, _l, _p, _p, _p],
+    "hrseg_swap": [_p, _p, _l, _p],
     "hrseg_encode_targets": [_p, _p, C.POINTER(C.c_int), _p, _i, _i, _l, _p],
     "hrseg_augment_image": [_p, _p, _p, _p, _i, _i, _i, _p, C.c_size_t, _p],
     "hrseg_augment_targets": [_p, _p, _p, C.POINTER(C.c_int), _p, _p, _i, _i, _i, _i, _i, _p, C.c_size_t, _p],

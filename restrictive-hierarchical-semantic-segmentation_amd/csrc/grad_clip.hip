@@ -13,6 +13,10 @@
 // whatever the "deterministic" knob says.  Every element is widened to fp64 BEFORE it is squared, so a finite fp32
 // gradient can neither overflow nor underflow the sum (|g| <= 3.4e38 -> g^2 <= 1.2e77, n <= 2^63; the smallest
 // subnormal squared is 2e-90), and S is finite exactly when every element is.
+//
+// Weight EMA (second half of this file): the shadow e[n] of the parameters is advanced by the update kernel itself
+// (adamw_dev_ema_kernel / adamw_dev_clip_ema_kernel: one more 16-byte load and store per element group, no launch of
+// its own), by ema_update_kernel for an already updated p, and exchanged with p by swap_kernel.
 #include "common.h"
 
 #define GRAD_CHUNK 8192          // floats per partial: 256 threads x 8 pieces of 16 bytes
@@ -100,13 +104,27 @@ __global__ __launch_bounds__(256) void grad_clip_finalize_kernel(const double* _
   }
 }
 
+// emacfg = {decay, warmup (0 or 1), s0}; state[0] = s, the step count AFTER this step's tick.  t = s - s0 - 1 updates of
+// the shadow have been done; eff = warmup ? min(d, (1 + t) / (10 + t)) : d; -> alpha = 1 - eff.  All counts are small
+// integers held exactly in fp32.  Evaluated once per thread from grid-uniform scalars.
+__device__ __forceinline__ float ema_alpha(const float* __restrict__ state, const float* __restrict__ emacfg) {
+  const float d = emacfg[0], t = state[0] - emacfg[2] - 1.f;
+  const float eff = (emacfg[1] != 0.f) ? fminf(d, (1.f + t) / (10.f + t)) : d;
+  return 1.f - eff;
+}
+// e + (p' - e) * alpha, the product and the sum as ONE fused multiply-add -- spelled out, so that the fused update
+// kernels and ema_update_kernel round alike whatever the compiler would contract on its own.
+__device__ __forceinline__ float ema_line(float e, float p, float alpha) { return __builtin_fmaf(p - e, alpha, e); }
+
 // One element group of the update.  CLIP = false is, expression by expression, the body of adamw_dev_kernel
-// (bn_elem.hip), so that a step whose coef is exactly 1 rounds exactly as that kernel does.
-template <bool CLIP>
+// (bn_elem.hip), so that a step whose coef is exactly 1 rounds exactly as that kernel does.  EMA = true appends the shadow's
+// update on the p' just computed (still in its registers); p, m, v are computed and stored as with EMA = false.
+template <bool CLIP, bool EMA = false>
 __device__ __forceinline__ void adamw_clip_body(float* __restrict__ p, const float* __restrict__ g,
                                                 float* __restrict__ m, float* __restrict__ v, long n4, long n, float lr,
                                                 float b1, float b2, float eps, float wd, float gscale, float coef,
-                                                float step, float rsqrt_bc2) {
+                                                float step, float rsqrt_bc2, float* __restrict__ e = nullptr,
+                                                float alpha = 0.f) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
     f32x4 pp = gc_ld4(p + 4 * i), gg = gc_ld4(g + 4 * i) * gscale, mm = gc_ld4(m + 4 * i), vv = gc_ld4(v + 4 * i);
     if (CLIP) gg = gg * coef;
@@ -118,13 +136,25 @@ __device__ __forceinline__ void adamw_clip_body(float* __restrict__ p, const flo
     gc_st4(p + 4 * i, pp);
     gc_st4(m + 4 * i, mm);
     gc_st4(v + 4 * i, vv);
+    if (EMA) {
+      f32x4 ee = gc_ld4(e + 4 * i);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) ee[j] = ema_line(ee[j], pp[j], alpha);
+      gc_st4(e + 4 * i, ee);
+    }
   }
   if (blockIdx.x == 0 && threadIdx.x < (n - 4 * n4)) {
     const long i = 4 * n4 + threadIdx.x;
     float pp = p[i] * (1.f - lr * wd), gg = g[i] * gscale;
     if (CLIP) gg = gg * coef;
     const float mm = m[i] + (gg - m[i]) * (1.f - b1), vv = v[i] * b2 + gg * gg * (1.f - b2);
-    p[i] = pp - step * mm / (sqrtf(vv) * rsqrt_bc2 + eps);
+    if (EMA) {
+      pp = pp - step * mm / (sqrtf(vv) * rsqrt_bc2 + eps);
+      p[i] = pp;
+      e[i] = ema_line(e[i], pp, alpha);
+    } else {
+      p[i] = pp - step * mm / (sqrtf(vv) * rsqrt_bc2 + eps);
+    }
     m[i] = mm;
     v[i] = vv;
   }
@@ -142,6 +172,87 @@ __global__ __launch_bounds__(256) void adamw_dev_clip_kernel(float* __restrict__
   if (coef == 1.f) adamw_clip_body<false>(p, g, m, v, n4, n, lr, b1, b2, eps, wd, gscale, coef, step, rsqrt_bc2);
   else adamw_clip_body<true>(p, g, m, v, n4, n, lr, b1, b2, eps, wd, gscale, coef, step, rsqrt_bc2);
 }
+
+// --------------------------------------------------------------------------- weight EMA
+// adam_tick_kernel of bn_elem.hip (kernels are not visible across translation units): the same expressions on the same types
+__global__ void adam_tick_ema_kernel(float* state, const float* hyper) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    const double step = (double)state[0] + 1.0;
+    state[0] = (float)step;
+    state[1] = (float)(1.0 - pow((double)hyper[1], step));
+    state[2] = (float)(1.0 / sqrt(1.0 - pow((double)hyper[2], step)));
+  }
+}
+
+__global__ __launch_bounds__(256) void adamw_dev_ema_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                            float* __restrict__ m, float* __restrict__ v,
+                                                            float* __restrict__ e, long n4, long n,
+                                                            const float* __restrict__ hyper,
+                                                            const float* __restrict__ state,
+                                                            const float* __restrict__ emacfg) {
+  const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4], gscale = hyper[5];
+  const float step = lr / state[1], rsqrt_bc2 = state[2];
+  adamw_clip_body<false, true>(p, g, m, v, n4, n, lr, b1, b2, eps, wd, gscale, 1.f, step, rsqrt_bc2, e,
+                               ema_alpha(state, emacfg));
+}
+
+__global__ __launch_bounds__(256) void adamw_dev_clip_ema_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                                 float* __restrict__ m, float* __restrict__ v,
+                                                                 float* __restrict__ e, long n4, long n,
+                                                                 const float* __restrict__ hyper,
+                                                                 const float* __restrict__ state,
+                                                                 const float* __restrict__ clipcfg,
+                                                                 const float* __restrict__ clip,
+                                                                 const float* __restrict__ emacfg) {
+  if (clipcfg[1] != 0.f && clip[2] == 0.f) return;      // void step: p, m, v AND e stay as they are (grid-uniform)
+  const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4], gscale = hyper[5];
+  const float step = lr / state[1], rsqrt_bc2 = state[2], coef = clip[1];
+  const float alpha = ema_alpha(state, emacfg);
+  if (coef == 1.f) adamw_clip_body<false, true>(p, g, m, v, n4, n, lr, b1, b2, eps, wd, gscale, coef, step, rsqrt_bc2, e, alpha);
+  else adamw_clip_body<true, true>(p, g, m, v, n4, n, lr, b1, b2, eps, wd, gscale, coef, step, rsqrt_bc2, e, alpha);
+}
+
+// the shadow's update alone, for a p that has its step behind it (state already advanced)
+__global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ e, const float* __restrict__ p, long n4, long n,
+                                                         const float* __restrict__ state,
+                                                         const float* __restrict__ emacfg) {
+  const float alpha = ema_alpha(state, emacfg);
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    f32x4 ee = gc_ld4(e + 4 * i);
+    const f32x4 pp = gc_ld4(p + 4 * i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ee[j] = ema_line(ee[j], pp[j], alpha);
+    gc_st4(e + 4 * i, ee);
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n - 4 * n4)) {
+    const long i = 4 * n4 + threadIdx.x;
+    e[i] = ema_line(e[i], p[i], alpha);
+  }
+}
+
+// a <-> b, contents not pointers: whoever holds either address (a recorded launch tape) keeps a valid one
+__global__ __launch_bounds__(256) void swap_kernel(float* __restrict__ a, float* __restrict__ b, long n4, long n) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    const f32x4 aa = gc_ld4(a + 4 * i), bb = gc_ld4(b + 4 * i);
+    gc_st4(a + 4 * i, bb);
+    gc_st4(b + 4 * i, aa);
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n - 4 * n4)) {
+    const long i = 4 * n4 + threadIdx.x;
+    const float aa = a[i], bb = b[i];
+    a[i] = bb;
+    b[i] = aa;
+  }
+}
+
+// 256 threads x 16 bytes, at most 8192 blocks (the grid of the AdamW kernels); n < 4: one block for the tail
+static inline int flat_blocks(long n4) {
+  long blocks = (n4 + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  if (blocks < 1) blocks = 1;
+  return (int)blocks;
+}
+static inline bool al16(const void* q) { return (uintptr_t)q % 16 == 0; }
 
 // --------------------------------------------------------------------------- entry points
 extern "C" int hrseg_grad_sumsq_chunk_len(void) { return GRAD_CHUNK; }
@@ -187,5 +298,55 @@ extern "C" int hrseg_adamw_dev_clip(float* p, const float* g, float* m, float* v
   hipLaunchKernelGGL(adamw_dev_clip_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4, n, hyper,
                      state, clipcfg, clip);
   HRSEG_LAUNCH_CHECK("adamw_dev_clip");
+  return 0;
+}
+
+extern "C" int hrseg_adamw_dev_ema(float* p, const float* g, float* m, float* v, float* e, long n, const float* hyper,
+                                   float* state, const float* emacfg, hrseg_stream_t stream) {
+  HRSEG_CHECK_ARG(p && g && m && v && e && hyper && state && emacfg && n > 0, "hrseg_adamw_dev_ema: bad arguments");
+  HRSEG_CHECK_ARG(al16(p) && al16(g) && al16(m) && al16(v) && al16(e), "hrseg_adamw_dev_ema: buffers must be 16-byte aligned");
+  HRSEG_CHECK_ARG(e != p && e != g && e != m && e != v, "hrseg_adamw_dev_ema: the shadow must be a buffer of its own");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(adam_tick_ema_kernel, dim3(1), dim3(64), 0, st, state, hyper);
+  HRSEG_LAUNCH_CHECK("adam_tick_ema");
+  const long n4 = n / 4;
+  hipLaunchKernelGGL(adamw_dev_ema_kernel, dim3(flat_blocks(n4)), dim3(256), 0, st, p, g, m, v, e, n4, n, hyper, state, emacfg);
+  HRSEG_LAUNCH_CHECK("adamw_dev_ema");
+  return 0;
+}
+
+extern "C" int hrseg_adamw_dev_clip_ema(float* p, const float* g, float* m, float* v, float* e, long n, const float* hyper,
+                                        const float* state, const float* clipcfg, const float* clip, const float* emacfg,
+                                        hrseg_stream_t stream) {
+  HRSEG_CHECK_ARG(p && g && m && v && e && hyper && state && clipcfg && clip && emacfg && n > 0,
+                  "hrseg_adamw_dev_clip_ema: bad arguments");
+  HRSEG_CHECK_ARG(al16(p) && al16(g) && al16(m) && al16(v) && al16(e),
+                  "hrseg_adamw_dev_clip_ema: buffers must be 16-byte aligned");
+  HRSEG_CHECK_ARG(e != p && e != g && e != m && e != v, "hrseg_adamw_dev_clip_ema: the shadow must be a buffer of its own");
+  const long n4 = n / 4;
+  hipLaunchKernelGGL(adamw_dev_clip_ema_kernel, dim3(flat_blocks(n4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, e, n4, n,
+                     hyper, state, clipcfg, clip, emacfg);
+  HRSEG_LAUNCH_CHECK("adamw_dev_clip_ema");
+  return 0;
+}
+
+extern "C" int hrseg_ema_update(float* e, const float* p, long n, const float* state, const float* emacfg,
+                                hrseg_stream_t stream) {
+  HRSEG_CHECK_ARG(e && p && state && emacfg && n > 0, "hrseg_ema_update: bad arguments");
+  HRSEG_CHECK_ARG(al16(e) && al16(p), "hrseg_ema_update: buffers must be 16-byte aligned");
+  HRSEG_CHECK_ARG(e != p, "hrseg_ema_update: the shadow must be a buffer of its own");
+  const long n4 = n / 4;
+  hipLaunchKernelGGL(ema_update_kernel, dim3(flat_blocks(n4)), dim3(256), 0, (hipStream_t)stream, e, p, n4, n, state, emacfg);
+  HRSEG_LAUNCH_CHECK("ema_update");
+  return 0;
+}
+
+extern "C" int hrseg_swap(float* a, float* b, long n, hrseg_stream_t stream) {
+  HRSEG_CHECK_ARG(a && b && n > 0, "hrseg_swap: bad arguments");
+  HRSEG_CHECK_ARG(al16(a) && al16(b), "hrseg_swap: buffers must be 16-byte aligned");
+  HRSEG_CHECK_ARG(a + n <= b || b + n <= a, "hrseg_swap: the buffers overlap");
+  const long n4 = n / 4;
+  hipLaunchKernelGGL(swap_kernel, dim3(flat_blocks(n4)), dim3(256), 0, (hipStream_t)stream, a, b, n4, n);
+  HRSEG_LAUNCH_CHECK("swap");
   return 0;
 }

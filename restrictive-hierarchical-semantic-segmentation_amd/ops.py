@@ -1260,3 +1260,28 @@ def adamw_dev_clip(p, g, m, v, hyper, state, clipcfg, clip):
     """adamw_dev with the gradient scaled by clip's coefficient, or nothing at all on a void step; `state` was advanced
     by grad_clip_finalize"""
     call("hrseg_adamw_dev_clip", ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), ptr(hyper), ptr(state), ptr(clipcfg), ptr(clip))
+
+
+def adamw_dev_ema(p, g, m, v, e, hyper, state, emacfg):
+    """adamw_dev that also advances the weight average e (emacfg = {decay, warmup, s0}; see hrseg.h): p, m, v bitwise as
+    from adamw_dev, no extra launch"""
+    call("hrseg_adamw_dev_ema", ptr(p), ptr(g), ptr(m), ptr(v), ptr(e), p.numel(), ptr(hyper), ptr(state), ptr(emacfg))
+
+
+def adamw_dev_clip_ema(p, g, m, v, e, hyper, state, clipcfg, clip, emacfg):
+    """adamw_dev_clip that also advances the weight average e; a void step leaves e alone too"""
+    call("hrseg_adamw_dev_clip_ema", ptr(p), ptr(g), ptr(m), ptr(v), ptr(e), p.numel(), ptr(hyper), ptr(state), ptr(clipcfg),
+         ptr(clip), ptr(emacfg))
+
+
+def ema_update(e, p, state, emacfg):
+    """the weight average's update alone, for parameters p whose step is done (`state` already advanced): bitwise the e
+    of the fused kernels"""
+    call("hrseg_ema_update", ptr(e), ptr(p), p.numel(), ptr(state), ptr(emacfg))
+
+
+def swap(a, b):
+    """exchange the contents of two flat fp32 buffers in place (hrseg_swap)"""
+    if a.numel() != b.numel():
+        raise ValueError(f"ops.swap: {a.numel()} vs {b.numel()} elements")
+    call("hrseg_swap", ptr(a), ptr(b), a.numel())

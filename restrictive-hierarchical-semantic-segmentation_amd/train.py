@@ -15,6 +15,7 @@ Dataset / checkpoint / CSV orchestration (build, train, main) is out of scope
 """
 from __future__ import annotations
 
+import contextlib
 import time
 
 import numpy as np
@@ -42,10 +43,23 @@ class FusedAdamW(torch.optim.Optimizer):
     ``skip_nonfinite``: a step whose gradient holds a NaN or an infinity is void -- parameters, moments and the step
     count stay bitwise as they were and ``skipped_steps`` goes up by one.
     Either option makes the step three launches (sum of squares, finalize + step count, update); ``grad_stats`` is the
-    device tensor {norm, coef, finite, skipped_total} of the latest step."""
+    device tensor {norm, coef, finite, skipped_total} of the latest step.
+
+    ``ema_decay`` (default None: off, the step makes exactly the calls it made without it): an exponential moving average
+    of the parameters, kept in a shadow buffer with the model's own flat layout and advanced by the update kernel itself
+    -- no launch of its own, on either path above.  After every step, in fp32: e += (p' - e) * (1 - eff), p' the updated
+    parameter, eff = ema_decay, or with ``ema_warmup`` (default on) min(ema_decay, (1 + t) / (10 + t)) with t the number
+    of averaged steps so far.  t comes from AdamW's own device step counter, so a void step leaves the average and its
+    warm-up alone.  The shadow starts as a copy of the parameters at the first step (or ``_moments()``) with averaging on.
+    Parameters only: BatchNorm running statistics are not averaged (they are a momentum average already); evaluated
+    with the averaged weights the model uses its live running statistics, as
+    torch.optim.swa_utils.AveragedModel(use_buffers=False) does.  ``optimizer.ema_decay = x`` between steps is written to
+    device memory and holds from the next step on, recorded tape or captured graph included (None <-> a number switches
+    the path and re-records).  ``with optimizer.ema_parameters(): ...`` runs the model on the averaged weights;
+    ``ema_state_dict()`` / ``load_ema_state_dict()`` move them in the model's state_dict format."""
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None,
-                 skip_nonfinite=False):
+                 skip_nonfinite=False, ema_decay=None, ema_warmup=True):
         if isinstance(lr, (list, tuple)):          # the reference passes eval("[1e-4]")
             lr = lr[0]
         self.model = model
@@ -62,6 +76,112 @@ class FusedAdamW(torch.optim.Optimizer):
         self.grad_stats = None              # device {norm, coef, finite, skipped_total} once the clipping path has run
         self.last_grad_norm = None          # set by train_epoch from the step's one readback
         self.last_step_skipped = False
+        self._ema_decay = None
+        self.ema_decay = ema_decay          # validated by the setter
+        self.ema_warmup = bool(ema_warmup)
+        self._ema = self._emacfg = self._emacfg_host = None      # shadow [flat.numel], device {decay, warmup, s0}
+        self._ema_s0 = 0                    # AdamW's step count when averaging began
+        self._ema_seeded = False
+        self._ema_swapped = False           # inside ema_parameters(): the model holds the average, the shadow the weights
+
+    @property
+    def ema_decay(self):
+        return self._ema_decay
+
+    @ema_decay.setter
+    def ema_decay(self, value):
+        if value is not None and not 0.0 < float(value) < 1.0:
+            raise ValueError(f"FusedAdamW: ema_decay={value} must lie strictly between 0 and 1 (None: no averaging)")
+        if value is None:
+            self._ema_seeded = False        # switched on again later, the average starts over from the parameters then
+        self._ema_decay = None if value is None else float(value)
+
+    @property
+    def ema_path(self):
+        """does step() take the entry points that also advance the weight average?"""
+        return self._ema_decay is not None
+
+    def _sync_ema(self, flat):
+        """the average's device buffers: the shadow (allocated once per flat buffer, seeded from the parameters when
+        averaging begins) and emacfg = {decay, warmup, s0}, which follows the host values in place like _hyper does"""
+        dev = flat.data.device
+        if self._ema is None or self._ema.numel() != flat.numel or self._ema.device != dev:
+            self._ema = torch.empty_like(flat.data)
+            self._ema_seeded = False
+        if not self._ema_seeded:
+            self._ema.copy_(flat.data)
+            # the device counter is the truth where it exists (void steps do not advance it)
+            known = self._state is not None and self._state.device == dev and not torch.cuda.is_current_stream_capturing()
+            self._ema_s0 = int(self._state[0].item()) if known else int(self._step)
+            self._ema_seeded = True
+        host = (float(self._ema_decay), float(self.ema_warmup), float(self._ema_s0))
+        if self._emacfg is None or self._emacfg.device != dev:
+            self._emacfg = torch.tensor(host, dtype=torch.float32, device=dev)
+            self._emacfg_host = host
+        elif host != self._emacfg_host:
+            self._emacfg.copy_(torch.tensor(host, dtype=torch.float32))
+            self._emacfg_host = host
+
+    def _ema_reseed(self, step):
+        """the average starts over from the current parameters at step count `step`, in the buffers it already has"""
+        flat = self.model.flatten_parameters()
+        self._ema_seeded = False
+        self._sync_ema(flat)
+        self._ema_s0 = int(step)
+        self._sync_ema(flat)
+
+    def _ema_swap(self, flat):
+        ops.swap(flat.data, self._ema)
+        flat.wt_stale = True                # transposed weights; the weight images are rebuilt by every model call
+        if hasattr(self.model, "notify_parameters_changed"):
+            self.model.notify_parameters_changed()      # folded BatchNorm weights
+
+    @contextlib.contextmanager
+    def ema_parameters(self):
+        """inside the block the model runs on the averaged weights (with its live BatchNorm running statistics): the
+        flat parameter buffer and the shadow exchange their CONTENTS, so a recorded step keeps valid addresses; on exit they
+        are exchanged back.  No step, taped replay, checkpoint or second ema_parameters() inside the block."""
+        if not self.ema_path:
+            raise RuntimeError("FusedAdamW.ema_parameters: averaging is off (ema_decay=None)")
+        if self._ema_swapped:
+            raise RuntimeError("FusedAdamW.ema_parameters: already inside ema_parameters()")
+        flat = self._moments()
+        self._ema_swap(flat)
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            self._ema_swap(flat)
+            self._ema_swapped = False
+
+    def _check_not_swapped(self, what):
+        if self._ema_swapped:
+            raise RuntimeError(f"FusedAdamW: {what} inside ema_parameters(): the model holds the averaged weights; leave "
+                               "the block first")
+
+    @torch.no_grad()
+    def ema_state_dict(self):
+        """the model's state_dict() with every parameter replaced by a logical-shape ([Cout,Cin,kh,kw]) copy of its
+        average; buffers (BatchNorm running statistics) are the model's live ones"""
+        if not self.ema_path:
+            raise RuntimeError("FusedAdamW.ema_state_dict: averaging is off (ema_decay=None)")
+        flat = self._moments()
+        src = flat.data if self._ema_swapped else self._ema
+        sd = self.model.state_dict()
+        for name, p in self.model.named_parameters():
+            sd[name] = flat.view_of(src, p).contiguous().clone()
+        return sd
+
+    @torch.no_grad()
+    def load_ema_state_dict(self, sd):
+        """the inverse of ema_state_dict(): parameters of `sd` are copied into the shadow the optimizer already has
+        (a recorded step holds its address); buffers are not touched"""
+        if not self.ema_path:
+            raise RuntimeError("FusedAdamW.load_ema_state_dict: averaging is off (ema_decay=None)")
+        self._check_not_swapped("load_ema_state_dict()")
+        flat = self._moments()
+        for name, p in self.model.named_parameters():
+            flat.view_of(self._ema, p).copy_(sd[name].to(self._ema.device))
 
     @property
     def clip_path(self):
@@ -108,23 +228,35 @@ class FusedAdamW(torch.optim.Optimizer):
         elif host != self._hyper_host:
             self._hyper.copy_(torch.tensor(host, dtype=torch.float32))
             self._hyper_host = host
+        if self.ema_path and getattr(self.model, "_flat", None) is not None:
+            self._sync_ema(self.model._flat)
 
     @torch.no_grad()
     def step(self, closure=None):
+        self._check_not_swapped("step()")
         flat = self.model.flatten_parameters()
         if self._m is None or self._m.numel() != flat.numel or self._m.device != flat.data.device:
             self._m = torch.zeros_like(flat.data)
             self._v = torch.zeros_like(flat.data)
         if not torch.cuda.is_current_stream_capturing():
             self._sync_hyper(flat.data.device)
+        ema = self.ema_path
+        if ema and (self._emacfg is None or not self._ema_seeded or self._ema.device != flat.data.device):
+            self._sync_ema(flat)            # (only while capturing without a warm-up)
         self._step += 1
         if self.clip_path:
             if self._partial is None or self._partial.device != flat.data.device:     # (only while capturing without a warm-up)
                 self._sync_clip(flat.data.device, flat.numel)
             ops.grad_sumsq(flat.grad, self._partial)
             ops.grad_clip_finalize(self._partial, self._hyper, self._clipcfg, self._state, self.grad_stats)
-            ops.adamw_dev_clip(flat.data, flat.grad, self._m, self._v, self._hyper, self._state, self._clipcfg,
-                               self.grad_stats)
+            if ema:
+                ops.adamw_dev_clip_ema(flat.data, flat.grad, self._m, self._v, self._ema, self._hyper, self._state,
+                                       self._clipcfg, self.grad_stats, self._emacfg)
+            else:
+                ops.adamw_dev_clip(flat.data, flat.grad, self._m, self._v, self._hyper, self._state, self._clipcfg,
+                                   self.grad_stats)
+        elif ema:
+            ops.adamw_dev_ema(flat.data, flat.grad, self._m, self._v, self._ema, self._hyper, self._state, self._emacfg)
         else:
             ops.adamw_dev(flat.data, flat.grad, self._m, self._v, self._hyper, self._state)
         if hasattr(self.model, "notify_parameters_changed"):
@@ -146,6 +278,8 @@ class FusedAdamW(torch.optim.Optimizer):
             self._v = torch.zeros_like(flat.data)
         if self.clip_path:
             self._sync_clip(flat.data.device, flat.numel)
+        if self.ema_path:
+            self._sync_ema(flat)
         return flat
 
     def state_dict(self):
@@ -187,16 +321,27 @@ class FusedAdamW(torch.optim.Optimizer):
                 step = max(step, int(float(st["step"])))
         self._step = step
         self._hyper = self._state = None                  # rebuilt (with the loaded step) on the next step
+        if self.ema_path:                                 # no average comes with this format: it starts over from here
+            self._ema_reseed(step)                        # (load_checkpoint restores one on top of this when the file has it)
 
 
 def save_checkpoint(path, model, optimizer, epoch, loss, test_measure_mean=None, test_measure_std=None):
     """the checkpoint dict of the reference (train.py:668-680, 689-703), written atomically like there
     (new_*.pt then rename); loadable by the reference's own torch.load + load_state_dict"""
     import os
+    if getattr(optimizer, "_ema_swapped", False):
+        optimizer._check_not_swapped("save_checkpoint()")
     tmp = os.path.join(os.path.dirname(path) or ".", "new_" + os.path.basename(path))
     sd = {k: v.detach().contiguous().cpu() for k, v in _unwrap(model).state_dict().items()}
-    torch.save({"epoch": epoch, "model_state_dict": sd, "optimizer_state_dict": optimizer.state_dict(),
-                "loss": loss, "test_measure_mean": test_measure_mean, "test_measure_std": test_measure_std}, tmp)
+    ck = {"epoch": epoch, "model_state_dict": sd, "optimizer_state_dict": optimizer.state_dict(),
+          "loss": loss, "test_measure_mean": test_measure_mean, "test_measure_std": test_measure_std}
+    if getattr(optimizer, "ema_path", False):
+        # two keys on top of the reference's dict (which its own torch.load + load_state_dict still read): the averaged
+        # weights in the model's state_dict format and what the average's schedule needs to continue
+        ck["ema_state_dict"] = {k: v.detach().contiguous().cpu() for k, v in optimizer.ema_state_dict().items()}
+        ck["ema_meta"] = {"decay": float(optimizer.ema_decay), "warmup": bool(optimizer.ema_warmup),
+                          "start_step": int(optimizer._ema_s0)}
+    torch.save(ck, tmp)
     if os.path.exists(path):
         os.remove(path)
     os.rename(tmp, path)
@@ -208,6 +353,15 @@ def load_checkpoint(path, model, optimizer=None, device="cuda"):
     _unwrap(model).load_state_dict(ck["model_state_dict"])
     if optimizer is not None and "optimizer_state_dict" in ck:
         optimizer.load_state_dict(ck["optimizer_state_dict"])
+    if optimizer is not None and getattr(optimizer, "ema_path", False):
+        if "ema_state_dict" in ck and "ema_meta" in ck:
+            meta = ck["ema_meta"]
+            optimizer.ema_decay, optimizer.ema_warmup = float(meta["decay"]), bool(meta["warmup"])
+            optimizer.load_ema_state_dict(ck["ema_state_dict"])
+            optimizer._ema_s0 = int(meta["start_step"])
+            optimizer._sync_ema(_unwrap(model).flatten_parameters())
+        elif "optimizer_state_dict" not in ck:
+            optimizer._ema_reseed(optimizer._step)        # (with an optimizer state, load_state_dict has done this)
     return ck
 
 
@@ -384,6 +538,8 @@ class GraphedTrainStep:
         torch.cuda.synchronize()
 
     def __call__(self, data, target):
+        if getattr(self.optimizer, "_ema_swapped", False):
+            self.optimizer._check_not_swapped("a graph replay of the step")
         self.x.copy_(data, non_blocking=True)
         self.t.copy_(target, non_blocking=True)
         self.optimizer._sync_hyper(self.x.device)
@@ -422,6 +578,7 @@ class TapedTrainStep:
         self._lib = _lib
         self.model, self.optimizer, self.args = model, optimizer, args
         self.clip_path = bool(getattr(optimizer, "clip_path", False))      # fixed for the life of the recording
+        self.ema_path = bool(getattr(optimizer, "ema_path", False))        # so is whether the update advances an average
         m = _unwrap(model)
         for ce_fn, dice_fn in lossFuncts:
             if not (isinstance(ce_fn, losses.CrossEntropyLoss) and isinstance(dice_fn, losses.SoftDiceLoss)):
@@ -537,6 +694,11 @@ class TapedTrainStep:
         if m._flat is not self._flat or not self._flat.valid(self.x.device):
             raise RuntimeError("TapedTrainStep: the model's parameters were moved (.to() / .cuda() / re-flattened) after the step "
                                "was recorded; record a new one")
+        if getattr(self.optimizer, "_ema_swapped", False):
+            self.optimizer._check_not_swapped("a taped replay of the step")
+        if bool(getattr(self.optimizer, "ema_path", False)) != self.ema_path:
+            raise RuntimeError("TapedTrainStep: optimizer.ema_decay was switched between None and a number after the step was "
+                               "recorded; record a new one")
         self._load(data, target)
         self.optimizer._sync_hyper(self.x.device)
         self.optimizer._step += 1
@@ -625,7 +787,8 @@ def taped_step_for(model, optimizer, lossFuncts, args, class_tree, data, target,
            bool(getattr(m, "sync_bn", False)), _lib.deterministic(), _lib.tune_generation(), id(m._grad_hook),
            dist.is_available() and dist.is_initialized() and dist.get_world_size(), m.training,
            tuple(tuple(float(v) for v in w) for w in args.level_weights),
-           bool(getattr(optimizer, "clip_path", False)))       # the path, not the threshold: that lives on the device
+           bool(getattr(optimizer, "clip_path", False)),       # the path, not the threshold: that lives on the device
+           bool(getattr(optimizer, "ema_path", False)))        # likewise: the decay is read from device memory
     cache = m.__dict__.setdefault("_hr_tapes", {})
     step = cache.get(key)
     if step is not None:
