@@ -193,14 +193,21 @@ class DeviceDecode:
         self.leaf_values = sorted(v for row, kids in zip(self.tables.pixel_val, self.tables.n_children)
                                   for v, k in zip(row, kids) if k == 0)
 
-    def decode(self, output_logits, desc, desc_host=None, want_confidence=False) -> RaggedLabels:
-        require_gpu()
-        logits = [output_logits] if torch.is_tensor(output_logits) else list(output_logits)
+    @staticmethod
+    def _descriptors(desc, desc_host, logits):
+        """(desc on the device of the first logit tensor, desc_host): a host table is its own host copy"""
         if desc_host is None:
             if desc.is_cuda:
                 raise ValueError("a device descriptor table needs its host copy (desc_host)")
             desc_host = desc
-        desc = desc.to(logits[0].device, non_blocking=True)
+        if logits and torch.is_tensor(logits[0]):
+            desc = desc.to(logits[0].device, non_blocking=True)
+        return desc, desc_host
+
+    def decode(self, output_logits, desc, desc_host=None, want_confidence=False) -> RaggedLabels:
+        require_gpu()
+        logits = [output_logits] if torch.is_tensor(output_logits) else list(output_logits)
+        desc, desc_host = self._descriptors(desc, desc_host, logits)
         labels, conf = ops.decode_labels(logits, self.tables, desc, desc_host, want_confidence)
         return RaggedLabels(labels, conf, desc, desc_host)
 
@@ -215,12 +222,7 @@ class DeviceDecode:
         `decode` decodes one set of logits.  One launch (csrc/decode_views.hip)."""
         require_gpu()
         views = [(([z] if torch.is_tensor(z) else list(z)), f) for z, f in views]
-        if desc_host is None:
-            if desc.is_cuda:
-                raise ValueError("a device descriptor table needs its host copy (desc_host)")
-            desc_host = desc
-        if views and views[0][0]:
-            desc = desc.to(views[0][0][0].device, non_blocking=True)
+        desc, desc_host = self._descriptors(desc, desc_host, views[0][0] if views else [])
         labels, conf = ops.decode_views(views, self.tables, desc, desc_host, want_confidence)
         return RaggedLabels(labels, conf, desc, desc_host)
 
@@ -234,12 +236,7 @@ class DeviceDecode:
         resampled to the wanted sizes and decoded as `decode` decodes one set of logits.  One launch (csrc/windows.hip)."""
         require_gpu()
         logits = [output_logits] if torch.is_tensor(output_logits) else list(output_logits)
-        if desc_host is None:
-            if desc.is_cuda:
-                raise ValueError("a device descriptor table needs its host copy (desc_host)")
-            desc_host = desc
-        if logits and torch.is_tensor(logits[0]):
-            desc = desc.to(logits[0].device, non_blocking=True)
+        desc, desc_host = self._descriptors(desc, desc_host, logits)
         labels, conf = ops.decode_windows(logits, self.tables, plan, profile, desc, desc_host, want_confidence)
         return RaggedLabels(labels, conf, desc, desc_host)
 

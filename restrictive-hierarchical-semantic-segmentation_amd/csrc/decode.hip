@@ -147,23 +147,13 @@ extern "C" int hrseg_decode_labels(int nlevels, const float* const* z, const int
                                    hrseg_stream_t stream) {
   HRSEG_CHECK_ARG(z && C && tree && desc && labels && B > 0 && B <= 65535 && S > 0 && S <= 32768,
                   "hrseg_decode_labels: bad arguments");
-  HRSEG_CHECK_ARG(((uintptr_t)labels & 3) == 0 && ((uintptr_t)confidence & 15) == 0,
-                  "hrseg_decode_labels: labels must be 4-byte and confidence 16-byte aligned");
   DecodeArgs a;
-  if (const int rc = dec_pack_tree("hrseg_decode_labels", nlevels, C, tree, a.node, a.C)) return rc;
-  for (int L = 0; L < HRSEG_DECODE_MAX_LEVELS; ++L) {
-    HRSEG_CHECK_ARG(L >= nlevels || z[L], "hrseg_decode_labels: level %d has no logits", L);
-    a.z[L] = L < nlevels ? z[L] : nullptr;
-  }
+  if (const int rc = dec_outputs_and_tree("hrseg_decode_labels", nlevels, C, tree, labels, confidence, a.node, a.C, &a.root_softmax))
+    return rc;
+  if (const int rc = dec_level_pointers("hrseg_decode_labels", nlevels, z, a.z)) return rc;
   a.nlevels = nlevels;
-  a.root_softmax = tree->root_softmax ? 1 : 0;
-  const dim3 grid((unsigned)dec_blocks_per_sample(B), (unsigned)B);
-  if (confidence)
-    hipLaunchKernelGGL(decode_labels_kernel<true>, grid, dim3(DEC_TPB), 0, (hipStream_t)stream, a, (const long long*)desc, labels,
-                       confidence, S);
-  else
-    hipLaunchKernelGGL(decode_labels_kernel<false>, grid, dim3(DEC_TPB), 0, (hipStream_t)stream, a, (const long long*)desc, labels,
-                       confidence, S);
+  dec_launch(decode_labels_kernel<true>, decode_labels_kernel<false>, confidence, B, stream, a, (const long long*)desc, labels,
+             confidence, S);
   HRSEG_LAUNCH_CHECK("decode_labels");
   hrseg_count(CNT_DECODE_LABELS);
   return 0;

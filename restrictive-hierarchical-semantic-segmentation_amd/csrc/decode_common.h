@@ -1,6 +1,6 @@
 // What the decode kernels share (decode.hip: one view, decode_views.hip: the mean logit of several views, windows.hip: the
-// blend of overlapping windows): the tile shape, the bilinear taps of one output coordinate, the arithmetic of a channel step and the
-// host-side validation and packing of the tree.
+// blend of overlapping windows): the tile shape, the bilinear taps of one output coordinate, the arithmetic of a channel step and,
+// on the host, the validation and packing of the tree and the prelude and launch of the three entry points.
 #pragma once
 #include "common.h"
 
@@ -94,4 +94,33 @@ static inline int dec_pack_tree(const char* who, int nlevels, const int* C, cons
 static inline int dec_blocks_per_sample(int B) {
   const int per_sample = 8192 / B;
   return per_sample < 1 ? 1 : (per_sample > 1024 ? 1024 : per_sample);
+}
+
+// ---- the prelude and the launch that hrseg_decode_labels, hrseg_decode_views and hrseg_decode_windows share (host)
+// the alignment the dword / float4 stores of the outputs need, then the tree (dec_pack_tree) and its root_softmax as 0 / 1
+static inline int dec_outputs_and_tree(const char* who, int nlevels, const int* C, const hrseg_decode_tree_t* tree,
+                                       const unsigned char* labels, const float* confidence, unsigned* node, int* Cout,
+                                       int* root_softmax) {
+  HRSEG_CHECK_ARG(((uintptr_t)labels & 3) == 0 && ((uintptr_t)confidence & 15) == 0,
+                  "%s: labels must be 4-byte and confidence 16-byte aligned", who);
+  if (const int rc = dec_pack_tree(who, nlevels, C, tree, node, Cout)) return rc;
+  *root_softmax = tree->root_softmax ? 1 : 0;
+  return 0;
+}
+
+// one set of level pointers z[0 .. nlevels) -> out[HRSEG_DECODE_MAX_LEVELS] (nullptr beyond nlevels)
+static inline int dec_level_pointers(const char* who, int nlevels, const float* const* z, const float** out) {
+  for (int L = 0; L < HRSEG_DECODE_MAX_LEVELS; ++L) {
+    HRSEG_CHECK_ARG(L >= nlevels || z[L], "%s: level %d has no logits", who, L);
+    out[L] = L < nlevels ? z[L] : nullptr;
+  }
+  return 0;
+}
+
+// the grid every decode uses, and the instantiation with or without the confidence
+template <typename... P, typename... A>
+static inline void dec_launch(void (*with_conf)(P...), void (*labels_only)(P...), const float* confidence, int B,
+                              hrseg_stream_t stream, A... args) {
+  const dim3 grid((unsigned)dec_blocks_per_sample(B), (unsigned)B);
+  hipLaunchKernelGGL(confidence ? with_conf : labels_only, grid, dim3(DEC_TPB), 0, (hipStream_t)stream, args...);
 }

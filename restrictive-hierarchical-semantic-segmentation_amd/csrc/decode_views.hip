@@ -192,12 +192,9 @@ extern "C" int hrseg_decode_views(int nviews, const int* S, const int* flags, in
   HRSEG_CHECK_ARG(nviews >= 1 && nviews <= HRSEG_DECODE_MAX_VIEWS, "hrseg_decode_views: nviews=%d not in 1..%d", nviews,
                   HRSEG_DECODE_MAX_VIEWS);
   HRSEG_CHECK_ARG(S && flags && z && C && tree && desc && labels && B > 0 && B <= 65535, "hrseg_decode_views: bad arguments");
-  HRSEG_CHECK_ARG(((uintptr_t)labels & 3) == 0 && ((uintptr_t)confidence & 15) == 0,
-                  "hrseg_decode_views: labels must be 4-byte and confidence 16-byte aligned");
-  DecodeViewsArgs a;
-  if (const int rc = dec_pack_tree("hrseg_decode_views", nlevels, C, tree, a.node, a.C)) return rc;
-  for (int i = 0; i < DEC_VIEWS * HRSEG_DECODE_MAX_LEVELS; ++i) a.z[i] = nullptr;
-  for (int v = 0; v < DEC_VIEWS; ++v) a.S[v] = a.flags[v] = 0;
+  DecodeViewsArgs a = {};
+  if (const int rc = dec_outputs_and_tree("hrseg_decode_views", nlevels, C, tree, labels, confidence, a.node, a.C, &a.root_softmax))
+    return rc;
   for (int v = 0; v < nviews; ++v) {
     HRSEG_CHECK_ARG(S[v] >= 1 && S[v] <= 32768, "hrseg_decode_views: S[%d]=%d not in 1..32768", v, S[v]);
     HRSEG_CHECK_ARG(flags[v] >= 0 && flags[v] <= 3, "hrseg_decode_views: flags[%d]=%d not in 0..3", v, flags[v]);
@@ -210,15 +207,9 @@ extern "C" int hrseg_decode_views(int nviews, const int* S, const int* flags, in
   }
   a.nviews = nviews;
   a.nlevels = nlevels;
-  a.root_softmax = tree->root_softmax ? 1 : 0;
   a.inv_views = 1.0f / (float)nviews;
-  const dim3 grid((unsigned)dec_blocks_per_sample(B), (unsigned)B);
-  if (confidence)
-    hipLaunchKernelGGL(decode_views_kernel<true>, grid, dim3(DEC_TPB), 0, (hipStream_t)stream, a, (const long long*)desc, labels,
-                       confidence);
-  else
-    hipLaunchKernelGGL(decode_views_kernel<false>, grid, dim3(DEC_TPB), 0, (hipStream_t)stream, a, (const long long*)desc, labels,
-                       confidence);
+  dec_launch(decode_views_kernel<true>, decode_views_kernel<false>, confidence, B, stream, a, (const long long*)desc, labels,
+             confidence);
   HRSEG_LAUNCH_CHECK("decode_views");
   hrseg_count(CNT_DECODE_VIEWS);
   return 0;

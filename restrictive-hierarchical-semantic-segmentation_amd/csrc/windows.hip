@@ -281,25 +281,15 @@ extern "C" int hrseg_decode_windows(int nlevels, const float* const* z, const in
   HRSEG_CHECK_ARG(B > 0 && B <= 65535, "hrseg_decode_windows: B=%d not in 1..65535", B);
   HRSEG_CHECK_ARG(S >= 1 && S <= 32768, "hrseg_decode_windows: S=%d not in 1..32768", S);
   HRSEG_CHECK_ARG(nwindows >= B, "hrseg_decode_windows: %d windows for %d images", nwindows, B);
-  HRSEG_CHECK_ARG(((uintptr_t)labels & 3) == 0 && ((uintptr_t)confidence & 15) == 0,
-                  "hrseg_decode_windows: labels must be 4-byte and confidence 16-byte aligned");
   DecodeWindowsArgs a;
-  if (const int rc = dec_pack_tree("hrseg_decode_windows", nlevels, C, tree, a.node, a.C)) return rc;
-  for (int L = 0; L < HRSEG_DECODE_MAX_LEVELS; ++L) {
-    HRSEG_CHECK_ARG(L >= nlevels || z[L], "hrseg_decode_windows: level %d has no logits", L);
-    a.z[L] = L < nlevels ? z[L] : nullptr;
-  }
+  if (const int rc = dec_outputs_and_tree("hrseg_decode_windows", nlevels, C, tree, labels, confidence, a.node, a.C, &a.root_softmax))
+    return rc;
+  if (const int rc = dec_level_pointers("hrseg_decode_windows", nlevels, z, a.z)) return rc;
   a.nlevels = nlevels;
-  a.root_softmax = tree->root_softmax ? 1 : 0;
   a.S = S;
   a.nwindows = nwindows;
-  const dim3 grid((unsigned)dec_blocks_per_sample(B), (unsigned)B);
-  if (confidence)
-    hipLaunchKernelGGL(decode_windows_kernel<true>, grid, dim3(DEC_TPB), 0, (hipStream_t)stream, a, (const long long*)wdesc,
-                       origins, profile, (const long long*)desc, labels, confidence);
-  else
-    hipLaunchKernelGGL(decode_windows_kernel<false>, grid, dim3(DEC_TPB), 0, (hipStream_t)stream, a, (const long long*)wdesc,
-                       origins, profile, (const long long*)desc, labels, confidence);
+  dec_launch(decode_windows_kernel<true>, decode_windows_kernel<false>, confidence, B, stream, a, (const long long*)wdesc, origins,
+             profile, (const long long*)desc, labels, confidence);
   HRSEG_LAUNCH_CHECK("decode_windows");
   hrseg_count(CNT_DECODE_WINDOWS);
   return 0;

@@ -662,29 +662,55 @@ def _decode_tree_struct(tables):
     return t
 
 
-def decode_labels(logits, tables, desc, desc_host, want_confidence=False):
-    """per-level logits (list of [B,C_L,S,S] fp32 device tensors, or one tensor) + a Data.decode.DecodeTables + [B,4] int64
-    label descriptors (byte offset, H, W, 1; device, and their host copy for the bounds check) -> the packed uint8
-    label maps (sum of H*W bytes: a densely packed batch), each at its own H x W, plus the packed fp32 path confidence
-    when asked for (else None).  The tables are read afresh on every call.  One launch, no synchronisation."""
+def _decode_logits(who, logits, tables, view=None):
+    """one set of per-level logits of `who` (a list of [N,C_L,S,S] fp32 device tensors, or one tensor; `view`: its number
+    in an ensemble, for the messages) against the tables -> (the tensors, contiguous; N; S)"""
+    has, at = (f"view {view} has ", f"view {view}, ") if view is not None else ("", "")
     logits = [logits] if torch.is_tensor(logits) else list(logits)
-    check_decode_tables(tables)
     if len(logits) != len(tables.C):
-        raise ValueError(f"decode_labels: {len(logits)} logit levels for a {len(tables.C)}-level table")
-    B, S = logits[0].shape[0], logits[0].shape[2]
+        raise ValueError(f"{who}: {has}{len(logits)} logit levels for a {len(tables.C)}-level table")
+    if logits[0].dim() != 4:
+        raise ValueError(f"{who}: {at}level 0 logits of shape {tuple(logits[0].shape)}, expected 4 dimensions")
+    N, S = logits[0].shape[0], logits[0].shape[2]
     for L, z in enumerate(logits):
-        if z.dim() != 4 or tuple(z.shape) != (B, tables.C[L], S, S):
-            raise ValueError(f"decode_labels: level {L} logits of shape {tuple(z.shape)}, expected {(B, tables.C[L], S, S)}")
-        assert z.is_cuda and z.dtype == torch.float32
-    assert desc.dtype == torch.int64 and desc.is_cuda and desc.dim() == 2 and tuple(desc.shape) == tuple(desc_host.shape) == (B, 4)
+        if z.dim() != 4 or tuple(z.shape) != (N, tables.C[L], S, S):
+            raise ValueError(f"{who}: {at}level {L} logits of shape {tuple(z.shape)}, expected {(N, tables.C[L], S, S)}")
+        if not z.is_cuda or z.dtype != torch.float32:
+            raise ValueError(f"{who}: {at}level {L}: logits must be fp32 device tensors")
+    return [_c(z) for z in logits], N, S
+
+
+def _decode_desc(who, desc, desc_host, B=None):
+    """the [B,4] int64 label descriptors (byte offset, H, W, 1) of `who`, on the device and their host copy (B: from the host
+    copy where None), and the ragged rows against the densely packed buffer they describe -> its bytes"""
+    if not torch.is_tensor(desc_host) or desc_host.dim() != 2 or desc_host.shape[1] != 4:
+        raise ValueError(f"{who}: the host descriptor table must be [B,4] int64")
+    B = desc_host.shape[0] if B is None else B
+    if desc.dtype != torch.int64 or not desc.is_cuda or not tuple(desc.shape) == tuple(desc_host.shape) == (B, 4):
+        raise ValueError(f"{who}: the descriptor tables must be [{B},4] int64, one on the device and its host copy")
     rows = desc_host.tolist()
     n = sum(H * W for _, H, W, _ in rows)
     for off, H, W, ch in rows:
         if ch != 1 or H < 1 or W < 1 or off < 0 or off + H * W > n:
             raise ValueError(f"ragged descriptor (offset {off}, {H}x{W}, {ch} channels) does not fit a {n}-byte label buffer")
-    logits = [_c(z) for z in logits]
-    labels = torch.empty(n, dtype=torch.uint8, device=logits[0].device)
-    conf = torch.empty(n, dtype=torch.float32, device=logits[0].device) if want_confidence else None
+    return n
+
+
+def _decode_outputs(n, device, want_confidence):
+    """the packed uint8 labels and, when asked for, the packed fp32 confidence (else None) of n pixels"""
+    return (torch.empty(n, dtype=torch.uint8, device=device),
+            torch.empty(n, dtype=torch.float32, device=device) if want_confidence else None)
+
+
+def decode_labels(logits, tables, desc, desc_host, want_confidence=False):
+    """per-level logits (list of [B,C_L,S,S] fp32 device tensors, or one tensor) + a Data.decode.DecodeTables + [B,4] int64
+    label descriptors (byte offset, H, W, 1; device, and their host copy for the bounds check) -> the packed uint8
+    label maps (sum of H*W bytes: a densely packed batch), each at its own H x W, plus the packed fp32 path confidence
+    when asked for (else None).  The tables are read afresh on every call.  One launch, no synchronisation."""
+    check_decode_tables(tables)
+    logits, B, S = _decode_logits("decode_labels", logits, tables)
+    n = _decode_desc("decode_labels", desc, desc_host, B)
+    labels, conf = _decode_outputs(n, logits[0].device, want_confidence)
     call("hrseg_decode_labels", len(logits), _lib.ptr_array(logits), _lib.int_array(list(tables.C)),
          C.byref(_decode_tree_struct(tables)),
          ptr(desc), ptr(labels), ptr(conf), B, S)
@@ -726,38 +752,20 @@ def decode_views(views, tables, desc, desc_host, want_confidence=False):
     tensor; flags), ...] with flags 0, VIEW_HFLIP, VIEW_VFLIP or both (the network saw the image mirrored), the sizes
     S_v free per view -> (packed uint8 labels, packed fp32 confidence or None) exactly as decode_labels returns them.
     Contiguous batch slices z[v*B:(v+1)*B] of one batched forward are read in place.  One launch, no synchronisation."""
-    views = [(([z] if torch.is_tensor(z) else list(z)), f) for z, f in views]
     flags = _check_view_flags("decode_views", [f for _, f in views])
     check_decode_tables(tables)
-    B = views[0][0][0].shape[0] if views[0][0] and views[0][0][0].dim() == 4 else -1
-    sizes = []
+    flat, sizes, B = [], [], None
     for v, (logits, _) in enumerate(views):
-        if len(logits) != len(tables.C):
-            raise ValueError(f"decode_views: view {v} has {len(logits)} logit levels for a {len(tables.C)}-level table")
-        if logits[0].dim() != 4:
-            raise ValueError(f"decode_views: view {v}, level 0 logits of shape {tuple(logits[0].shape)}, expected 4 dimensions")
-        if logits[0].shape[0] != B:
-            raise ValueError(f"decode_views: view {v} has batch size {logits[0].shape[0]}, view 0 has {B}")
-        S = logits[0].shape[2]
+        logits, N, S = _decode_logits("decode_views", logits, tables, v)
+        B = N if B is None else B
+        if N != B:
+            raise ValueError(f"decode_views: view {v} has batch size {N}, view 0 has {B}")
         if not 1 <= S <= DECODE_MAX_SIZE:
             raise ValueError(f"decode_views: view {v} has size {S}, supported 1..{DECODE_MAX_SIZE}")
-        for L, z in enumerate(logits):
-            if z.dim() != 4 or tuple(z.shape) != (B, tables.C[L], S, S):
-                raise ValueError(f"decode_views: view {v}, level {L} logits of shape {tuple(z.shape)}, expected "
-                                 f"{(B, tables.C[L], S, S)}")
-            if not z.is_cuda or z.dtype != torch.float32:
-                raise ValueError(f"decode_views: view {v}, level {L}: logits must be fp32 device tensors")
+        flat += logits
         sizes.append(S)
-    if desc.dtype != torch.int64 or not desc.is_cuda or desc.dim() != 2 or not tuple(desc.shape) == tuple(desc_host.shape) == (B, 4):
-        raise ValueError(f"decode_views: the descriptor tables must be [{B},4] int64, one on the device and its host copy")
-    rows = desc_host.tolist()
-    n = sum(H * W for _, H, W, _ in rows)
-    for off, H, W, ch in rows:
-        if ch != 1 or H < 1 or W < 1 or off < 0 or off + H * W > n:
-            raise ValueError(f"ragged descriptor (offset {off}, {H}x{W}, {ch} channels) does not fit a {n}-byte label buffer")
-    flat = [_c(z) for logits, _ in views for z in logits]
-    labels = torch.empty(n, dtype=torch.uint8, device=flat[0].device)
-    conf = torch.empty(n, dtype=torch.float32, device=flat[0].device) if want_confidence else None
+    n = _decode_desc("decode_views", desc, desc_host, B)
+    labels, conf = _decode_outputs(n, flat[0].device, want_confidence)
     call("hrseg_decode_views", len(views), _lib.int_array(sizes), _lib.int_array(flags), len(tables.C), _lib.ptr_array(flat),
          _lib.int_array(list(tables.C)), C.byref(_decode_tree_struct(tables)), ptr(desc), ptr(labels), ptr(conf), B)
     return labels, conf
@@ -841,38 +849,18 @@ def decode_windows(logits, tables, plan, profile, desc, desc_host, want_confiden
     tensors, or one tensor), a Data.decode.WindowPlan, the blend profile (S positive fp32 weights) and [B,4] label
     descriptors of the wanted sizes -> (packed uint8 labels, packed fp32 confidence or None) as decode_labels returns
     them.  No canvas-size tensor is built.  One launch, no synchronisation."""
-    logits = [logits] if torch.is_tensor(logits) else list(logits)
     check_decode_tables(tables)
-    if len(logits) != len(tables.C):
-        raise ValueError(f"decode_windows: {len(logits)} logit levels for a {len(tables.C)}-level table")
-    if logits[0].dim() != 4:
-        raise ValueError(f"decode_windows: level 0 logits of shape {tuple(logits[0].shape)}, expected 4 dimensions")
-    N, S = logits[0].shape[0], logits[0].shape[2]
-    for L, z in enumerate(logits):
-        if z.dim() != 4 or tuple(z.shape) != (N, tables.C[L], S, S):
-            raise ValueError(f"decode_windows: level {L} logits of shape {tuple(z.shape)}, expected {(N, tables.C[L], S, S)}")
-        if not z.is_cuda or z.dtype != torch.float32:
-            raise ValueError(f"decode_windows: level {L}: logits must be fp32 device tensors")
-    if not torch.is_tensor(desc_host) or desc_host.dim() != 2 or desc_host.shape[1] != 4:
-        raise ValueError("decode_windows: the host descriptor table must be [B,4] int64")
+    logits, N, S = _decode_logits("decode_windows", logits, tables)
+    n = _decode_desc("decode_windows", desc, desc_host)
     B = desc_host.shape[0]
-    if desc.dtype != torch.int64 or not desc.is_cuda or tuple(desc.shape) != (B, 4):
-        raise ValueError(f"decode_windows: the descriptor tables must be [{B},4] int64, one on the device and its host copy")
     check_window_plan("decode_windows", plan, B, S)
     if int(plan.nwindows) != N:
         raise ValueError(f"decode_windows: logits of {N} windows for a plan of {plan.nwindows}")
     check_window_profile("decode_windows", profile, S)
-    rows = desc_host.tolist()
-    n = sum(H * W for _, H, W, _ in rows)
-    for off, H, W, ch in rows:
-        if ch != 1 or H < 1 or W < 1 or off < 0 or off + H * W > n:
-            raise ValueError(f"ragged descriptor (offset {off}, {H}x{W}, {ch} channels) does not fit a {n}-byte label buffer")
-    logits = [_c(z) for z in logits]
     device = logits[0].device
     wdesc, origins = _window_tables(plan, device)
     profile = _c(profile.to(device))
-    labels = torch.empty(n, dtype=torch.uint8, device=device)
-    conf = torch.empty(n, dtype=torch.float32, device=device) if want_confidence else None
+    labels, conf = _decode_outputs(n, device, want_confidence)
     call("hrseg_decode_windows", len(logits), _lib.ptr_array(logits), _lib.int_array(list(tables.C)),
          C.byref(_decode_tree_struct(tables)), ptr(wdesc), ptr(origins), ptr(profile), ptr(desc), ptr(labels), ptr(conf), B, S, N)
     return labels, conf

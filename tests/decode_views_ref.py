@@ -15,10 +15,10 @@ import torch
 import torch.nn.functional as F
 
 from tests import decode_ref as R
+from tests.decode_harness import MASK_CAP, RAGGED  # noqa: F401  (the project's cap; output sizes of the cases)
+from tests.decode_harness import _wide_tree as wide_tree
 
 HFLIP, VFLIP = 1, 2
-RAGGED = [(50, 70), (80, 64), (62, 62), (30, 100)]
-MASK_CAP = 0.005
 
 
 def flip(z, flags):
@@ -110,18 +110,6 @@ EIGHT_VIEWS = [(62, f) for f in range(4)] + [(46, f) for f in range(4)]
 # (tree key: "tl" | "ext" | "wide", model_type, view set)
 CASES = [(key, mt, vs) for key in ("tl", "ext") for mt in (1, 0) for vs in range(len(VIEW_SETS))] + \
         [("wide", 1, 0), ("tl", 1, "eight")]
-
-
-def wide_tree():
-    """level 1 has 16 channels (the kernel's limit) in groups of 5, 5 and 6 (as tests/test_decode_gpu.py builds it)"""
-    tree, cmap, v = {"background": {}}, {"background": 0}, 10
-    for g, n in enumerate((5, 5, 6)):
-        tree[f"group{g}"] = {}
-        for k in range(n):
-            tree[f"group{g}"][f"g{g}c{k}"] = {}
-            cmap[f"g{g}c{k}"] = v
-            v += 10
-    return tree, cmap
 
 
 def case_views(tree, model_type, vs):

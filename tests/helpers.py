@@ -1,6 +1,8 @@
 """Shared test helpers: golden-case table, oracle model construction."""
 import json
 import os
+import re
+import subprocess
 
 import numpy as np
 
@@ -22,6 +24,34 @@ CASES = {
     "hrnet_hier_tl_64": ("hrnet", True, "class_tree_tl.json", 64, 2),
     "hrnet_hier_ext_62": ("hrnet", True, "class_tree_tl_extended.json", 62, 2),
 }
+
+
+CSRC = os.path.join(ROOT, "restrictive-hierarchical-semantic-segmentation_amd", "csrc")
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+
+
+def _resources(unit):
+    """{mangled kernel name: (vgprs, scratch bytes per lane, spilled vgprs)} of one translation unit, compiled with the flags the
+    Makefile gives that unit: -fno-slp-vectorize for the units of its CONV_SRCS only"""
+    with open(os.path.join(CSRC, "Makefile")) as f:
+        conv = re.search(r"^CONV_SRCS = (.*)$", f.read().replace("\\\n", " "), re.M).group(1).split()
+    assert "conv_ws.hip" in conv, conv
+    cmd = [HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-w"] + \
+        (["-fno-slp-vectorize"] if unit + ".hip" in conv else []) + \
+        ["-Rpass-analysis=kernel-resource-usage", "-c", unit + ".hip", "-o", os.devnull]
+    err = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True, check=True).stderr
+    out, name = {}, None
+    for line in err.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            out[name] = {}
+            continue
+        for key, pat in (("vgprs", r" VGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"), ("spill", r"VGPRs Spill: (\d+)")):
+            m = re.search(pat, line)
+            if m and name:
+                out[name][key] = int(m.group(1))
+    return out
 
 
 def load_tree(tree_file):

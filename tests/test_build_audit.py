@@ -3,34 +3,11 @@ arithmetic must not spill.  Round 4 found the forward wave-specialised kernels r
 `s_waitcnt vmcnt(0)` in EVERY tile's epilogue -- invisible in every functional test, worth ~10 % of the kernel -- so the
 resource remarks of the compiler are asserted here (about a minute of hipcc)."""
 import os
-import re
-import subprocess
 from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "restrictive-hierarchical-semantic-segmentation_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-
-
-def _resources(unit):
-    """{mangled kernel name: (vgprs, scratch bytes per lane, spilled vgprs)} of one translation unit, compiled as the Makefile does"""
-    cmd = [HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-w", "-fno-slp-vectorize",
-           "-Rpass-analysis=kernel-resource-usage", "-c", unit + ".hip", "-o", os.devnull]
-    err = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True, check=True).stderr
-    out, name = {}, None
-    for line in err.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            out[name] = {}
-            continue
-        for key, pat in (("vgprs", r" VGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"), ("spill", r"VGPRs Spill: (\d+)")):
-            m = re.search(pat, line)
-            if m and name:
-                out[name][key] = int(m.group(1))
-    return out
+from tests.helpers import HIPCC, _resources
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc")

@@ -1,23 +1,12 @@
 """Device output pipeline, the parts that need no GPU: the tree tables of Data.decode.DeviceDecode, their error cases,
 and the float64 oracle (tests/decode_ref.py) on a round trip through the target encoding and on a hand-computed case."""
-import csv
-import os
-
 import numpy as np
 import pytest
 import torch
 
 from oracle import targets as OT
 from tests import decode_ref as R
-from tests.helpers import DATA, load_tree
-
-TREES = {"tl": ("class_tree_tl.json", "class_map.csv"), "ext": ("class_tree_tl_extended.json", "class_map_extended.csv")}
-
-
-def _tree(key):
-    t, m = TREES[key]
-    with open(os.path.join(DATA, m)) as f:
-        return load_tree(t), list(csv.DictReader(f))
+from tests.decode_harness import _tree
 
 
 def _decoder(tree, cmap, model_type):

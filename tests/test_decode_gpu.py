@@ -2,11 +2,10 @@
 (tests/decode_ref.py).  The kernel tests feed the SAME synthetic logits to the device and to the oracle, so they do not
 depend on model numerics; the end-to-end tests apply the oracle to the logits the GPU forward itself returned.
 
-Labels must be equal outside the oracle's near-tie mask (gap of the deciding group below 2e-4), which may cover at most
-0.5 % of a case's pixels.  The confidence is compared outside the mask with a bar of 4x the largest distance of the
-fp32 torch-CPU evaluation of the same formula from the fp64 one on the same inputs (floor 1e-6)."""
+Oracle parity is the rule of tests/decode_harness.py: labels equal outside the oracle's near-tie mask (gap of the deciding
+group below 2e-4), which may cover at most 0.5 % of a case's pixels; confidence outside the mask within 4x the largest
+distance of the fp32 torch-CPU evaluation of the same formula from the fp64 one on the same inputs (floor 1e-6)."""
 import argparse
-import csv
 import os
 
 import numpy as np
@@ -14,60 +13,21 @@ import pytest
 import torch
 
 from tests import decode_ref as R
-from tests.helpers import DATA, build_model, load_tree
+from tests.decode_harness import RAGGED, STRIDED, _source, _tree, _wide_tree, check
+from tests.helpers import build_model
 
 pytestmark = pytest.mark.gpu
 
-TREES = {"tl": ("class_tree_tl.json", "class_map.csv"), "ext": ("class_tree_tl_extended.json", "class_map_extended.csv")}
-RAGGED = [(50, 70), (80, 64), (62, 62), (30, 100)]
-MASK_CAP = 0.005
 
-
-def _tree(key):
-    t, m = TREES[key]
-    with open(os.path.join(DATA, m)) as f:
-        return load_tree(t), list(csv.DictReader(f))
-
-
-def _wide_tree():
-    """level 1 has 16 channels (the kernel's limit) in groups of 5, 5 and 6"""
-    tree, cmap, v = {"background": {}}, {"background": 0}, 10
-    for g, n in enumerate((5, 5, 6)):
-        tree[f"group{g}"] = {}
-        for k in range(n):
-            tree[f"group{g}"][f"g{g}c{k}"] = {}
-            cmap[f"g{g}c{k}"] = v
-            v += 10
-    return tree, cmap
-
-
-def _check(out, logits, tree, cmap, model_type, what, check_confidence=True):
-    """a RaggedLabels against the oracle on the same logits (list of CPU [B,C_L,S,S]); prints every figure it asserts"""
-    maps, confs = out.unpack(), out.unpack_confidence()
-    sizes = [(H, W) for _, H, W, _ in out.desc_host.tolist()]
-    masked = total = 0
-    d32 = dgot = 0.0
-    for b, (H, W) in enumerate(sizes):
+def _check(out, logits, tree, cmap, model_type, what):
+    """a RaggedLabels against the oracle on the same logits (list of CPU [B,C_L,S,S]): the harness' rule on the fp64 and fp32
+    evaluations of tests/decode_ref.py"""
+    samples = []
+    for b, (_, H, W, _) in enumerate(out.desc_host.tolist()):
         zb = [z[b] for z in logits]
-        want, conf, tie, _ = R.decode_sample(zb, tree, cmap, model_type, H, W)
-        assert maps[b].shape == (H, W) and maps[b].dtype == np.uint8
-        keep = ~tie
-        got = torch.from_numpy(maps[b])
-        wrong = int(((got != want) & keep).sum())
-        print(f"{what} sample {b} {H}x{W}: {int(tie.sum())} near ties, {wrong} labels differ outside them")
-        assert wrong == 0, (what, b, wrong)
-        masked += int(tie.sum())
-        total += H * W
-        if check_confidence:
-            _, conf32, _, _ = R.decode_sample(zb, tree, cmap, model_type, H, W, dtype=torch.float32)
-            d32 = max(d32, float((conf32.double() - conf).abs()[keep].max()))
-            dgot = max(dgot, float((torch.from_numpy(confs[b]).double() - conf).abs()[keep].max()))
-    print(f"{what}: mask {masked}/{total}")
-    assert masked <= MASK_CAP * total, (what, masked, total)
-    if check_confidence:
-        bar = max(4.0 * d32, 1e-6)
-        print(f"{what}: confidence distance from fp64: device {dgot:.3e}, torch-CPU fp32 {d32:.3e}, bar {bar:.3e}")
-        assert dgot <= bar, (what, dgot, d32)
+        want, conf, tie, path = R.decode_sample(zb, tree, cmap, model_type, H, W)
+        samples.append((want, conf, tie, path, R.decode_sample(zb, tree, cmap, model_type, H, W, dtype=torch.float32)[1]))
+    check(out, samples, what)
 
 
 def _run(tree, cmap, model_type, S, sizes, seed, what):
@@ -91,6 +51,14 @@ def test_620_to_two_panoramics_tl_tree():
 def test_ragged_up_and_downsampling_both_trees(key, model_type):
     tree, cmap = _tree(key)
     _run(tree, cmap, model_type, 62, RAGGED, 1 + model_type, f"62->ragged {key} model_type {model_type}")
+
+
+@pytest.mark.parametrize("key", ["tl", "ext"])
+def test_a_block_that_takes_a_second_tile(key):
+    """one 4100 x 250 map: 1025 tiles for the 1024 blocks of a batch of one, so block 0 runs its tile loop twice (the logits
+    of the bit-identity tests of the multi-view and window decodes at this size: seed 40 + model_type)"""
+    tree, cmap = _tree(key)
+    _run(tree, cmap, 1, 62, STRIDED, 41, f"62->4100x250 {key}")
 
 
 def test_level_of_16_channels():
@@ -180,14 +148,6 @@ def test_argument_checks_raise_without_launching():
 
 
 # ----------------------------------------------------------------------------------------------------------- end to end
-def _source(rng, H, W, ch):
-    yy, xx = np.mgrid[0:H, 0:W]
-    base = (96 + 80 * np.sin(xx / (7.0 + W / 40)) * np.cos(yy / (5.0 + H / 50)))[..., None]
-    noise = rng.integers(-60, 61, size=(H, W, ch))
-    img = np.clip(base + noise + np.array([0, 25, -25][:ch]), 0, 255).astype(np.uint8)
-    return img[..., 0] if ch == 1 else img
-
-
 @pytest.mark.parametrize("kind,size", [("unet", 62), ("hrnet", 64)])
 def test_predictor_matches_the_oracle_on_its_own_logits(kind, size, tmp_path):
     from PIL import Image

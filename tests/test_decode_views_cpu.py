@@ -1,7 +1,6 @@
 """Multi-view decode (test-time augmentation), the parts that need no GPU: the float64 oracle (tests/decode_views_ref.py)
 against the single-view oracle and under flipped copies, the near-tie share of every case the GPU test compares with it,
 predictEval.TestTimeAugment, and the compile-time resources of the decode_views kernels."""
-import csv
 import os
 
 import pytest
@@ -9,16 +8,8 @@ import torch
 
 from tests import decode_ref as R
 from tests import decode_views_ref as V
-from tests.helpers import DATA, load_tree
-from tests.test_build_audit import HIPCC, _resources
-
-TREES = {"tl": ("class_tree_tl.json", "class_map.csv"), "ext": ("class_tree_tl_extended.json", "class_map_extended.csv")}
-
-
-def _tree(key):
-    t, m = TREES[key]
-    with open(os.path.join(DATA, m)) as f:
-        return load_tree(t), list(csv.DictReader(f))
+from tests.decode_harness import _tree
+from tests.helpers import HIPCC, _resources
 
 
 def _same(a, b):

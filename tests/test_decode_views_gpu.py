@@ -2,15 +2,13 @@
 Data.DeviceDecode.decode_views, predictEval.Predictor(tta=...)) against the float64 torch-CPU oracle
 (tests/decode_views_ref.py) and against the single-view decode.
 
-Oracle parity: labels equal outside the oracle's near-tie mask (gap of the deciding group below 2e-4; at most 0.5 % of
+Oracle parity (tests/decode_harness.py): labels equal outside the oracle's near-tie mask (gap of the deciding group below 2e-4; at most 0.5 % of
 a case's pixels, and tests/test_decode_views_cpu.py shows every case far below that); confidence outside the mask
 within 4x the largest distance of the fp32 torch-CPU evaluation of the same formula from the fp64 one (floor 1e-6).
 Bit identities need no oracle: one unflipped view IS the single-view decode, and so are flipped copies of one logit set
 (mirrored taps read the same values, and the fp32 mean of 2 or 4 equal values is exact)."""
 import argparse
-import csv
 import ctypes
-import os
 
 import numpy as np
 import pytest
@@ -18,47 +16,16 @@ import torch
 
 from tests import decode_ref as R
 from tests import decode_views_ref as V
-from tests.helpers import DATA, build_model, load_tree
+from tests.decode_harness import EDGE, IDENTITY, STRIDED, _source, _tree, check
+from tests.helpers import build_model
 
 pytestmark = pytest.mark.gpu
 
-TREES = {"tl": ("class_tree_tl.json", "class_map.csv"), "ext": ("class_tree_tl_extended.json", "class_map_extended.csv")}
-EDGE = [(7, 3), (1, 1), (3, 9), (2, 260)]          # misaligned rows, rows narrower than a lane, a row crossing a tile
-IDENTITY = [(62, 62)] * 3
 FLIP_SETS = {"one": [0], "h": [0, 1], "v": [0, 2], "all": [0, 1, 2, 3]}
-
-
-def _tree(key):
-    t, m = TREES[key]
-    with open(os.path.join(DATA, m)) as f:
-        return load_tree(t), list(csv.DictReader(f))
 
 
 def _cuda(views):
     return [([z.cuda() for z in logits], f) for logits, f in views]
-
-
-def _check(out, samples, what):
-    """a RaggedLabels against oracle_batch's per-sample results; prints every figure it asserts"""
-    maps, confs = out.unpack(), out.unpack_confidence()
-    masked = total = 0
-    d32 = dgot = 0.0
-    for b, (want, conf, tie, _, conf32) in enumerate(samples):
-        H, W = want.shape
-        assert maps[b].shape == (H, W) and maps[b].dtype == np.uint8
-        keep = ~tie
-        wrong = int(((torch.from_numpy(maps[b]) != want) & keep).sum())
-        print(f"{what} sample {b} {H}x{W}: {int(tie.sum())} near ties, {wrong} labels differ outside them")
-        assert wrong == 0, (what, b, wrong)
-        masked += int(tie.sum())
-        total += H * W
-        d32 = max(d32, float((conf32.double() - conf).abs()[keep].max()))
-        dgot = max(dgot, float((torch.from_numpy(confs[b]).double() - conf).abs()[keep].max()))
-    print(f"{what}: mask {masked}/{total}")
-    assert masked <= V.MASK_CAP * total, (what, masked, total)
-    bar = max(4.0 * d32, 1e-6)
-    print(f"{what}: confidence distance from fp64: device {dgot:.3e}, torch-CPU fp32 {d32:.3e}, bar {bar:.3e}")
-    assert dgot <= bar, (what, dgot, d32)
 
 
 # -------------------------------------------------------------------------------------------------------- oracle parity
@@ -71,13 +38,13 @@ def test_views_match_the_oracle(key, model_type, vs):
         assert dec.tables.C == [4, 16]
     dev = _cuda(views)
     out = dec.decode_views_sizes(dev, V.RAGGED, want_confidence=True)
-    _check(out, samples, f"{key} model_type {model_type} views {vs}")
+    check(out, samples, f"{key} model_type {model_type} views {vs}")
     plain = dec.decode_views_sizes(dev, V.RAGGED)                              # the kernel without the confidence
     assert plain.confidence is None and torch.equal(plain.labels, out.labels)
 
 
 # ------------------------------------------------------------------------------------------------------- bit identities
-@pytest.mark.parametrize("sizes", [V.RAGGED, EDGE, IDENTITY], ids=["ragged", "edge", "identity"])
+@pytest.mark.parametrize("sizes", [V.RAGGED, EDGE, IDENTITY, STRIDED], ids=["ragged", "edge", "identity", "strided"])
 @pytest.mark.parametrize("key,model_type", [("tl", 1), ("ext", 1), ("ext", 0)])
 def test_one_view_and_flipped_copies_are_the_single_view_decode(key, model_type, sizes):
     from hrseg_amd.Data import DeviceDecode
@@ -220,14 +187,6 @@ def test_argument_checks_raise_without_launching():
 
 
 # ----------------------------------------------------------------------------------------------------------- end to end
-def _source(rng, H, W, ch):
-    yy, xx = np.mgrid[0:H, 0:W]
-    base = (96 + 80 * np.sin(xx / (7.0 + W / 40)) * np.cos(yy / (5.0 + H / 50)))[..., None]
-    noise = rng.integers(-60, 61, size=(H, W, ch))
-    img = np.clip(base + noise + np.array([0, 25, -25][:ch]), 0, 255).astype(np.uint8)
-    return img[..., 0] if ch == 1 else img
-
-
 @pytest.mark.parametrize("kind,size", [("unet", 62), ("hrnet", 64)])
 def test_predictor_with_tta_end_to_end(kind, size):
     from hrseg_amd import _lib
@@ -272,7 +231,7 @@ def test_predictor_with_tta_end_to_end(kind, size):
     views = [([z.detach().float().cpu() for z in logits], f) for logits, f in kept]
     sizes = [s[:2] for s in shapes]
     assert [(H, W) for _, H, W, _ in out.desc_host.tolist()] == sizes
-    _check(out, V.oracle_batch(views, tree, cmap, 1, sizes), f"predictor tta {kind}")
+    check(out, V.oracle_batch(views, tree, cmap, 1, sizes), f"predictor tta {kind}")
     again = predictor.decoder.decode_views(kept, out.desc_host, None, True)          # the decode adds no convolution launch
     assert _lib.launch_count() == convs and torch.equal(again.labels, out.labels)
     leaf_values = set(predictor.decoder.leaf_values)

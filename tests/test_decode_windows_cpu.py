@@ -2,7 +2,6 @@
 last window, the refusals), the blend profile, the float64 oracle (tests/window_ref.py) against the single-window oracle and
 on windows cut from one global logit field, the near-tie share of every case the GPU test compares with the oracle, and the
 compile-time resources of the kernels."""
-import csv
 import os
 
 import pytest
@@ -10,16 +9,8 @@ import torch
 
 from tests import decode_ref as R
 from tests import window_ref as WR
-from tests.helpers import DATA, load_tree
-from tests.test_build_audit import HIPCC, _resources
-
-TREES = {"tl": ("class_tree_tl.json", "class_map.csv"), "ext": ("class_tree_tl_extended.json", "class_map_extended.csv")}
-
-
-def _tree(key):
-    t, m = TREES[key]
-    with open(os.path.join(DATA, m)) as f:
-        return load_tree(t), list(csv.DictReader(f))
+from tests.decode_harness import _tree
+from tests.helpers import HIPCC, _resources
 
 
 # ------------------------------------------------------------------------------------------------------------- the plan

@@ -2,7 +2,7 @@
 Data.DeviceDecode.decode_windows, predictEval.Predictor(window=...)) against the float64 torch-CPU oracle
 (tests/window_ref.py), against the single-window decode and against the eval-mode resize.
 
-Oracle parity is the rule of tests/test_decode_views_gpu.py: labels equal outside the oracle's near-tie mask (gap of the
+Oracle parity is the rule of tests/decode_harness.py: labels equal outside the oracle's near-tie mask (gap of the
 deciding group below 2e-4; at most 0.5 % of a call's pixels, and tests/test_decode_windows_cpu.py shows every call far below
 that); confidence outside the mask within 4x the largest distance of the fp32 torch-CPU evaluation of the same formula from the
 fp64 one (floor 1e-6).  Bit identities need no oracle: one window per image with the all-ones profile IS the single-window
@@ -17,9 +17,8 @@ import torch.nn.functional as F
 
 from tests import decode_ref as R
 from tests import window_ref as WR
-from tests.decode_views_ref import RAGGED
+from tests.decode_harness import EDGE, IDENTITY, RAGGED, STRIDED, _source, _tree, check
 from tests.helpers import build_model
-from tests.test_decode_views_gpu import EDGE, IDENTITY, _check, _source, _tree
 
 pytestmark = pytest.mark.gpu
 
@@ -43,13 +42,13 @@ def test_windows_match_the_oracle(key, model_type, overlap, blend):
         assert plan.nwindows == logits[0].shape[0] and plan.first_window(3) > 3, "four images per call: the n0 offsets matter"
         dev = [z.cuda() for z in logits]
         out = dec.decode_windows_sizes(dev, plan, prof, sizes, want_confidence=True)
-        _check(out, samples, f"{key} model_type {model_type} overlap {overlap} {blend} call {batch}")
+        check(out, samples, f"{key} model_type {model_type} overlap {overlap} {blend} call {batch}")
         plain = dec.decode_windows_sizes(dev, plan, prof, sizes)                    # the kernel without the confidence
         assert plain.confidence is None and torch.equal(plain.labels, out.labels)
 
 
 # ------------------------------------------------------------------------------------------------------- bit identities
-@pytest.mark.parametrize("sizes", [RAGGED, EDGE, IDENTITY], ids=["ragged", "edge", "identity"])
+@pytest.mark.parametrize("sizes", [RAGGED, EDGE, IDENTITY, STRIDED], ids=["ragged", "edge", "identity", "strided"])
 @pytest.mark.parametrize("key,model_type", [("tl", 1), ("ext", 1), ("ext", 0)])
 def test_one_window_with_the_uniform_profile_is_the_single_window_decode(key, model_type, sizes):
     from hrseg_amd.Data import DeviceDecode
@@ -330,7 +329,7 @@ def test_predictor_with_windows_end_to_end(kind, size):
     canvases = [plan.canvas(m) for m in range(2)]
     assert [(H, W) for _, H, W, _ in out.desc_host.tolist()] == sizes
     stride, prof = WR.stride_of(size, 0.5), WR.profile(size, "hann")
-    _check(out, WR.oracle_batch(cpu, canvases, sizes, size, stride, prof, tree, cmap, 1), f"predictor windows {kind}")
+    check(out, WR.oracle_batch(cpu, canvases, sizes, size, stride, prof, tree, cmap, 1), f"predictor windows {kind}")
     again = predictor.decoder.decode_windows(logits, plan, window.profile(size), out.desc_host, None, True)
     assert _lib.launch_count() == convs and torch.equal(again.labels, out.labels), "the decode adds no convolution launch"
     leaf_values = set(predictor.decoder.leaf_values)
@@ -342,7 +341,7 @@ def test_predictor_with_windows_end_to_end(kind, size):
     scores = predictor.score(imgs, gts)
     maps = predictor.last_labels
     assert [(H, W) for _, H, W, _ in maps.desc_host.tolist()] == [(100, 150), (33, 47)]
-    _check(maps, WR.oracle_batch([z.detach().float().cpu() for z in predictor.last_window_logits[0]], canvases,
+    check(maps, WR.oracle_batch([z.detach().float().cpu() for z in predictor.last_window_logits[0]], canvases,
                                  [(100, 150), (33, 47)], size, stride, prof, tree, cmap, 1), f"predictor windows {kind} score")
     buf, ghost = pack_images(gts)
     want = DeviceScore(tree, cmap).score(maps, (buf, ghost, ghost))

@@ -9,19 +9,17 @@ import pytest
 import torch
 
 from tests import score_ref as R
-from tests.helpers import DATA, build_model, load_tree
+from tests.decode_harness import _source
+from tests.decode_harness import _tree as _shipped_tree
+from tests.helpers import build_model
 
 pytestmark = pytest.mark.gpu
-
-TREES = {"tl": ("class_tree_tl.json", "class_map.csv"), "ext": ("class_tree_tl_extended.json", "class_map_extended.csv")}
 
 
 def _tree(key):
     if key in ("wide", "chain", "flat", "uniform"):
         return {"wide": R.wide_tree, "chain": R.chain_tree, "flat": R.flat_tree, "uniform": R.uniform_tree}[key]()
-    t, m = TREES[key]
-    with open(os.path.join(DATA, m)) as f:
-        return load_tree(t), list(csv.DictReader(f))
+    return _shipped_tree(key)
 
 
 def _values(cmap):
@@ -221,13 +219,6 @@ def test_argument_checks_raise_without_launching():
 
 
 # ----------------------------------------------------------------------------------------------------------- end to end
-def _source(rng, H, W, ch):
-    yy, xx = np.mgrid[0:H, 0:W]
-    base = (96 + 80 * np.sin(xx / (7.0 + W / 40)) * np.cos(yy / (5.0 + H / 50)))[..., None]
-    img = np.clip(base + rng.integers(-60, 61, size=(H, W, ch)) + np.array([0, 25, -25][:ch]), 0, 255).astype(np.uint8)
-    return img[..., 0] if ch == 1 else img
-
-
 def _blocky(rng, vals, H, W):
     coarse = rng.choice(vals, size=(H // 6 + 1, W // 6 + 1))
     return np.ascontiguousarray(np.repeat(np.repeat(coarse, 6, 0), 6, 1)[:H, :W])
