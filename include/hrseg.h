@@ -199,16 +199,9 @@ int hrseg_weight_transpose(const float* w, float* wt, int Cout, int taps, int Ci
 /* ------------------------------------------------------------------ batch norm
  * Replaces nn.BatchNorm2d / SyncBatchNorm-without-process-group in training
  * mode (Models/models.py:114,117; bn_helper.py:4-11; BN_MOMENTUM :318) fused
- * with the ReLU / residual add that follows it (:115,118,345,353-354,542).   */
-/* per-channel partial sums of y and y*y over pixel chunks -> partial[nchunks][2][C] (double) */
-int hrseg_bn_stats(const float* y, int ldy, long npix, int C, double* partial, int nchunks,
-                   hrseg_stream_t stream);
-/* reduce partials; write mean,rstd,scale,shift ([4][C] fp32 in `coef`); update
- * running stats (momentum, unbiased var) and ++num_batches_tracked if given. */
-int hrseg_bn_finalize(const double* partial, int nchunks, long npix, int C, const float* gamma,
-                      const float* beta, float* running_mean, float* running_var,
-                      int64_t* num_batches_tracked, float momentum, float eps, float* coef,
-                      hrseg_stream_t stream);
+ * with the ReLU / residual add that follows it (:115,118,345,353-354,542).
+ * One implementation: the grouped forms below, which take n = 1 for a single
+ * problem and a phase mask for a single launch of the three.                   */
 /* inference: BatchNorm (running statistics) folded into the convolution in front of it -- w_out[co][:] = w[co][:] * s,
  * b_out[co] = (bias[co] - running_mean[co]) * s + beta[co] with s = gamma[co] / sqrt(running_var[co] + eps); `row` =
  * k*k*Cin floats per output channel (OHWI), bias may be NULL.  With hrseg_conv_shape_t.residual / relu the whole
@@ -216,28 +209,13 @@ int hrseg_bn_finalize(const double* partial, int nchunks, long npix, int C, cons
 int hrseg_bn_fold(const float* w, const float* bias, const float* gamma, const float* beta, const float* running_mean,
                   const float* running_var, float eps, int Cout, int row, float* w_out, float* b_out,
                   hrseg_stream_t stream);
-/* eval mode: coef from running stats */
-int hrseg_bn_eval_coef(const float* gamma, const float* beta, const float* running_mean,
-                       const float* running_var, float eps, int C, float* coef,
-                       hrseg_stream_t stream);
-/* z = relu?( y*scale + shift (+ residual) ) */
-int hrseg_bn_apply(const float* y, int ldy, const float* coef, const float* residual, int ldr,
-                   int relu, float* z, int ldz, long npix, int C, hrseg_stream_t stream);
-/* backward, phase 1: g = dz * (z>0 if relu); partial sums of g and g*xhat */
-int hrseg_bn_bwd_reduce(const float* dz, int lddz, const float* z, int ldz, int relu,
-                        const float* y, int ldy, const float* coef, long npix, int C,
-                        double* partial, int nchunks, hrseg_stream_t stream);
-/* backward, phase 2: dgamma += sum g*xhat, dbeta += sum g (if not NULL);
- * dy = gamma*rstd*(g - mean_g - xhat*mean_gx); optionally dres (+)= g.
- * `partial` must hold (nchunks+1)*2*C doubles: the last [2][C] receives the totals. */
-int hrseg_bn_bwd_apply(const double* partial, int nchunks, const float* dz, int lddz,
-                       const float* z, int ldz, int relu, const float* y, int ldy,
-                       const float* coef, const float* gamma, float* dgamma, float* dbeta,
-                       float* dy, int lddy, float* dres, int lddres, int dres_accumulate,
-                       long npix, int C, int eval_mode, hrseg_stream_t stream);
-
-/* Grouped forms: n (1..8) independent BatchNorm problems in three launches (statistics, finalize,
- * apply; eval: coefficients, apply) resp. (reduce, finalize, apply) for the backward. */
+/* n (1..8) independent BatchNorm problems in three launches (statistics, finalize, apply; eval: coefficients,
+ * apply) resp. (reduce, finalize, apply) for the backward.
+ * Forward: partial[nchunks][2][C] (double) receives the per-channel sums of y and y*y over pixel chunks; the finalize
+ * reduces them, writes mean, rstd, scale, shift ([4][C] fp32 in `coef`), updates the running statistics (momentum,
+ * unbiased variance) and num_batches_tracked if given; the apply is z = relu?( y*scale + shift (+ residual) ).
+ * Backward: g = dz * (z>0 if relu); partial sums of g and g*xhat; dgamma += sum g*xhat, dbeta += sum g (if not NULL);
+ * dy = gamma*rstd*(g - mean_g - xhat*mean_gx); optionally dres (+)= g. */
 typedef struct {
   const float* y; int ldy; long npix; int C;       /* conv output [npix][C]                      */
   const float* gamma; const float* beta;
@@ -273,7 +251,9 @@ typedef struct {
 int hrseg_bn_fwd_group(int n, const hrseg_bn_fwd_t* problems, int training, hrseg_stream_t stream);
 /* the same in phases (bit 0 statistics, bit 1 finalize / eval coefficients, bit 2 apply; 7 = all): a caller that
  * synchronises BatchNorm statistics across ranks runs phase 1, all-reduces `partial`, then runs phases 2|4 with
- * stat_ranks set (the reference's SyncBatchNorm would do this WITH a process group; it never has one) */
+ * stat_ranks set (the reference's SyncBatchNorm would do this WITH a process group; it never has one).
+ * A problem needs only what its phases touch: y with bit 0 (training) or bit 2; z, ldz with bit 2; partial / nchunks in
+ * training with bit 0 or 1; the running statistics in eval with bit 1; coef always. */
 int hrseg_bn_fwd_group_phases(int n, const hrseg_bn_fwd_t* problems, int training, int phases, hrseg_stream_t stream);
 typedef struct {
   const float* dz; int lddz; const float* z; int ldz; int relu;   /* relu with z == NULL: the forward had

@@ -77,13 +77,7 @@ PROTOTYPES = {
     "hrseg_conv_wgrad_group_ws": [_i, _p, _p, _p, C.POINTER(ConvShape), _p, C.c_size_t, _p],
     "hrseg_weight_transpose": [_p, _p, _i, _i, _i, _p],
     "hrseg_weight_transpose_all": [_p, _p, _p, _i, _p],
-    "hrseg_bn_stats": [_p, _i, _l, _i, _p, _i, _p],
-    "hrseg_bn_finalize": [_p, _i, _l, _i, _p, _p, _p, _p, _p, _f, _f, _p, _p],
-    "hrseg_bn_eval_coef": [_p, _p, _p, _p, _f, _i, _p, _p],
     "hrseg_bn_fold": [_p, _p, _p, _p, _p, _p, _f, _i, _i, _p, _p, _p],
-    "hrseg_bn_apply": [_p, _i, _p, _p, _i, _i, _p, _i, _l, _i, _p],
-    "hrseg_bn_bwd_reduce": [_p, _i, _p, _i, _i, _p, _i, _p, _l, _i, _p, _i, _p],
-    "hrseg_bn_bwd_apply": [_p, _i, _p, _i, _p, _i, _i, _p, _i, _p, _p, _p, _p, _p, _i, _p, _i, _i, _l, _i, _i, _p],
     "hrseg_bn_fwd_group": [_i, C.POINTER(BnFwd), _i, _p],
     "hrseg_bn_bwd_group": [_i, C.POINTER(BnBwd), _i, _p],
     "hrseg_bn_fwd_group_phases": [_i, C.POINTER(BnFwd), _i, _i, _p],
@@ -285,7 +279,7 @@ for _name, _args in PROTOTYPES.items():
     _fn[_name] = f
 
 
-ABI_VERSION = 15    # must equal hrseg_abi_version() of the built library (struct layouts above)
+ABI_VERSION = 16    # must equal hrseg_abi_version() of the built library (struct layouts above)
 
 
 raw = {}

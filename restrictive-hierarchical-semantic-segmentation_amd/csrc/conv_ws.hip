@@ -758,7 +758,7 @@ __device__ __forceinline__ void igemm_patch_ws_body(const IgemmArgs& p, unsigned
   }
   if (stat) {
     // every consumer has added its last tile (LDS atomics complete before the barrier); the block's sums go out as row
-    // `block_row` of the partial buffer [rows][2][N], which hrseg_bn_finalize adds up in row order
+    // `block_row` of the partial buffer [rows][2][N], which the BatchNorm finalize phase (hrseg_bn_fwd_group_phases) adds up in row order
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     double* row = p.stat_partial + (size_t)block_row * 2 * p.N;

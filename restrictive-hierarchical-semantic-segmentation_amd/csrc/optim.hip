@@ -1,6 +1,9 @@
-// Global-norm gradient clipping and the non-finite step skip of the fused AdamW, for gfx950.
+// The optimiser on flat fp32 buffers, for gfx950: AdamW (host scalars, or step count and hyper-parameters in device memory),
+// global-norm gradient clipping with the non-finite step skip, the weight EMA, and the fill that zeroes its buffers.
+// adamw_body is the spelling of the update: an AdamW kernel here is loads of its scalars plus that body, so the variants
+// round alike by construction -- except adamw_dev_kernel, which keeps the same text written out (measured reason there).
 //
-// Three launches over the flat gradient buffer g[n] that AdamW is about to consume:
+// Clipping: three launches over the flat gradient buffer g[n] that AdamW is about to consume:
 //   1. grad_sumsq_kernel       partial[c] = sum over chunk c of (double)g_i * (double)g_i
 //   2. grad_clip_finalize_kernel  S = sum of the partials in a fixed order -> clip = {norm, coef, finite, skipped_total},
 //                              and the work of adam_tick_kernel (advance state) unless the step is void
@@ -14,16 +17,13 @@
 // gradient can neither overflow nor underflow the sum (|g| <= 3.4e38 -> g^2 <= 1.2e77, n <= 2^63; the smallest
 // subnormal squared is 2e-90), and S is finite exactly when every element is.
 //
-// Weight EMA (second half of this file): the shadow e[n] of the parameters is advanced by the update kernel itself
+// Weight EMA: the shadow e[n] of the parameters is advanced by the update kernel itself
 // (adamw_dev_ema_kernel / adamw_dev_clip_ema_kernel: one more 16-byte load and store per element group, no launch of
 // its own), by ema_update_kernel for an already updated p, and exchanged with p by swap_kernel.
-#include "common.h"
+#include "elem_common.h"   // ld4 / st4, flat_blocks, al16
 
 #define GRAD_CHUNK 8192          // floats per partial: 256 threads x 8 pieces of 16 bytes
 #define GRAD_MAX_BLOCKS 2048     // 256 CUs x 8 resident blocks of 256 threads; more chunks than this: a block takes several
-
-__device__ __forceinline__ f32x4 gc_ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void gc_st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 
 __device__ __forceinline__ double sq4(double acc, f32x4 v) {
 #pragma unroll
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict
     if (lo + GRAD_CHUNK <= n) {                   // block-uniform: eight unguarded 16-byte loads in flight per thread
       f32x4 v[8];
 #pragma unroll
-      for (int k = 0; k < 8; ++k) v[k] = gc_ld4(src + 4 * (t + 256 * k));
+      for (int k = 0; k < 8; ++k) v[k] = ld4(src + 4 * (t + 256 * k));
       __builtin_amdgcn_sched_barrier(0);          // all eight loads are issued before the first one is waited for
 #pragma unroll
       for (int k = 0; k < 8; ++k) acc = sq4(acc, v[k]);
@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict
       // scalar select read a stale condition code and this path ran with the full length (caught by the n = 1 test)
       const int len = (int)(n - lo);
       const int nvec = len >> 2;
-      for (int i = t; i < nvec; i += 256) acc = sq4(acc, gc_ld4(src + 4 * i));
+      for (int i = t; i < nvec; i += 256) acc = sq4(acc, ld4(src + 4 * i));
       const int tail = len & 3;
       if (t < tail) {
         const double d = (double)src[4 * nvec + t];
@@ -69,8 +69,20 @@ __global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict
   }
 }
 
-// hyper = {lr, beta1, beta2, eps, weight_decay, grad_scale}; clipcfg = {max_norm, skip_nonfinite};
-// state = {step, bc1, 1/sqrt(bc2)}; clip = {norm, coef, finite, skipped_total}
+// Graph-replayable AdamW: step count and hyper-parameters live in device memory, so a captured
+// launch picks up the next step's bias correction and a scheduler's new lr on every replay.
+// hyper = {lr, beta1, beta2, eps, weight_decay, grad_scale}; state = {step, bc1, 1/sqrt(bc2)}
+__device__ __forceinline__ void adam_tick(float* state, const float* hyper) {
+  const double step = (double)state[0] + 1.0;
+  state[0] = (float)step;
+  state[1] = (float)(1.0 - pow((double)hyper[1], step));
+  state[2] = (float)(1.0 / sqrt(1.0 - pow((double)hyper[2], step)));
+}
+__global__ void adam_tick_kernel(float* state, const float* hyper) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) adam_tick(state, hyper);
+}
+
+// clipcfg = {max_norm, skip_nonfinite}; clip = {norm, coef, finite, skipped_total}
 __global__ __launch_bounds__(256) void grad_clip_finalize_kernel(const double* __restrict__ partial, int nchunks,
                                                                  const float* __restrict__ hyper,
                                                                  const float* __restrict__ clipcfg, float* state,
@@ -96,11 +108,8 @@ __global__ __launch_bounds__(256) void grad_clip_finalize_kernel(const double* _
   clip[2] = finite ? 1.f : 0.f;
   if (is_void) {
     clip[3] = clip[3] + 1.f;
-  } else {                                        // adam_tick_kernel
-    const double step = (double)state[0] + 1.0;
-    state[0] = (float)step;
-    state[1] = (float)(1.0 - pow((double)hyper[1], step));
-    state[2] = (float)(1.0 / sqrt(1.0 - pow((double)hyper[2], step)));
+  } else {
+    adam_tick(state, hyper);
   }
 }
 
@@ -116,34 +125,34 @@ __device__ __forceinline__ float ema_alpha(const float* __restrict__ state, cons
 // kernels and ema_update_kernel round alike whatever the compiler would contract on its own.
 __device__ __forceinline__ float ema_line(float e, float p, float alpha) { return __builtin_fmaf(p - e, alpha, e); }
 
-// One element group of the update.  CLIP = false is, expression by expression, the body of adamw_dev_kernel
-// (bn_elem.hip), so that a step whose coef is exactly 1 rounds exactly as that kernel does.  EMA = true appends the shadow's
-// update on the p' just computed (still in its registers); p, m, v are computed and stored as with EMA = false.
+// AdamW over one flat buffer (torch.optim.AdamW single-tensor semantics; step = lr / bc1).  CLIP = true scales the gradient
+// by coef as well; a step whose coef is exactly 1 takes CLIP = false and so rounds exactly as the plain update does.  EMA = true
+// appends the shadow's update on the p' just computed (still in its registers); p, m, v are computed and stored as with EMA = false.
 template <bool CLIP, bool EMA = false>
-__device__ __forceinline__ void adamw_clip_body(float* __restrict__ p, const float* __restrict__ g,
+__device__ __forceinline__ void adamw_body(float* __restrict__ p, const float* __restrict__ g,
                                                 float* __restrict__ m, float* __restrict__ v, long n4, long n, float lr,
                                                 float b1, float b2, float eps, float wd, float gscale, float coef,
                                                 float step, float rsqrt_bc2, float* __restrict__ e = nullptr,
                                                 float alpha = 0.f) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-    f32x4 pp = gc_ld4(p + 4 * i), gg = gc_ld4(g + 4 * i) * gscale, mm = gc_ld4(m + 4 * i), vv = gc_ld4(v + 4 * i);
+    f32x4 pp = ld4(p + 4 * i), gg = ld4(g + 4 * i) * gscale, mm = ld4(m + 4 * i), vv = ld4(v + 4 * i);
     if (CLIP) gg = gg * coef;
     pp = pp * (1.f - lr * wd);
-    mm = mm + (gg - mm) * (1.f - b1);
+    mm = mm + (gg - mm) * (1.f - b1);          // lerp, as torch: m.lerp_(g, 1-b1)
     vv = vv * b2 + gg * gg * (1.f - b2);
 #pragma unroll
     for (int j = 0; j < 4; ++j) pp[j] -= step * mm[j] / (sqrtf(vv[j]) * rsqrt_bc2 + eps);
-    gc_st4(p + 4 * i, pp);
-    gc_st4(m + 4 * i, mm);
-    gc_st4(v + 4 * i, vv);
+    st4(p + 4 * i, pp);
+    st4(m + 4 * i, mm);
+    st4(v + 4 * i, vv);
     if (EMA) {
-      f32x4 ee = gc_ld4(e + 4 * i);
+      f32x4 ee = ld4(e + 4 * i);
 #pragma unroll
       for (int j = 0; j < 4; ++j) ee[j] = ema_line(ee[j], pp[j], alpha);
-      gc_st4(e + 4 * i, ee);
+      st4(e + 4 * i, ee);
     }
   }
-  if (blockIdx.x == 0 && threadIdx.x < (n - 4 * n4)) {
+  if (blockIdx.x == 0 && threadIdx.x < (n - 4 * n4)) {  // tail
     const long i = 4 * n4 + threadIdx.x;
     float pp = p[i] * (1.f - lr * wd), gg = g[i] * gscale;
     if (CLIP) gg = gg * coef;
@@ -160,6 +169,47 @@ __device__ __forceinline__ void adamw_clip_body(float* __restrict__ p, const flo
   }
 }
 
+// host scalars
+__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                    float* __restrict__ m, float* __restrict__ v, long n4, long n,
+                                                    float lr, float b1, float b2, float eps, float wd, float bc1,
+                                                    float rsqrt_bc2, float gscale) {
+  adamw_body<false>(p, g, m, v, n4, n, lr, b1, b2, eps, wd, gscale, 1.f, lr / bc1, rsqrt_bc2);
+}
+
+__global__ __launch_bounds__(256) void adamw_dev_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                        float* __restrict__ m, float* __restrict__ v, long n4, long n,
+                                                        const float* __restrict__ hyper,
+                                                        const float* __restrict__ state) {
+  const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4], gscale = hyper[5];
+  const float step = lr / state[1], rsqrt_bc2 = state[2];
+  // adamw_body<false>, written out.  Built on the template this kernel -- the one every default training step launches -- reads
+  // blockDim with a vector load from the dispatch packet ahead of its loop (as the clip / EMA kernels do) instead of a scalar
+  // load of the kernel arguments: 6 instructions more, same loop.  Measured on MI355X, medians of three alternating runs, us per
+  // call: 65.9 M elements 318.2 -> 321.4 (parent's own spread 4.2), 13.4 M elements 60.14 -> 60.81 (spread 0.48): outside the
+  // spread at the smaller size and above the parent in every pair, so the step's kernel keeps its own text.
+  // tests/test_gradclip_gpu.py holds the two spellings together bit for bit (adamw_dev against adamw_dev_clip at coef == 1).
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    f32x4 pp = ld4(p + 4 * i), gg = ld4(g + 4 * i) * gscale, mm = ld4(m + 4 * i), vv = ld4(v + 4 * i);
+    pp = pp * (1.f - lr * wd);
+    mm = mm + (gg - mm) * (1.f - b1);
+    vv = vv * b2 + gg * gg * (1.f - b2);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) pp[j] -= step * mm[j] / (sqrtf(vv[j]) * rsqrt_bc2 + eps);
+    st4(p + 4 * i, pp);
+    st4(m + 4 * i, mm);
+    st4(v + 4 * i, vv);
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n - 4 * n4)) {
+    const long i = 4 * n4 + threadIdx.x;
+    float pp = p[i] * (1.f - lr * wd), gg = g[i] * gscale;
+    const float mm = m[i] + (gg - m[i]) * (1.f - b1), vv = v[i] * b2 + gg * gg * (1.f - b2);
+    p[i] = pp - step * mm / (sqrtf(vv) * rsqrt_bc2 + eps);
+    m[i] = mm;
+    v[i] = vv;
+  }
+}
+
 __global__ __launch_bounds__(256) void adamw_dev_clip_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                              float* __restrict__ m, float* __restrict__ v, long n4, long n,
                                                              const float* __restrict__ hyper,
@@ -169,21 +219,11 @@ __global__ __launch_bounds__(256) void adamw_dev_clip_kernel(float* __restrict__
   if (clipcfg[1] != 0.f && clip[2] == 0.f) return;      // void step: p, m, v stay as they are (grid-uniform)
   const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4], gscale = hyper[5];
   const float step = lr / state[1], rsqrt_bc2 = state[2], coef = clip[1];
-  if (coef == 1.f) adamw_clip_body<false>(p, g, m, v, n4, n, lr, b1, b2, eps, wd, gscale, coef, step, rsqrt_bc2);
-  else adamw_clip_body<true>(p, g, m, v, n4, n, lr, b1, b2, eps, wd, gscale, coef, step, rsqrt_bc2);
+  if (coef == 1.f) adamw_body<false>(p, g, m, v, n4, n, lr, b1, b2, eps, wd, gscale, coef, step, rsqrt_bc2);
+  else adamw_body<true>(p, g, m, v, n4, n, lr, b1, b2, eps, wd, gscale, coef, step, rsqrt_bc2);
 }
 
 // --------------------------------------------------------------------------- weight EMA
-// adam_tick_kernel of bn_elem.hip (kernels are not visible across translation units): the same expressions on the same types
-__global__ void adam_tick_ema_kernel(float* state, const float* hyper) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    const double step = (double)state[0] + 1.0;
-    state[0] = (float)step;
-    state[1] = (float)(1.0 - pow((double)hyper[1], step));
-    state[2] = (float)(1.0 / sqrt(1.0 - pow((double)hyper[2], step)));
-  }
-}
-
 __global__ __launch_bounds__(256) void adamw_dev_ema_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                             float* __restrict__ m, float* __restrict__ v,
                                                             float* __restrict__ e, long n4, long n,
@@ -192,7 +232,7 @@ __global__ __launch_bounds__(256) void adamw_dev_ema_kernel(float* __restrict__ 
                                                             const float* __restrict__ emacfg) {
   const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4], gscale = hyper[5];
   const float step = lr / state[1], rsqrt_bc2 = state[2];
-  adamw_clip_body<false, true>(p, g, m, v, n4, n, lr, b1, b2, eps, wd, gscale, 1.f, step, rsqrt_bc2, e,
+  adamw_body<false, true>(p, g, m, v, n4, n, lr, b1, b2, eps, wd, gscale, 1.f, step, rsqrt_bc2, e,
                                ema_alpha(state, emacfg));
 }
 
@@ -208,8 +248,8 @@ __global__ __launch_bounds__(256) void adamw_dev_clip_ema_kernel(float* __restri
   const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4], gscale = hyper[5];
   const float step = lr / state[1], rsqrt_bc2 = state[2], coef = clip[1];
   const float alpha = ema_alpha(state, emacfg);
-  if (coef == 1.f) adamw_clip_body<false, true>(p, g, m, v, n4, n, lr, b1, b2, eps, wd, gscale, coef, step, rsqrt_bc2, e, alpha);
-  else adamw_clip_body<true, true>(p, g, m, v, n4, n, lr, b1, b2, eps, wd, gscale, coef, step, rsqrt_bc2, e, alpha);
+  if (coef == 1.f) adamw_body<false, true>(p, g, m, v, n4, n, lr, b1, b2, eps, wd, gscale, coef, step, rsqrt_bc2, e, alpha);
+  else adamw_body<true, true>(p, g, m, v, n4, n, lr, b1, b2, eps, wd, gscale, coef, step, rsqrt_bc2, e, alpha);
 }
 
 // the shadow's update alone, for a p that has its step behind it (state already advanced)
@@ -218,11 +258,11 @@ __global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ e, 
                                                          const float* __restrict__ emacfg) {
   const float alpha = ema_alpha(state, emacfg);
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-    f32x4 ee = gc_ld4(e + 4 * i);
-    const f32x4 pp = gc_ld4(p + 4 * i);
+    f32x4 ee = ld4(e + 4 * i);
+    const f32x4 pp = ld4(p + 4 * i);
 #pragma unroll
     for (int j = 0; j < 4; ++j) ee[j] = ema_line(ee[j], pp[j], alpha);
-    gc_st4(e + 4 * i, ee);
+    st4(e + 4 * i, ee);
   }
   if (blockIdx.x == 0 && threadIdx.x < (n - 4 * n4)) {
     const long i = 4 * n4 + threadIdx.x;
@@ -233,9 +273,9 @@ __global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ e, 
 // a <-> b, contents not pointers: whoever holds either address (a recorded launch tape) keeps a valid one
 __global__ __launch_bounds__(256) void swap_kernel(float* __restrict__ a, float* __restrict__ b, long n4, long n) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-    const f32x4 aa = gc_ld4(a + 4 * i), bb = gc_ld4(b + 4 * i);
-    gc_st4(a + 4 * i, bb);
-    gc_st4(b + 4 * i, aa);
+    const f32x4 aa = ld4(a + 4 * i), bb = ld4(b + 4 * i);
+    st4(a + 4 * i, bb);
+    st4(b + 4 * i, aa);
   }
   if (blockIdx.x == 0 && threadIdx.x < (n - 4 * n4)) {
     const long i = 4 * n4 + threadIdx.x;
@@ -245,16 +285,46 @@ __global__ __launch_bounds__(256) void swap_kernel(float* __restrict__ a, float*
   }
 }
 
-// 256 threads x 16 bytes, at most 8192 blocks (the grid of the AdamW kernels); n < 4: one block for the tail
-static inline int flat_blocks(long n4) {
-  long blocks = (n4 + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  if (blocks < 1) blocks = 1;
-  return (int)blocks;
+__global__ void fill_kernel(float* p, float v, long n) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) p[i] = v;
 }
-static inline bool al16(const void* q) { return (uintptr_t)q % 16 == 0; }
 
 // --------------------------------------------------------------------------- entry points
+extern "C" int hrseg_fill(float* p, float v, long n, hrseg_stream_t stream) {
+  HRSEG_CHECK_ARG(p && n >= 0, "hrseg_fill: bad arguments");
+  if (n == 0) return 0;
+  long blocks = (n + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(fill_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, p, v, n);
+  HRSEG_LAUNCH_CHECK("fill");
+  return 0;
+}
+
+extern "C" int hrseg_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
+                           float eps, float weight_decay, float bc1, float bc2, float gscale,
+                           hrseg_stream_t stream) {
+  HRSEG_CHECK_ARG(p && g && m && v && n > 0, "hrseg_adamw: bad arguments");
+  HRSEG_CHECK_ARG(al16(p) && al16(g) && al16(m) && al16(v), "hrseg_adamw: buffers must be 16-byte aligned");
+  const long n4 = n / 4;
+  hipLaunchKernelGGL(adamw_kernel, dim3(flat_blocks(n4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4, n, lr, beta1,
+                     beta2, eps, weight_decay, bc1, 1.0f / sqrtf(bc2), gscale);
+  HRSEG_LAUNCH_CHECK("adamw");
+  return 0;
+}
+
+extern "C" int hrseg_adamw_dev(float* p, const float* g, float* m, float* v, long n, const float* hyper, float* state,
+                               hrseg_stream_t stream) {
+  HRSEG_CHECK_ARG(p && g && m && v && hyper && state && n > 0, "hrseg_adamw_dev: bad arguments");
+  HRSEG_CHECK_ARG(al16(p) && al16(g) && al16(m) && al16(v), "hrseg_adamw_dev: buffers must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(64), 0, st, state, hyper);
+  HRSEG_LAUNCH_CHECK("adam_tick");
+  const long n4 = n / 4;
+  hipLaunchKernelGGL(adamw_dev_kernel, dim3(flat_blocks(n4)), dim3(256), 0, st, p, g, m, v, n4, n, hyper, state);
+  HRSEG_LAUNCH_CHECK("adamw_dev");
+  return 0;
+}
+
 extern "C" int hrseg_grad_sumsq_chunk_len(void) { return GRAD_CHUNK; }
 extern "C" int hrseg_grad_sumsq_max_blocks(void) { return GRAD_MAX_BLOCKS; }
 
@@ -265,8 +335,7 @@ extern "C" int hrseg_grad_sumsq_chunks(long n) {
 
 extern "C" int hrseg_grad_sumsq(const float* g, long n, double* partial, int nchunks, hrseg_stream_t stream) {
   HRSEG_CHECK_ARG(g && partial && n > 0, "hrseg_grad_sumsq: bad arguments");
-  HRSEG_CHECK_ARG(((uintptr_t)g % 16 == 0) && ((uintptr_t)partial % 8 == 0),
-                  "hrseg_grad_sumsq: g must be 16-byte aligned, partial 8-byte aligned");
+  HRSEG_CHECK_ARG(al16(g) && ((uintptr_t)partial % 8 == 0), "hrseg_grad_sumsq: g must be 16-byte aligned, partial 8-byte aligned");
   HRSEG_CHECK_ARG(hrseg_grad_sumsq_chunks(n) == nchunks, "hrseg_grad_sumsq: nchunks=%d does not match n=%ld (%ld per chunk)",
                   nchunks, n, (long)GRAD_CHUNK);
   const int blocks = nchunks < GRAD_MAX_BLOCKS ? nchunks : GRAD_MAX_BLOCKS;
@@ -288,14 +357,9 @@ extern "C" int hrseg_grad_clip_finalize(const double* partial, int nchunks, cons
 extern "C" int hrseg_adamw_dev_clip(float* p, const float* g, float* m, float* v, long n, const float* hyper,
                                     const float* state, const float* clipcfg, const float* clip, hrseg_stream_t stream) {
   HRSEG_CHECK_ARG(p && g && m && v && hyper && state && clipcfg && clip && n > 0, "hrseg_adamw_dev_clip: bad arguments");
-  HRSEG_CHECK_ARG(((uintptr_t)p % 16 == 0) && ((uintptr_t)g % 16 == 0) && ((uintptr_t)m % 16 == 0) &&
-                      ((uintptr_t)v % 16 == 0),
-                  "hrseg_adamw_dev_clip: buffers must be 16-byte aligned");
+  HRSEG_CHECK_ARG(al16(p) && al16(g) && al16(m) && al16(v), "hrseg_adamw_dev_clip: buffers must be 16-byte aligned");
   const long n4 = n / 4;
-  long blocks = (n4 + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(adamw_dev_clip_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4, n, hyper,
+  hipLaunchKernelGGL(adamw_dev_clip_kernel, dim3(flat_blocks(n4)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4, n, hyper,
                      state, clipcfg, clip);
   HRSEG_LAUNCH_CHECK("adamw_dev_clip");
   return 0;
@@ -307,8 +371,8 @@ extern "C" int hrseg_adamw_dev_ema(float* p, const float* g, float* m, float* v,
   HRSEG_CHECK_ARG(al16(p) && al16(g) && al16(m) && al16(v) && al16(e), "hrseg_adamw_dev_ema: buffers must be 16-byte aligned");
   HRSEG_CHECK_ARG(e != p && e != g && e != m && e != v, "hrseg_adamw_dev_ema: the shadow must be a buffer of its own");
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(adam_tick_ema_kernel, dim3(1), dim3(64), 0, st, state, hyper);
-  HRSEG_LAUNCH_CHECK("adam_tick_ema");
+  hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(64), 0, st, state, hyper);
+  HRSEG_LAUNCH_CHECK("adam_tick");
   const long n4 = n / 4;
   hipLaunchKernelGGL(adamw_dev_ema_kernel, dim3(flat_blocks(n4)), dim3(256), 0, st, p, g, m, v, e, n4, n, hyper, state, emacfg);
   HRSEG_LAUNCH_CHECK("adamw_dev_ema");

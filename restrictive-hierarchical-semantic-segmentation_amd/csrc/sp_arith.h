@@ -1,6 +1,6 @@
 // Split-precision arithmetic on the 16-bit matrix pipe (gfx950): the piece schemes, the on-the-fly operand split, the piece
 // products and the PRE-SPLIT activation granule.  Included by every unit that splits or joins: the split-precision convolution
-// families (sp_im2col.h, sp_patch.h, conv_sp_*.hip, conv_ws.hip, conv_wgrad_sp.hip) and the BatchNorm / elementwise unit (bn_elem.hip).
+// families (sp_im2col.h, sp_patch.h, conv_sp_*.hip, conv_ws.hip, conv_wgrad_sp.hip) and the BatchNorm unit (bn.hip).
 //
 // v_mfma_f32_16x16x4_f32 runs at 1/16 of the bf16 MFMA rate.  An fp32 value splits EXACTLY into three bf16
 // pieces (8 significand bits each: hi = truncate(x), mid = truncate(x - hi), lo = x - hi - mid), so an fp32

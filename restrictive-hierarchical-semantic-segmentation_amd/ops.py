@@ -249,16 +249,14 @@ def _nchunks(npix, Cn):
     return max(1, min(_BN_MAX_CHUNKS, npix // (8 * p)))
 
 
+# The single-problem forms: one item through the grouped launches (there is no second implementation).
+def _bn_one(y=None, gamma=None, beta=None, rm=None, rv=None, nbt=None, momentum=0.0, eps=0.0, residual=None, relu=False, **kw):
+    return [dict(y=y, gamma=gamma, beta=beta, rm=rm, rv=rv, nbt=nbt, momentum=momentum, eps=eps, residual=residual, relu=relu, **kw)]
+
+
 def bn_train_coef(y, gamma, beta, running_mean, running_var, nbt, momentum, eps):
     """batch statistics of y -> coef [4][C] (mean, rstd, scale, shift); updates running stats."""
-    Cn, npix = y.shape[3], _npix(y)
-    nch = _nchunks(npix, Cn)
-    part = torch.empty(nch * 2 * Cn, dtype=torch.float64, device=y.device)
-    coef = torch.empty(4 * Cn, dtype=torch.float32, device=y.device)
-    call("hrseg_bn_stats", ptr(y), _ld(y), npix, Cn, ptr(part), nch)
-    call("hrseg_bn_finalize", ptr(part), nch, npix, Cn, ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var),
-         ptr(nbt), float(momentum), float(eps), ptr(coef))
-    return coef
+    return bn_fwd_group(_bn_one(y, gamma, beta, running_mean, running_var, nbt, momentum, eps), True, phases=3)[0][1]
 
 
 def bn_fold(w, bias, gamma, beta, running_mean, running_var, eps, cout):
@@ -272,33 +270,18 @@ def bn_fold(w, bias, gamma, beta, running_mean, running_var, eps, cout):
 
 
 def bn_eval_coef(gamma, beta, running_mean, running_var, eps):
-    Cn = running_mean.numel()
-    coef = torch.empty(4 * Cn, dtype=torch.float32, device=running_mean.device)
-    call("hrseg_bn_eval_coef", ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var), float(eps), Cn, ptr(coef))
-    return coef
+    return bn_fwd_group(_bn_one(None, gamma, beta, running_mean, running_var, eps=eps), False, phases=2)[0][1]
 
 
 def bn_apply(y, coef, residual=None, relu=False, out=None):
-    if out is None:
-        out = torch.empty(y.shape, dtype=torch.float32, device=y.device)
-    call("hrseg_bn_apply", ptr(y), _ld(y), ptr(coef), ptr(residual), _ld(residual) if residual is not None else 0,
-         int(relu), ptr(out), _ld(out), _npix(y), y.shape[3])
-    return out
+    return bn_fwd_group(_bn_one(y, residual=residual, relu=relu, out=out, coef=coef), False, phases=4)[0][0]
 
 
 def bn_bwd(dz, z, relu, y, coef, dgamma, dbeta, dres=None, dres_accumulate=False, eval_mode=False, dy_out=None):
-    """-> dy (gradient w.r.t. the conv output); dgamma/dbeta accumulate; dres (+)= g."""
-    Cn, npix = y.shape[3], _npix(y)
-    nch = _nchunks(npix, Cn)
-    part = torch.empty((nch + 1) * 2 * Cn, dtype=torch.float64, device=y.device)   # + totals [2][C]
+    """-> dy (gradient w.r.t. the conv output), in a buffer of its own: dz stays as it was; dgamma/dbeta accumulate; dres (+)= g."""
     dy = dy_out if dy_out is not None else torch.empty(y.shape, dtype=torch.float32, device=y.device)
-    zz = z if relu else None
-    call("hrseg_bn_bwd_reduce", ptr(dz), _ld(dz), ptr(zz), _ld(z) if relu else 0, int(relu), ptr(y), _ld(y), ptr(coef),
-         npix, Cn, ptr(part), nch)
-    call("hrseg_bn_bwd_apply", ptr(part), nch, ptr(dz), _ld(dz), ptr(zz), _ld(z) if relu else 0, int(relu), ptr(y),
-         _ld(y), ptr(coef), None, ptr(dgamma), ptr(dbeta), ptr(dy), _ld(dy), ptr(dres),
-         _ld(dres) if dres is not None else 0, int(dres_accumulate), npix, Cn, int(eval_mode))
-    return dy
+    return bn_bwd_group([dict(dz=dz, z=z if relu else None, relu=relu, y=y, coef=coef, dgamma=dgamma, dbeta=dbeta, dres=dres,
+                              dres_accumulate=dres_accumulate, dy=dy)], eval_mode)[0]
 
 
 def _sync_world(sync):
@@ -332,6 +315,8 @@ def _check_sync_bn_shapes(sync, items, device):
 def bn_fwd_group(items, training, sync=None, phases=7):
     """items: list of dict(y, gamma, beta, rm, rv, nbt, momentum, eps, residual, relu[, out]);
     -> [(z, coef)] with three launches for the whole list (statistics, finalize, apply).
+    phases (bit 0 statistics, bit 1 finalize / eval coefficients, bit 2 apply): z is allocated only for the apply phase, and
+    the eval coefficients alone (training False, phases 2) need no y.
     sync (a process group, training only): cross-rank batch statistics -- the partial sums of all problems live in one
     buffer that is all-reduced between the statistics and the finalize phase (opt-in synchronised BN)."""
     n = len(items)
@@ -346,15 +331,16 @@ def bn_fwd_group(items, training, sync=None, phases=7):
         pool = torch.empty(total, dtype=torch.float64, device=items[0]["y"].device)
     for i, (a, it) in enumerate(zip(arr, items)):
         y = it["y"]
-        Cn, npix = y.shape[3], _npix(y)
+        Cn, npix = (y.shape[3], _npix(y)) if y is not None else (it["rm"].numel(), 0)
+        dev = y.device if y is not None else it["rm"].device
         z = it.get("out")
-        if z is None:
-            z = torch.empty(y.shape, dtype=torch.float32, device=y.device)
+        if z is None and phases & 4:
+            z = torch.empty(y.shape, dtype=torch.float32, device=dev)
         coef = it.get("coef")                       # given: the apply phase alone, on coefficients an earlier call finalized
         if coef is None:
-            coef = torch.empty(4 * Cn, dtype=torch.float32, device=y.device)
+            coef = torch.empty(4 * Cn, dtype=torch.float32, device=dev)
         res = it.get("residual")
-        a.y, a.ldy, a.npix, a.C = ptr(y), _ld(y), npix, Cn
+        a.y, a.ldy, a.npix, a.C = ptr(y), (_ld(y) if y is not None else 0), npix, Cn
         a.gamma, a.beta = ptr(it["gamma"]), ptr(it["beta"])
         a.running_mean, a.running_var = ptr(it["rm"]), ptr(it["rv"])
         a.num_batches_tracked = ptr(it["nbt"]) if training else None
@@ -362,7 +348,7 @@ def bn_fwd_group(items, training, sync=None, phases=7):
         a.stat_updates = int(it.get("repeat", 1))
         a.stat_div = int(it.get("stat_div", 1))
         a.residual, a.ldr, a.relu = ptr(res), (_ld(res) if res is not None else 0), int(it["relu"])
-        a.z, a.ldz, a.coef = ptr(z), _ld(z), ptr(coef)
+        a.z, a.ldz, a.coef = ptr(z), (_ld(z) if z is not None else 0), ptr(coef)
         a.relu_mask = ptr(it.get("relu_mask"))
         a.z_split = int(bool(it.get("z_split", False)))
         a.residual_split = int(bool(it.get("residual_split", False)))
@@ -396,8 +382,8 @@ def bn_fwd_group(items, training, sync=None, phases=7):
 
 
 def bn_bwd_group(items, eval_mode, sync=None):
-    """items: list of dict(dz, z, relu, y, coef, dgamma, dbeta, dres, dres_accumulate); dy is written
-    in place over dz.  Three launches for the whole list.  sync: see bn_fwd_group (the backward's batch means become
+    """items: list of dict(dz, z, relu, y, coef, dgamma, dbeta, dres, dres_accumulate[, dy]); dy is written
+    in place over dz unless the item brings a buffer `dy` for it.  Three launches for the whole list.  sync: see bn_fwd_group (the backward's batch means become
     global; dgamma / dbeta receive this rank's share, so the gradient all-reduce sums them to the global value)."""
     n = len(items)
     arr = (_lib.BnBwd * n)()
@@ -434,7 +420,8 @@ def bn_bwd_group(items, eval_mode, sync=None):
         a.z, a.ldz, a.relu = (ptr(z) if use_z else None), (_ld(z) if use_z else 0), int(it["relu"])
         a.y, a.ldy, a.coef = ptr(y), _ld(y), ptr(it["coef"])
         a.dgamma, a.dbeta = ptr(it["dgamma"]), ptr(it["dbeta"])
-        a.dy, a.lddy = ptr(dz), _ld(dz)
+        dy = it.get("dy", dz)
+        a.dy, a.lddy = ptr(dy), _ld(dy)
         a.dres, a.lddres = ptr(dres), (_ld(dres) if dres is not None else 0)
         a.dres_accumulate = int(bool(it.get("dres_accumulate", False)))
         a.npix, a.C, a.partial, a.nchunks = npix, Cn, ptr(part), nch
@@ -447,7 +434,7 @@ def bn_bwd_group(items, eval_mode, sync=None):
         call("hrseg_bn_bwd_group_phases", n, arr, 0, 6)
     else:
         call("hrseg_bn_bwd_group", n, arr, int(eval_mode))
-    return [it["dz"] for it in items]
+    return [it.get("dy", it["dz"]) for it in items]
 
 
 # ------------------------------------------------------------------ pooling / resize / glue

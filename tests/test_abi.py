@@ -44,7 +44,7 @@ def test_header_symbols_exported_and_prototypes_match():
         assert got == want, f"{name}: ctypes {got} != header {want}"
     for name in list(_lib.PROTOTYPES) + list(_lib.RAW_PROTOTYPES):
         assert name in decls, f"{name} bound in _lib.py but missing from hrseg.h"
-    assert _lib.abi_version() == _lib.ABI_VERSION == 15
+    assert _lib.abi_version() == _lib.ABI_VERSION == 16
     assert not any(n.startswith("hrseg_debug_") for n in decls), "experimental switches do not belong in the public header"
 
 
@@ -71,6 +71,17 @@ def test_invalid_arguments_are_reported_without_a_gpu():
         assert head_bwd(**bad) == -1 and b"hrseg_head_bwd: bad row strides" in lib.hrseg_last_error_string(), bad
     assert lib.hrseg_head_bwd(P, 64, None, P, P, 5, P, 64, 0, P, P, None, 2, 143, 62, 5, None) == -1
     assert b"hrseg_head_bwd: bad arguments" in lib.hrseg_last_error_string()
+    # hrseg_bn_fwd_group_phases asks of a problem what the phases that run touch, and refuses before anything is launched
+    lib.hrseg_bn_fwd_group_phases.argtypes = _lib.PROTOTYPES["hrseg_bn_fwd_group_phases"]
+
+    def bn_fwd(training, phases, **missing):
+        prob = dict(y=4096, ldy=64, npix=35, C=64, running_mean=4096, running_var=4096, z=4096, ldz=64, coef=4096, partial=4096,
+                    nchunks=2)
+        prob.update(missing)
+        return lib.hrseg_bn_fwd_group_phases(1, (_lib.BnFwd * 1)(_lib.BnFwd(**prob)), training, phases, None)
+    assert bn_fwd(0, 4, z=None) == -1 and b"hrseg_bn_fwd_group: bad tensor arguments" in lib.hrseg_last_error_string()
+    assert bn_fwd(1, 1, partial=None) == -1 and b"hrseg_bn_fwd_group: training needs partial" in lib.hrseg_last_error_string()
+    assert bn_fwd(1, 0) == -1 and b"hrseg_bn_fwd_group_phases: phases is a mask" in lib.hrseg_last_error_string()
     lib.hrseg_tune.argtypes = [ctypes.c_char_p, ctypes.c_int]
     assert lib.hrseg_tune(b"igemm_wtm", 0) == 0
     assert lib.hrseg_tune(b"no_such_knob", 1) == -1 and b"unknown key" in lib.hrseg_last_error_string()

@@ -1,4 +1,4 @@
-"""The weight-average kernels of csrc/grad_clip.hip -- hrseg_adamw_dev_ema, hrseg_adamw_dev_clip_ema, hrseg_ema_update,
+"""The weight-average kernels of csrc/optim.hip -- hrseg_adamw_dev_ema, hrseg_adamw_dev_clip_ema, hrseg_ema_update,
 hrseg_swap -- against the entry points they extend (bitwise) and tests/ema_ref.py (the derived bar), at the sizes of
 ema_ref.SIZES: the scalar tail alone, one 16-byte group, groups plus tail, and the size at which the cap on blocks sends threads
 round the grid-stride loop a second time.  "Bitwise" means torch.equal.  The fp64 reference is evaluated on the device that

@@ -1,4 +1,4 @@
-"""csrc/grad_clip.hip -- the fp64 sum of squares, the finalize + step-count launch and AdamW with a verdict -- against
+"""The clipping kernels of csrc/optim.hip -- the fp64 sum of squares, the finalize + step-count launch and AdamW with a verdict -- against
 tests/gradclip_ref.py at the smallest sizes where they can go wrong.  With CH = the library's chunk length and MB = the most
 blocks a launch uses (both read from the library): n = 1, 3 run the scalar tail alone, 4 exactly one 16-byte piece, 5 and
 1023 pieces plus tail; CH-1 / CH / CH+1 sit around the unguarded full-chunk path; 2*CH+5 is two full chunks and a one-element

@@ -1,7 +1,7 @@
 """The level heads fused into the BatchNorm + ReLU of the layer in front of them (hrseg_head_bn_fwd, hrseg_head_bn_bwd_reduce,
 hrseg_head_bn_bwd_apply; engine.DeferredAct; HRSEG_HEAD_BN_FUSE).
 
-Kernel level: the fused forward against hrseg_bn_apply + hrseg_head_fwd (same bits expected), the two fused backward passes with
+Kernel level: the fused forward against the BatchNorm apply phase (ops.bn_apply) + hrseg_head_fwd (same bits expected), the two fused backward passes with
 the unchanged finalize against hrseg_head_bwd into a zeroed buffer + the grouped BatchNorm backward.  dy, dgamma, dbeta and
 max|dy| are compared directly: the fused passes evaluate the expressions of the kernels they replace on the same chunks in the
 same per-thread order, so EQUALITY is asserted.  dW, dbias and dgb are atomic sums on both sides: each must be no further from an

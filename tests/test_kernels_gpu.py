@@ -157,6 +157,47 @@ def test_batchnorm_eval_coef(ops):
     assert rel(nchw(z), F.batch_norm(y, rm, rv, gamma, beta, False, 0.1, 1e-5)) < 1e-5
 
 
+def test_batchnorm_eval_coef_widest(ops):
+    """C = 1024 is the widest channel count the quad mapping admits: Q = 256 channel quads, one pixel lane per block"""
+    C = 1024
+    g = torch.Generator().manual_seed(1)
+    y = torch.randn(2, C, 3, 3, generator=g)
+    gamma, beta = torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g)
+    rm, rv = torch.randn(C, generator=g), torch.rand(C, generator=g) + 0.5
+    coef = ops.bn_eval_coef(gamma.cuda(), beta.cuda(), rm.cuda(), rv.cuda(), 1e-5)
+    z = ops.bn_apply(nhwc(y), coef, None, False)
+    assert rel(nchw(z), F.batch_norm(y, rm, rv, gamma, beta, False, 0.1, 1e-5)) < 1e-5
+
+
+@pytest.mark.parametrize("relu", [False, True])
+def test_bn_bwd_keeps_dz_and_honours_dy_out(ops, relu):
+    """ops.bn_bwd is one bn_bwd_group item with a dy buffer of its own: dz stays bit for bit, dy lands in dy_out (or a fresh
+    tensor) and carries the bits of the in-place grouped call.  C = 48: Q = 12, P = 21, so 4 threads of a block idle."""
+    C, B, H, W = 48, 2, 5, 7
+    g = torch.Generator().manual_seed(5)
+    yd = nhwc(torch.randn(B, C, H, W, generator=g) * 2 + 0.5)
+    gamma, beta = (torch.rand(C, generator=g) + 0.5).cuda(), (torch.randn(C, generator=g) * 0.1).cuda()
+    coef = ops.bn_train_coef(yd, gamma, beta, torch.zeros(C, device="cuda"), torch.ones(C, device="cuda"), None, 0.1, 1e-5)
+    z = ops.bn_apply(yd, coef, nhwc(torch.randn(B, C, H, W, generator=g)), relu)
+    dz = nhwc(torch.randn(B, C, H, W, generator=g))
+    dz0 = dz.clone()
+
+    def grads():
+        return torch.zeros(C, device="cuda"), torch.zeros(C, device="cuda")
+    (dg1, db1), (dg2, db2), (dg3, db3) = grads(), grads(), grads()
+    dy_fresh = ops.bn_bwd(dz, z, relu, yd, coef, dg1, db1)
+    assert torch.equal(dz, dz0) and dy_fresh.data_ptr() != dz.data_ptr()
+    buf = torch.full_like(dz, float("nan"))
+    dy_out = ops.bn_bwd(dz, z, relu, yd, coef, dg2, db2, dy_out=buf)
+    assert dy_out is buf and torch.equal(dz, dz0)
+    inplace = dz.clone()
+    dy_group = ops.bn_bwd_group([dict(dz=inplace, z=z if relu else None, relu=relu, y=yd, coef=coef, dgamma=dg3, dbeta=db3,
+                                      dres=None)], False)[0]
+    assert dy_group is inplace
+    assert torch.equal(dy_fresh, dy_group) and torch.equal(dy_out, dy_group)
+    assert torch.equal(dg1, dg3) and torch.equal(db1, db3) and torch.equal(dg2, dg3) and torch.equal(db2, db3)
+
+
 def test_batchnorm_group_fwd_bwd(ops):
     """grouped BN (statistics, finalize, apply; reduce, totals, apply): four problems of different size per
     launch, run twice, with and without residual; without residual the backward gets no z and recomputes

@@ -169,7 +169,7 @@ def _check_writer(problems, training, what, flags=None):
     return plain
 
 
-# one C per thread layout of csrc/bn_elem.hip make_lanes (Q = C / 4 channel quads, P = 256 / Q pixel lanes, threads beyond
+# one C per thread layout of csrc/elem_common.h make_lanes (Q = C / 4 channel quads, P = 256 / Q pixel lanes, threads beyond
 # P * Q idle): 16 / 64: Q divides 256, every thread works; 48 (P = 21), 96 (P = 10), 192 (P = 5), 384 (P = 2): 4, 16, 16
 # and 64 idle threads; 1024: Q = 256, P = 1 (one pixel per block pass)
 BN_CHANNELS = [16, 48, 64, 96, 192, 384, 1024]
