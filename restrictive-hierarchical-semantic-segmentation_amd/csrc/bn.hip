@@ -1,6 +1,7 @@
 // Batch-norm (training statistics, apply, backward; grouped: n problems per launch) and the level heads fused into
 // its backward, on NHWC fp32 for gfx950.  All HBM-bound: one pass per tensor, 16-byte accesses, per-channel parameters
 // held in registers.  Thread mapping: elem_common.h.
+#include <type_traits>
 #include "elem_common.h"
 #include "sp_arith.h"      // the pre-split activation granule: hrseg_split_f16x2 / hrseg_join_f16x2
 
@@ -521,6 +522,230 @@ __global__ __launch_bounds__(256) void head_bn_bwd_reduce_kernel(hrseg_head_bn_t
   }
 }
 
+// The first pass for wide rows (more than 128 channel quads: P = 1, every working thread walks EVERY pixel of its chunk).  The
+// kernel above keeps 8 x 16 bytes per thread in flight and stops loading while it adds: one wave per SIMD, 23 KB per block, and
+// the launch has one block per chunk on half the chip.  Here the block has a second set of 256 threads that only move data: they
+// stream the chunk's rows (and the rows' logit gradients) through registers into a two-slot ring in LDS, two stages of
+// HEAD_RING_ROWS rows in flight beside the one being written, while the first 256 threads -- thread cq the sums of channel quad
+// cq, as above -- take their 16 bytes per pixel from the ring.  The additions are the ones of the kernel above, per thread in the
+// same order, with the sample-boundary flush at the same pixel: the partial sums and what goes into the atomics are the same bits.
+// A block depends on nothing but its own loads; the stage barrier orders LDS traffic only (no vmcnt(0): conv_ws.hip).  Stages
+// come in pairs (the loaders alternate two register sets, and a loop with one exit is what lets the compiler count their loads
+// exactly): an odd count is rounded up, the extra stage holds no pixel.
+#define HEAD_RING_ROWS 16
+static size_t head_ring_lds_bytes(int F) { return (size_t)2 * HEAD_RING_ROWS * (F + 8) * sizeof(float); }
+template <int CO>
+__global__ __launch_bounds__(512) void head_bn_bwd_reduce_ring_kernel(hrseg_head_bn_t a, int chunk0) {
+  extern __shared__ __attribute__((aligned(16))) float ring[];      // y rows [2][R][F], then logit gradients [2][R][8]
+  constexpr int R = HEAD_RING_ROWS;
+  const int C = a.F, Q = C >> 2;
+  float* const ybuf = ring;
+  float* const gbuf = ring + (size_t)2 * R * C;
+  const bool loader = __builtin_amdgcn_readfirstlane((int)threadIdx.x) >= 256;      // wave-uniform: a scalar branch
+  const int cq = threadIdx.x & 255;
+  const bool active = cq < Q;
+  const int chunk = chunk0 + blockIdx.x;
+  const int cps = a.nchunks / a.nseg, seg = chunk / cps;
+  const long hw = a.hw, seg_pix = (long)a.B * hw;
+  const long per = (seg_pix + cps - 1) / cps;
+  const long seg_base = seg * seg_pix;
+  const long lo = seg_base + (long)(chunk - seg * cps) * per;
+  const long seg_end = seg_base + seg_pix;
+  const long hi = (lo + per < seg_end) ? lo + per : seg_end;
+  const int nst = lo < hi ? (int)(((hi - lo + R - 1) / R + 1) & ~1L) : 0;
+  if (blockIdx.x == 0 && threadIdx.x < 64 && a.dy_absmax) a.dy_absmax[threadIdx.x] = 0.f;
+  const float* __restrict__ gb = a.gb[seg];
+  const float* __restrict__ w = a.w[seg];
+  const float* __restrict__ dzl = a.dzl[seg];
+  const int lddz = a.lddzl[seg], Cout = a.Cout[seg];
+  float* dgb = a.dgb[seg];
+  auto stage_barrier = [&]() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+  };
+  if (loader) {
+    // No branch around a load and none around a store: rows past the chunk's end re-read its last row, threads past the last
+    // channel quad the last quad, every thread brings the logit gradients of row cq % R (equal bytes stored twice) -- so the
+    // compiler counts the loads in flight exactly and waits for one stage's registers with the next stage's still outstanding.
+    if (nst > 0) {
+      const int lcq = active ? cq : Q - 1, gr = cq & (R - 1);
+      f32x4 va[R], vb[R];
+      float ga[CO], gv[CO];
+      auto issue = [&](f32x4 (&v)[R], float (&g)[CO], int st) {
+        const long p0 = lo + (long)st * R;
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          const long pix = (p0 + r < hi) ? p0 + r : hi - 1;
+          v[r] = ld4(a.y + pix * a.ldy + 4 * lcq);
+        }
+        const long gp = (p0 + gr < hi) ? p0 + gr : hi - 1;
+#pragma unroll
+        for (int c = 0; c < CO; ++c) g[c] = dzl[(gp - seg_base) * lddz + (c < Cout ? c : Cout - 1)];
+        asm volatile("" ::: "memory");
+      };
+      auto write = [&](const f32x4 (&v)[R], const float (&g)[CO], int st) {
+        float* ys = ybuf + (size_t)(st & 1) * R * C + 4 * lcq;
+#pragma unroll
+        for (int r = 0; r < R; ++r) st4(ys + r * C, v[r]);
+        float* gs = gbuf + ((st & 1) * R + gr) * 8;
+#pragma unroll
+        for (int c = 0; c < CO; ++c) gs[c] = (c < Cout) ? g[c] : 0.f;
+      };
+      issue(va, ga, 0);
+      issue(vb, gv, 1);
+      write(va, ga, 0);
+      issue(va, ga, 2);
+      stage_barrier();
+      // trip t: the consumers read stage t; stage t + 1 goes into the other slot (read last in trip t - 1), its registers
+      // take stage t + 3
+      for (int t = 0; t < nst; t += 2) {
+        write(vb, gv, t + 1);
+        issue(vb, gv, t + 3);
+        stage_barrier();
+        write(va, ga, t + 2);
+        issue(va, ga, t + 4);
+        stage_barrier();
+      }
+    }
+    return;
+  }
+  f32x4 s = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
+  f32x4 a_dw[CO], a_dg = {0.f, 0.f, 0.f, 0.f}, a_db = {0.f, 0.f, 0.f, 0.f};
+  float a_bias[CO];
+#pragma unroll
+  for (int c = 0; c < CO; ++c) {
+    a_dw[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    a_bias[c] = 0.f;
+  }
+  // dbias (the plain sum of the logit gradients over the chunk, the same chain of additions in any thread): the adding waves
+  // are bound by their vector instructions, so where the fourth wave holds no channel quad (at most 192 of them) its first
+  // thread keeps this sum and the other three waves skip its two instructions per pixel; otherwise thread 0 as above
+  const int bias_tid = Q <= 192 ? 192 : 0;
+  const bool bias_wave = (__builtin_amdgcn_readfirstlane((int)threadIdx.x) >> 6) == (bias_tid >> 6);
+  float* dbias = a.dbias[seg];
+  if (nst > 0) {
+    const int ccq = active ? cq : 0;
+    const f32x4 mean = ld4(a.coef + 4 * ccq), rstd = ld4(a.coef + C + 4 * ccq);
+    const f32x4 sc = ld4(a.coef + 2 * C + 4 * ccq), sh = ld4(a.coef + 3 * C + 4 * ccq);
+    f32x4 wq[CO];
+#pragma unroll
+    for (int c = 0; c < CO; ++c) wq[c] = (c < Cout) ? ld4(w + c * C + 4 * ccq) : f32x4{0.f, 0.f, 0.f, 0.f};
+    long b = (lo - seg_base) / hw;                  // sample of the current pixel, bnd = first pixel of the next one
+    long bnd = seg_base + (b + 1) * hw;
+    f32x4 gam = {1.f, 1.f, 1.f, 1.f}, bet = {0.f, 0.f, 0.f, 0.f};
+    if (gb) {
+      gam = ld4(gb + (size_t)b * 2 * C + 4 * ccq);
+      bet = ld4(gb + (size_t)b * 2 * C + C + 4 * ccq);
+    }
+    auto flush_dgb = [&]() {
+      if (dgb && active) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          atomicAdd(dgb + (size_t)b * 2 * C + 4 * cq + j, a_dg[j]);
+          atomicAdd(dgb + (size_t)b * 2 * C + C + 4 * cq + j, a_db[j]);
+        }
+      }
+    };
+    // one pixel: the expressions of head_bn_bwd_reduce_kernel, y and the logit gradients from the ring
+    auto one = [&](auto with_bias, const float* ys, const float* gs) {
+      const f32x4 yv = ld4(ys);
+      float g[CO];
+      const f32x4 g0 = ld4(gs);
+#pragma unroll
+      for (int c = 0; c < (CO < 4 ? CO : 4); ++c) g[c] = g0[c];
+      if (CO > 4) {
+        const f32x4 g1 = ld4(gs + 4);
+#pragma unroll
+        for (int c = 4; c < CO; ++c) g[c] = g1[c - 4];
+      }
+      const f32x4 zc = bn_affine(yv, sc, sh);
+      f32x4 fv;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) fv[j] = fmaxf(zc[j], 0.f);
+      const f32x4 fm = fv * gam + bet;
+      f32x4 uu = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int c = 0; c < CO; ++c) {
+        uu += wq[c] * g[c];
+        a_dw[c] += fm * g[c];
+        if (decltype(with_bias)::value) a_bias[c] += g[c];
+      }
+      a_dg += fv * uu;
+      a_db += uu;
+      f32x4 gv = gam * uu;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) gv[j] = zc[j] > 0.f ? gv[j] : 0.f;
+      const f32x4 xh = (yv - mean) * rstd;
+      s += gv;
+      s2 += gv * xh;
+    };
+    auto stages = [&](auto with_bias) {
+    stage_barrier();                                // stage 0 is in its slot
+    for (int t = 0; t < nst; ++t) {
+      const float* ys = ybuf + (size_t)(t & 1) * R * C + 4 * ccq;
+      const float* gs = gbuf + (t & 1) * R * 8;
+      const long p0 = lo + (long)t * R;
+      if (p0 + R <= hi && p0 + R <= bnd) {          // a whole stage inside one sample
+        constexpr int UR = CO <= 4 ? R : 4;         // (registers: the eight-output instance holds twice the accumulators)
+#pragma unroll 1
+        for (int r0 = 0; r0 < R; r0 += UR)
+#pragma unroll
+          for (int r = r0; r < r0 + UR; ++r) one(with_bias, ys + r * C, gs + r * 8);
+      } else {
+        for (int r = 0; r < R && p0 + r < hi; ++r) {
+          while (p0 + r >= bnd) {                   // the sequence entered the next sample: its FiLM pair, its dgb rows
+            flush_dgb();
+            a_dg = f32x4{0.f, 0.f, 0.f, 0.f};
+            a_db = f32x4{0.f, 0.f, 0.f, 0.f};
+            ++b;
+            bnd += hw;
+            if (gb) {
+              gam = ld4(gb + (size_t)b * 2 * C + 4 * ccq);
+              bet = ld4(gb + (size_t)b * 2 * C + C + 4 * ccq);
+            }
+          }
+          one(with_bias, ys + r * C, gs + r * 8);
+        }
+      }
+      stage_barrier();
+    }
+    };
+    if (bias_wave) stages(std::true_type());
+    else stages(std::false_type());
+    flush_dgb();
+  }
+  if (dbias && (int)threadIdx.x == bias_tid) {
+#pragma unroll
+    for (int c = 0; c < CO; ++c)
+      if (c < Cout) {
+        float t = 0.f;
+        t += a_bias[c];
+        atomicAdd(dbias + c, t);
+      }
+  }
+  if (!active) return;
+  // one pixel lane: the fp64 sum over lanes of the kernel above is 0.0 + the lane's value, the dW / dbias lane sums 0.f + it
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    double sa = 0.0, sb = 0.0;
+    sa += (double)s[j];
+    sb += (double)s2[j];
+    a.partial[((size_t)chunk * 2 + 0) * C + 4 * cq + j] = sa;
+    a.partial[((size_t)chunk * 2 + 1) * C + 4 * cq + j] = sb;
+  }
+  float* dw = a.dw[seg];
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int c = 0; c < CO; ++c)
+      if (c < Cout) {
+        float t = 0.f;
+        t += a_dw[c][j];
+        atomicAdd(dw + c * C + 4 * cq + j, t);
+      }
+}
+
 // Second pass: bn_bwd_apply_group_kernel with g recomputed from y and the logit gradient instead of read from memory.
 template <int CO>
 __global__ __launch_bounds__(256) void head_bn_bwd_apply_kernel(hrseg_head_bn_t a) {
@@ -716,7 +941,22 @@ extern "C" int hrseg_head_bn_bwd_reduce(const hrseg_head_bn_t* p, int seg0, int 
     comax = p->Cout[s] > comax ? p->Cout[s] : comax;
   }
   const int cps = p->nchunks / p->nseg;
-  if (comax <= 4) hipLaunchKernelGGL(head_bn_bwd_reduce_kernel<4>, dim3(nsegs * cps), dim3(256), 0, (hipStream_t)stream, *p, seg0 * cps);
+  if (p->F / 4 > 128) {       // one pixel lane per block (P = 1): the ring kernel
+    const size_t lds = head_ring_lds_bytes(p->F);
+    static bool raised = false;         // dynamic LDS beyond 64 KB is asked for once per kernel
+    if (!raised) {
+      const int most = (int)head_ring_lds_bytes(1024);
+      const hipError_t e4 = hipFuncSetAttribute(reinterpret_cast<const void*>(&head_bn_bwd_reduce_ring_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, most);
+      const hipError_t e8 = hipFuncSetAttribute(reinterpret_cast<const void*>(&head_bn_bwd_reduce_ring_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, most);
+      if (e4 != hipSuccess || e8 != hipSuccess) {
+        hrseg_set_error("hrseg_head_bn_bwd_reduce: %d bytes of LDS refused: %s", most, hipGetErrorString(e4 != hipSuccess ? e4 : e8));
+        return HRSEG_ERR_LAUNCH;
+      }
+      raised = true;
+    }
+    if (comax <= 4) hipLaunchKernelGGL(head_bn_bwd_reduce_ring_kernel<4>, dim3(nsegs * cps), dim3(512), lds, (hipStream_t)stream, *p, seg0 * cps);
+    else hipLaunchKernelGGL(head_bn_bwd_reduce_ring_kernel<8>, dim3(nsegs * cps), dim3(512), lds, (hipStream_t)stream, *p, seg0 * cps);
+  } else if (comax <= 4) hipLaunchKernelGGL(head_bn_bwd_reduce_kernel<4>, dim3(nsegs * cps), dim3(256), 0, (hipStream_t)stream, *p, seg0 * cps);
   else hipLaunchKernelGGL(head_bn_bwd_reduce_kernel<8>, dim3(nsegs * cps), dim3(256), 0, (hipStream_t)stream, *p, seg0 * cps);
   HRSEG_LAUNCH_CHECK("head_bn_bwd_reduce");
   return 0;
