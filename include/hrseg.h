@@ -321,9 +321,9 @@ int hrseg_nchw_to_nhwc(const float* in, float* out, int ldout, int B, int C, int
 int hrseg_nhwc_to_nchw(const float* in, int ldin, float* out, int B, int C, int H, int W,
                        hrseg_stream_t stream);
 
-/* ------------------------------------------------------------------ FiLM + heads + composition
- * FiLM (models.py:58-77), outconv / classifier 1x1 heads (:180,:626-645),
- * sigmoid / grouped-softmax probability composition (:266-304,:763-798).     */
+/* ------------------------------------------------------------------ FiLM + heads (csrc/head.hip)
+ * FiLM (models.py:58-77), outconv / classifier 1x1 heads (:180,:626-645) and the
+ * resize of their logits; the fused head backward hrseg_head_bn_bwd_* is in csrc/bn.hip. */
 /* cond[b,c] = mean_{h,w} P[b,c,h,w]  (NCHW in); scratch: BC*64 doubles */
 int hrseg_gap_nchw(const float* p, float* cond, double* scratch, int BC, long hw,
                    hrseg_stream_t stream);
@@ -383,6 +383,11 @@ int hrseg_logits_up_fwd(const float* in, int ldin, int B, int Hi, int Wi, int C,
                         int Wo, int align_corners, hrseg_stream_t stream);
 int hrseg_logits_up_bwd(const float* dout, int B, int Hi, int Wi, int C, float* din, int lddin,
                         int Ho, int Wo, int align_corners, hrseg_stream_t stream);
+
+/* ------------------------------------------------------------------ composition over the class tree (csrc/compose.hip)
+ * sigmoid / grouped-softmax probability composition (models.py:266-304,:763-798),
+ * consistency (Metrics/losses.py:150-177) and the opt-in grouped KL (:180-210):
+ * the entry points that take the tree's group table.                         */
 /* P0 = sigmoid(z0) ; NCHW */
 int hrseg_sigmoid_fwd(const float* z, float* p, long n, hrseg_stream_t stream);
 /* level L>0: groups given as parent channel index + child count per group
@@ -399,20 +404,6 @@ int hrseg_compose_bwd(const float* dp, long sb, long sc, long si, const float* z
                       const int* group_parent, const int* group_size, hrseg_stream_t stream);
 int hrseg_sigmoid_bwd(const float* dp, long sb, long sc, long si, const float* z, float* dz,
                       int accumulate, int B, int C, long hw, hrseg_stream_t stream);
-
-/* ------------------------------------------------------------------ loss + metrics
- * CrossEntropyLoss / SoftDiceLoss (Metrics/losses.py:16-134), consistency
- * (:150-177), prediction prep + confusion counts (train.py:206-231,
- * Metrics/performance_metrics.py:27-141).                                    */
-/* partial[b][c][5] += {n, sum t*logp, sum p*t, sum p, sum t} over t!=-1 (double) */
-int hrseg_loss_partials(const float* z, const float* t, double* partial, int B, int C, long hw,
-                        hrseg_stream_t stream);
-/* out[0]=ce, out[1]=dice, out[2]=dice_valid_count; coef[b][c][4] for the backward */
-int hrseg_loss_finalize(const double* partial, const float* w, int B, int C, float* out,
-                        float* coef, hrseg_stream_t stream);
-/* dz (=|+=) g_ce*dCE/dz + g_dice*dDice/dz ; g = device pointer to {g_ce,g_dice} */
-int hrseg_loss_bwd(const float* z, const float* t, const float* coef, const float* g, float* dz,
-                   int accumulate, int B, int C, long hw, hrseg_stream_t stream);
 /* sum |sum_{c in group} P[b,c] - Pprev[b,parent]| per group -> out[ngroups] (double, +=) */
 int hrseg_consistency(const float* p, const float* pprev, double* out, int B, int C, int Cprev,
                       long hw, int ngroups, const int* group_parent, const int* group_size,
@@ -432,6 +423,19 @@ int hrseg_group_kl(const float* z, const float* pprev, double* out, int B, int C
 int hrseg_group_kl_bwd(const float* z, const float* pprev, const float* g, float scale, float* dz, int B, int C,
                        int Cprev, long hw, int ngroups, const int* group_parent, const int* group_size,
                        hrseg_stream_t stream);
+
+/* ------------------------------------------------------------------ loss + metrics (csrc/loss.hip)
+ * CrossEntropyLoss / SoftDiceLoss (Metrics/losses.py:16-134), prediction prep +
+ * confusion counts (train.py:206-231, Metrics/performance_metrics.py:27-141). */
+/* partial[b][c][5] += {n, sum t*logp, sum p*t, sum p, sum t} over t!=-1 (double) */
+int hrseg_loss_partials(const float* z, const float* t, double* partial, int B, int C, long hw,
+                        hrseg_stream_t stream);
+/* out[0]=ce, out[1]=dice, out[2]=dice_valid_count; coef[b][c][4] for the backward */
+int hrseg_loss_finalize(const double* partial, const float* w, int B, int C, float* out,
+                        float* coef, hrseg_stream_t stream);
+/* dz (=|+=) g_ce*dCE/dz + g_dice*dDice/dz ; g = device pointer to {g_ce,g_dice} */
+int hrseg_loss_bwd(const float* z, const float* t, const float* coef, const float* g, float* dz,
+                   int accumulate, int B, int C, long hw, hrseg_stream_t stream);
 /* per-class metric vectors of nlevels (1..8) levels from their confusion counts in ONE launch: cm[L] (DEVICE, int64
  * [K_L][K_L], (target, predicted) as hrseg_predict_metrics counts them), child[L] != 0: label 0 is the synthetic background
  * of a child level (its row is dropped, its class not reported).  out (DEVICE) receives [5][sum_L (K_L - child_L)] floats:
@@ -520,7 +524,7 @@ int hrseg_comm_allreduce_async(void* comm, float* buf, long count, hrseg_stream_
 int hrseg_comm_wait(hrseg_stream_t comm_stream, hrseg_stream_t consumer);   /* consumer waits for comm_stream */
 int hrseg_comm_destroy(void* comm);
 
-/* ------------------------------------------------------------------ target encoding (input side of the path)
+/* ------------------------------------------------------------------ target encoding (input side of the path; csrc/targets.hip)
  * SegDataset.separate_masks / traverse_tree / process_ignore_values (Data/dataset.py:41-124,
  * 227-265): label image [B,hw] of uint8 pixel values -> out [B,C,hw] fp32 (NCHW planes).
  * on_lut: DEVICE table [256] of uint64, bit c set when channel c's node contains the leaf class
@@ -711,7 +715,7 @@ int hrseg_score_labels(const unsigned char* pred, const long* pdesc, const unsig
                        const unsigned long long* path_lut, int nlevels, const int* C, long long* counts,
                        long long* ignored, int B, int per_image, hrseg_stream_t stream);
 
-/* ------------------------------------------------------------------ level synthesis for flat models (evaluation side)
+/* ------------------------------------------------------------------ level synthesis for flat models (evaluation side; csrc/targets.hip)
  * predictEval.py:85-129 get_parent_masks (parent = union of its descendant leaves, "any > 0") and :134-185
  * combine_levels (per-level tensors stitched from leaf and parent channels).  out[b][o] is the COPY of the single
  * input channel selected by masks[o] (is_union[o] == 0) or 1.0 where any selected input channel is > 0, else 0.0.

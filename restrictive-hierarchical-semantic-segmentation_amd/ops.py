@@ -1091,11 +1091,15 @@ def sigmoid_bwd(dp, z, dz=None, accumulate=False):
     return dz
 
 
+def _group_args(group_parent, group_size):
+    """the (ngroups, group_parent, group_size) argument triple of the entry points that take a level's group table"""
+    return len(group_parent), _lib.int_array(group_parent), _lib.int_array(group_size)
+
+
 def compose_fwd(z, pprev, group_parent, group_size):
     B, Cn, H, W = z.shape
     p = torch.empty_like(z)
-    call("hrseg_compose_fwd", ptr(z), ptr(pprev), ptr(p), B, Cn, pprev.shape[1], H * W, len(group_parent),
-         _lib.int_array(group_parent), _lib.int_array(group_size))
+    call("hrseg_compose_fwd", ptr(z), ptr(pprev), ptr(p), B, Cn, pprev.shape[1], H * W, *_group_args(group_parent, group_size))
     return p
 
 
@@ -1108,8 +1112,7 @@ def compose_bwd(dp, z, pprev, group_parent, group_size, dz=None, dz_accumulate=F
         dpprev, dpprev_accumulate = torch.empty_like(pprev), False
     sb, sc, si = _strides3(dp, B, Cn, H * W)
     call("hrseg_compose_bwd", ptr(dp), sb, sc, si, ptr(z), ptr(pprev), ptr(dz), int(dz_accumulate), ptr(dpprev),
-         int(dpprev_accumulate), B, Cn, pprev.shape[1], H * W, len(group_parent), _lib.int_array(group_parent),
-         _lib.int_array(group_size))
+         int(dpprev_accumulate), B, Cn, pprev.shape[1], H * W, *_group_args(group_parent, group_size))
     return dz, dpprev
 
 
@@ -1145,8 +1148,7 @@ def consistency_sums(p, pprev, group_parent, group_size):
     p, pprev = _c(p), _c(pprev)
     B, Cn, H, W = p.shape
     out = zeros((len(group_parent),), torch.float64, p.device)
-    call("hrseg_consistency", ptr(p), ptr(pprev), ptr(out), B, Cn, pprev.shape[1], H * W, len(group_parent),
-         _lib.int_array(group_parent), _lib.int_array(group_size))
+    call("hrseg_consistency", ptr(p), ptr(pprev), ptr(out), B, Cn, pprev.shape[1], H * W, *_group_args(group_parent, group_size))
     return out
 
 
@@ -1156,7 +1158,7 @@ def consistency_bwd(p, pprev, g, scale, group_parent, group_size):
     B, Cn, H, W = p.shape
     dp, dpprev = torch.empty_like(p), torch.empty_like(pprev)
     call("hrseg_consistency_bwd", ptr(p), ptr(pprev), ptr(g), float(scale), ptr(dp), ptr(dpprev), B, Cn, pprev.shape[1],
-         H * W, len(group_parent), _lib.int_array(group_parent), _lib.int_array(group_size))
+         H * W, *_group_args(group_parent, group_size))
     return dp, dpprev
 
 
@@ -1165,8 +1167,7 @@ def group_kl_sums(z, pprev, group_parent, group_size):
     z, pprev = _c(z), _c(pprev)
     B, Cn, H, W = z.shape
     out = zeros((len(group_parent),), torch.float64, z.device)
-    call("hrseg_group_kl", ptr(z), ptr(pprev), ptr(out), B, Cn, pprev.shape[1], H * W, len(group_parent),
-         _lib.int_array(group_parent), _lib.int_array(group_size))
+    call("hrseg_group_kl", ptr(z), ptr(pprev), ptr(out), B, Cn, pprev.shape[1], H * W, *_group_args(group_parent, group_size))
     return out
 
 
@@ -1175,7 +1176,7 @@ def group_kl_bwd(z, pprev, g, scale, group_parent, group_size):
     B, Cn, H, W = z.shape
     dz = torch.empty_like(z)
     call("hrseg_group_kl_bwd", ptr(z), ptr(pprev), ptr(g), float(scale), ptr(dz), B, Cn, pprev.shape[1], H * W,
-         len(group_parent), _lib.int_array(group_parent), _lib.int_array(group_size))
+         *_group_args(group_parent, group_size))
     return dz
 
 

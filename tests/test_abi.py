@@ -87,6 +87,38 @@ def test_invalid_arguments_are_reported_without_a_gpu():
     assert lib.hrseg_tune(b"no_such_knob", 1) == -1 and b"unknown key" in lib.hrseg_last_error_string()
 
 
+GROUP_TABLE_ENTRY_POINTS = ["hrseg_compose_fwd", "hrseg_compose_bwd", "hrseg_consistency", "hrseg_consistency_bwd", "hrseg_group_kl",
+                            "hrseg_group_kl_bwd"]
+
+
+def test_group_table_refusals_name_their_entry_point():
+    """The six entry points that take a class-tree group table refuse bad sizes first ("bad arguments"), then a bad table, each
+    under its own name, before anything is launched (placeholder pointers, never dereferenced)"""
+    from hrseg_amd import _lib
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    lib.hrseg_last_error_string.restype = ctypes.c_char_p
+    P = ctypes.c_void_p(4096)
+    for name in GROUP_TABLE_ENTRY_POINTS:
+        proto = _lib.PROTOTYPES[name]
+        # every one ends (B, C, Cprev, hw, ngroups, group_parent, group_size, stream); in front: its own pointers and scalars
+        assert proto[-8:] == [ctypes.c_int] * 3 + [ctypes.c_long, ctypes.c_int] + [ctypes.c_void_p] * 3, name
+        fn = getattr(lib, name)
+        fn.argtypes = proto
+        own = [P if t is ctypes.c_void_p else 1 for t in proto[:-8]]
+
+        def refused(C=4, ngroups=2, parents=(0, 1), sizes=(2, 2)):
+            rc = fn(*own, 1, C, 2, 16, ngroups, _lib.int_array(parents), _lib.int_array(sizes), None)
+            return rc, lib.hrseg_last_error_string().decode()
+        for bad in (dict(ngroups=0), dict(C=17)):
+            rc, msg = refused(**bad)
+            assert rc == -1 and f"{name}: bad arguments" in msg, (name, bad, msg)
+        for bad, want in ((dict(ngroups=17), "bad group table"),
+                          (dict(parents=(2, 0)), "group 0 out of range"),
+                          (dict(sizes=(2, 1)), "group sizes sum to 3, level has 4 channels")):
+            rc, msg = refused(**bad)
+            assert rc == -1 and f"{name}: {want}" in msg, (name, bad, msg)
+
+
 KNOBS = ["igemm_wtm", "igemm_kc", "igemm_db", "igemm_ksplit", "group_wtm", "wgrad_pix", "wgrad_db", "wgrad_blocks",
          "wgrad_group_mult", "wgrad_group_min", "wgrad_group_max", "sp_wtm", "sp_wtn", "sp_ksplit", "sp_patch", "sp_persist",
          "sp_ws", "sp_ws_waste", "small_cin3", "sp_ws_bf16", "sp_ws_n48", "sp_img", "wgrad9", "ws_epi_early", "exp_nosplit_x",

@@ -1,4 +1,4 @@
-"""The kernels downstream of the backbone -- csrc/head_loss.hip and the AdamW kernels of csrc/optim.hip -- against the fp64
+"""The kernels downstream of the backbone -- csrc/head.hip, compose.hip, loss.hip and the AdamW kernels of csrc/optim.hip -- against the fp64
 references of tests/headloss_ref.py, at the shapes where they take another path: every head template and thread mapping,
 both pixel loops striding, both align_corners values and down-sampling in the logits resize, singleton / 16-child / chained
 / saturated composition, the 16-wide loss and metrics instances, several loss blocks, the consistency backward, AdamW's
