@@ -309,6 +309,34 @@ int hrseg_absmax(const float* x, int ldx, long npix, int C, float* out64, hrseg_
 int hrseg_fuse_sum(int n_same, const float* const* same, const int* ld_same, int n_low, const float* const* low,
                    const int* ld_low, const int* Hi, const int* Wi, float* out, int ldo, int B, int H, int W, int C,
                    int align_corners, int relu, hrseg_stream_t stream);
+/* The HRNet head's 1x1 convolution at branch resolution (models.py:743-747 + the first shared_head layer).  Bilinear
+ * weights do not depend on the channel and sum to one, so conv1x1(cat_j up(x_j)) + b = W_0 x_0 + sum_j up(W_j x_j) + b with
+ * W_j the column block of the weight that reads branch j: the convolutions run at each branch's own size, 1/8 of the
+ * multiply-adds, and the concatenated tensor never exists.  The four entry points below are the glue around them.
+ *
+ * hrseg_head_mix: y (B x H x W x C, holding t_0 = W_0 x_0) += sum of n_low (0..3) terms low[j] (B x Hi[j] x Wi[j] x C)
+ * bilinearly resized to H x W (hrseg_fuse_sum's expression), then + bias[C] (may be NULL), in place.  partial (may be NULL):
+ * [nchunks][2][C] doubles, the per-chunk sums of y and y^2 in the layout hrseg_bn_fwd_t.partial / nchunks of the finalize
+ * phase: no statistics pass over y is needed.  Chunk k covers pixels [k * ceil(npix / nchunks), ...); fixed order, no
+ * atomics: the same bits every run.  HOST arrays of pointers / strides / sizes. */
+int hrseg_head_mix(float* y, int ldy, const float* bias, int n_low, const float* const* low, const int* ld_low,
+                   const int* Hi, const int* Wi, int B, int H, int W, int C, int align_corners, double* partial,
+                   int nchunks, hrseg_stream_t stream);
+/* its backward: the transpose of the bilinear resize of dout (B x Hout x Wout x C) onto n (1..3) targets din[j]
+ * (B x Hi[j] x Wi[j] x C, overwritten) in one launch; each target equals hrseg_bilinear_bwd of the same dout up to the
+ * order of the additions.  No atomics: the same bits every run.  absmax (may be NULL): [n][64] floats zeroed by the
+ * caller, row j receives max|din[j]| as hrseg_absmax leaves it (the FP16X2 gradient scale of the convolutions that
+ * follow).  HOST arrays. */
+int hrseg_bilinear_bwd_multi(const float* dout, int lddout, int B, int Hout, int Wout, int C, int n,
+                             float* const* din, const int* lddin, const int* Hi, const int* Wi, int align_corners,
+                             float* absmax, hrseg_stream_t stream);
+/* column blocks of a weight [rows = Cout * taps][Cin]: n (1..8) blocks of widths[j] input channels (multiples of 4 that
+ * sum to Cin; HOST array) are copied to `blocks`, laid end to end as contiguous [rows][widths[j]] matrices (block j
+ * starts at rows * (widths[0] + ... + widths[j-1]) floats); scatter_add is the reverse with dw += (the gradient). */
+int hrseg_weight_cols_gather(const float* w, int rows, int Cin, int n, const int* widths, float* blocks,
+                             hrseg_stream_t stream);
+int hrseg_weight_cols_scatter_add(const float* blocks, int rows, int Cin, int n, const int* widths, float* dw,
+                                  hrseg_stream_t stream);
 /* out = relu?(a + b) ; strided channel copy ; masked relu backward */
 int hrseg_add(const float* a, int lda, const float* b, int ldb, float* out, int ldo, int relu,
               long npix, int C, hrseg_stream_t stream);

@@ -918,6 +918,11 @@ class HighResolutionNet(_EngineModel):
             for mod in getattr(self, f"stage{t_idx + 1}"):
                 ys = mod.run(rec, ys)
         rec.mark("shared_head")
+        # training: the 1x1 convolution runs per branch at the branch's own resolution and the concatenated tensor never exists
+        # (Recorder.head_conv_bn).  HRSEG_HEAD_BRANCH_RES=0 (A/B switch, read per call): upsample + concat + convolution, the
+        # path of inference
+        if rec.training and os.environ.get("HRSEG_HEAD_BRANCH_RES", "1") != "0":
+            return rec.head_conv_bn(ys, self.shared_head[0], self.shared_head[1], self.align_corners, defer=True)
         cat = rec.upsample_concat(ys, self.align_corners)
         # the level heads are this tensor's only readers: where the recorder allows it they take it un-normalised (defer)
         return rec.conv_bn(cat, self.shared_head[0], self.shared_head[1], relu=True, defer=True)

@@ -88,6 +88,10 @@ PROTOTYPES = {
     "hrseg_bilinear_bwd": [_p, _i, _i, _i, _i, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "hrseg_absmax": [_p, _i, _l, _i, _p, _p],
     "hrseg_fuse_sum": [_i, _p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
+    "hrseg_head_mix": [_p, _i, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _i, _p],
+    "hrseg_bilinear_bwd_multi": [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p],
+    "hrseg_weight_cols_gather": [_p, _i, _i, _i, _p, _p, _p],
+    "hrseg_weight_cols_scatter_add": [_p, _i, _i, _i, _p, _p, _p],
     "hrseg_add": [_p, _i, _p, _i, _p, _i, _i, _l, _i, _p],
     "hrseg_copy": [_p, _i, _p, _i, _i, _l, _i, _p],
     "hrseg_relu_bwd": [_p, _i, _p, _i, _p, _i, _l, _i, _p],

@@ -332,6 +332,10 @@ static int spw_wtn(const IgemmArgs& a) {
   // the body walks its slabs six at a time (register sets and LDS buffers are compile-time): short reductions would
   // multiply zeros for most of a trip -- they stay on the narrow body (hrseg_tune sp_wide = 2 lifts the rule: tests)
   const int nslabs = (a.ntaps * (a.K / 16) + 1) / 2, padded = (nslabs + 5) / 6 * 6;
+  // ... except reductions of at most two slabs on 240-channel tiles (K <= 64: the HRNet head's 48 -> 720 convolution at full
+  // resolution, which is bound by writing its output): they have an instance of their own that runs exactly two slabs
+  // (launch_spw_kernel), and the narrow body would pull their pixel operand through L2 once per 48 output channels
+  if (hrseg_g_sp_wide < 2 && wtn == 15 && nslabs <= 2) return wtn;
   if (hrseg_g_sp_wide < 2 && (padded - nslabs) * 10 > nslabs) return 0;
   return wtn;
 }
@@ -392,7 +396,7 @@ static int dispatch_igemm(const IgemmArgs& a_in, int precision, hipStream_t st) 
       const size_t bytes = (size_t)(a.N / (16 * wtn)) * ((a.ntaps * (a.K / 16) + 1) / 2) * (size_t)(2 * 16 * wtn * 64);
       if (unsigned char* img = scratch_reserve(st, bytes)) {
         hrseg_count(CNT_SP_WIDE);
-        if (launch_spw_kernel(a, wtn, 1, img, st) == 0) return 0;
+        if (launch_spw_kernel(a, wtn, 1, img, st, hrseg_g_sp_wide < 2) == 0) return 0;
       }
     }
     if (pl.ksplit > 1 && !a.accumulate) zero_f32(a.y, (size_t)a.B * a.Hy * a.Wy * a.N, st);
@@ -620,15 +624,19 @@ static int ksplit_for_rounds(int tiles, int kmin, int kmax, int slots) {
 static int wgrad_target_blocks(int tiles) { return 7 * tiles < 512 ? 512 : 7 * tiles > 4096 ? 4096 : 7 * tiles; }
 static int dispatch_wgrad_sp(int ns, WgradArgs a, hipStream_t st) {
   // wide layers whose channels divide into 240 x 144 block tiles (the 720 -> 720 head layer): wgrad_spw_body
-  if (ns == 4 && hrseg_g_wgrad_sp_wide && a.Cout % 240 == 0 && a.Cin % 144 == 0 && a.M >= 65536 && !hrseg_g_deterministic && !hrseg_g_wgrad_blocks) {
-    const int tiles = (a.Cout / 240) * (a.Cin / 144) * a.T;
-    int kmax = a.M / 2048;                       // at least 64 stages of 32 pixels per block
-    if (kmax > 64) kmax = 64;
-    const int ksplit = ksplit_for_rounds(tiles, 1, kmax, 256);
+  // ... and 240 x 48 tiles (3 waves) where the input channels divide into 48 only (the head's 48 -> 720 convolution at full
+  // resolution): dy is read exactly once.  These blocks are small (38 KB of LDS, 192 threads): two per CU, shorter pixel ranges
+  // (input widths that are multiples of 80 keep the 80 x 80 tiles of the tap-per-block body below, as measured for them)
+  const bool wide144 = a.Cin % 144 == 0, wide48 = !wide144 && a.Cin % 48 == 0 && a.Cin % 80 != 0;
+  if (ns == 4 && hrseg_g_wgrad_sp_wide && a.Cout % 240 == 0 && (wide144 || wide48) && a.M >= 65536 && !hrseg_g_deterministic && !hrseg_g_wgrad_blocks) {
+    const int tiles = (a.Cout / 240) * (a.Cin / (wide144 ? 144 : 48)) * a.T;
+    int kmax = a.M / (wide144 ? 2048 : 512);     // at least 64 (16) stages of 32 pixels per block
+    if (kmax > (wide144 ? 64 : 256)) kmax = wide144 ? 64 : 256;
+    const int ksplit = ksplit_for_rounds(tiles, 1, kmax, wide144 ? 256 : 512);
     a.pix_per_block = ceil_div(ceil_div(a.M, ksplit), 32) * 32;
     if (int e = check_wgrad_span(a)) return e;
     hrseg_count(CNT_WGRAD_SP_WIDE);
-    return launch_wgrad_spw_kernel(a, ceil_div(a.M, a.pix_per_block), tiles, st);
+    return launch_wgrad_spw_kernel(a, wide144 ? 3 : 1, ceil_div(a.M, a.pix_per_block), tiles, st);
   }
   int tn = (a.Cout % 48 == 0) ? 3 : (a.Cout % 64 == 0) ? 4 : (a.Cout % 32 == 0) ? 2 : 1;
   int tk = (a.Cin % 48 == 0) ? 3 : (a.Cin % 64 == 0) ? 4 : (a.Cin % 32 == 0) ? 2 : 1;

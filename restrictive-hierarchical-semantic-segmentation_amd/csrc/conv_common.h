@@ -178,7 +178,7 @@ int launch_igemm_group_f32(const IgemmGroup& g, int wtm, int wtn, int kc, hipStr
 int launch_wgrad_f32(const WgradArgs& a, int tn, int tk, int pix, int db, int target, hipStream_t st);   // conv_wgrad_f32.hip
 int launch_wgrad_group_f32(const WgradGroup& g, int tn, int tk, int nblocks, hipStream_t st);
 int launch_sp_kernel(int ns, const IgemmArgs& a, const SpPlan& pl, hipStream_t st);                  // conv_sp_im2col.hip
-int launch_spw_kernel(const IgemmArgs& a, int wtn, int ksplit, unsigned char* img, hipStream_t st);
+int launch_spw_kernel(const IgemmArgs& a, int wtn, int ksplit, unsigned char* img, hipStream_t st, bool two_slab_ok);
 int launch_sp_group_kernel(int ns, const IgemmGroup& g, int wtm, int wtn, bool full, hipStream_t st);
 int launch_patch_sp_kernel(int ns, const IgemmArgs& a, int wtn, int cs, int flip, int blocks, int ntotal, hipStream_t st);  // conv_sp_patch.hip
 int launch_sp_pgroup_kernel(int ns, const IgemmGroup& g, int wtm, int wtn, int cs, int flip, hipStream_t st);               // conv_sp_pgroup.hip
@@ -188,7 +188,7 @@ int launch_weight_images(const WeightImageGroup& g, int nblocks, hipStream_t st)
 int launch_weight_image_table(const WeightImageTabEntry* tab, int n, int nblocks, hipStream_t st);
 int launch_wgrad_sp_kernel(int ns, const WgradArgs& a, int tn, int tk, int gx, int tiles, hipStream_t st);     // conv_wgrad_sp.hip
 int launch_wgrad_group_sp(const WgradGroup& g, int tn, int tk, int nblocks, hipStream_t st);
-int launch_wgrad_spw_kernel(const WgradArgs& a, int gx, int tiles, hipStream_t st);
+int launch_wgrad_spw_kernel(const WgradArgs& a, int nwc, int gx, int tiles, hipStream_t st);
 int launch_wgrad9_kernels(int ns, int tnk, const Wgrad9Group& g, int nblocks, const Wgrad9Reduce& r, int rblocks, hipStream_t st);
 int check_wgrad_span(const WgradArgs& a);
 #define HRSEG_SMALL_CIN_MAX 8

@@ -43,7 +43,10 @@ __global__ __launch_bounds__(256) void sp_weight_image_im2col_kernel(const float
   }
 }
 
-template <int WTM, int WTN>
+// TWO: the reduction has at most two slabs (K <= 64 of a 1x1 convolution; host-checked): the body runs exactly slabs 0 and 1
+// instead of a trip of six, four of which would multiply zeros -- an output-bound problem (48 -> 720 channels) then spends
+// a third of the matrix time per tile.  Same staging, same order of the products: the bits of the six-slab trip.
+template <int WTM, int WTN, bool TWO = false>
 __device__ __forceinline__ void igemm_spw_body(const IgemmArgs& p, unsigned char* lds, const int bid, const int nblk,
                                                const int ks_idx, const int ks_n) {
   constexpr int NS = 4;
@@ -249,6 +252,10 @@ __device__ __forceinline__ void igemm_spw_body(const IgemmArgs& p, unsigned char
     __syncthreads();
   };
   static_assert(D == 3, "unrolled by hand: 2 * D slabs per trip");
+  if constexpr (TWO) {
+    slab(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
+    slab(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{});
+  } else
   for (int s0 = 0; s0 < nslabs; s0 += 6) {       // (slabs past the slice are zeros: every load of theirs was out of range)
     slab(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
     slab(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{});
@@ -298,6 +305,11 @@ __global__ __launch_bounds__(256) void igemm_spw_kernel(IgemmArgs p) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[SpwLds<WTN>::BYTES];
   igemm_spw_body<WTM, WTN>(p, lds, blockIdx.x, gridDim.x, blockIdx.y, gridDim.y);
 }
+template <int WTM, int WTN>
+__global__ __launch_bounds__(256) void igemm_spw2_kernel(IgemmArgs p) {      // at most two slabs, no split-K
+  __shared__ __attribute__((aligned(16))) unsigned char lds[SpwLds<WTN>::BYTES];
+  igemm_spw_body<WTM, WTN, true>(p, lds, blockIdx.x, gridDim.x, 0, 1);
+}
 
 // --------------------------------------------------------------------------- launchers
 template <int NS>
@@ -334,7 +346,8 @@ int launch_sp_group_kernel(int ns, const IgemmGroup& g, int wtm, int wtn, bool f
 }
 
 // wide channel tiles with pre-split weights (fp16x2): builds the weight image into `img`, then the convolution
-int launch_spw_kernel(const IgemmArgs& a, int wtn, int ksplit, unsigned char* img, hipStream_t st) {
+// two_slab_ok: reductions of at most two slabs on 240-channel tiles take the two-slab instance
+int launch_spw_kernel(const IgemmArgs& a, int wtn, int ksplit, unsigned char* img, hipStream_t st, bool two_slab_ok) {
   const int BN = 16 * wtn;
   const int nslabs = (a.ntaps * (a.K / 16) + 1) / 2;
   hipLaunchKernelGGL(sp_weight_image_im2col_kernel, dim3((a.N / BN) * nslabs), dim3(256), 0, st, a.w, img, a.K, a.T, a.ntaps,
@@ -342,6 +355,10 @@ int launch_spw_kernel(const IgemmArgs& a, int wtn, int ksplit, unsigned char* im
   IgemmArgs b = a;
   b.wimg = img;
   const dim3 grid(ceil_div(a.M, 128) * (a.N / BN), ksplit);
+  if (two_slab_ok && wtn == 15 && nslabs <= 2 && ksplit == 1) {
+    hipLaunchKernelGGL((igemm_spw2_kernel<2, 15>), grid, dim3(256), 0, st, b);
+    return 0;
+  }
 #define SPW(N_) if (wtn == N_) { hipLaunchKernelGGL((igemm_spw_kernel<2, N_>), grid, dim3(256), 0, st, b); return 0; }
   SPW(6) SPW(8) SPW(12) SPW(15)
 #undef SPW

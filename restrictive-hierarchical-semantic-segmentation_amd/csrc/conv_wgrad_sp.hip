@@ -615,8 +615,10 @@ int launch_wgrad_sp_kernel(int ns, const WgradArgs& a, int tn, int tk, int gx, i
   return ns == 4 ? launch_wgrad_sp<4>(a, tn, tk, gx, tiles, st) : ns == 3 ? launch_wgrad_sp<3>(a, tn, tk, gx, tiles, st)
        : ns == 2 ? launch_wgrad_sp<2>(a, tn, tk, gx, tiles, st) : launch_wgrad_sp<1>(a, tn, tk, gx, tiles, st);
 }
-int launch_wgrad_spw_kernel(const WgradArgs& a, int gx, int tiles, hipStream_t st) {       // fp16x2, 240 x 144 block tiles
-  hipLaunchKernelGGL((wgrad_spw_kernel<4, 5, 3, 3, 3>), dim3(gx, tiles), dim3(576), 0, st, a);
+// fp16x2, 240 x 144 block tiles (nwc = 3: 3 x 3 waves) or 240 x 48 (nwc = 1: 3 waves, the layers of 48 input channels)
+int launch_wgrad_spw_kernel(const WgradArgs& a, int nwc, int gx, int tiles, hipStream_t st) {
+  if (nwc == 3) hipLaunchKernelGGL((wgrad_spw_kernel<4, 5, 3, 3, 3>), dim3(gx, tiles), dim3(576), 0, st, a);
+  else hipLaunchKernelGGL((wgrad_spw_kernel<4, 5, 3, 3, 1>), dim3(gx, tiles), dim3(192), 0, st, a);
   return 0;
 }
 int launch_wgrad_group_sp(const WgradGroup& g, int tn, int tk, int nblocks, hipStream_t st) {      // fp16x2 only

@@ -167,6 +167,116 @@ __global__ __launch_bounds__(256) void fuse_sum_kernel(FuseSumArgs a) {
   }
 }
 
+// HRNet head at branch resolution (hrseg_head_mix): y = t0 + sum_j up(t_j) + bias in place over t0, where t_j = W_j x_j are
+// the 1x1 convolutions of the branches at their own resolution -- bilinear weights do not depend on the channel and sum to
+// one, so the resize commutes with the 1x1 convolution.  fuse_sum_kernel's interpolation expression, the bias added last.
+// One block per pixel chunk (stats_body's chunk -> pixel range rule), threads = channel quads x `lanes` pixel lanes (up to
+// 1024 threads: a lane's walk is a chain of dependent loads, so the lanes are what keeps bytes in flight); a lane walks its
+// piece of the chunk in ascending order and keeps the fp32 sums of y and y^2, the block adds its lanes in lane order in fp64
+// and leaves row `chunk` of the [nchunks][2][C] partial sums the BatchNorm finalize phase reads: no atomics, the same bits
+// every run, and no statistics pass over y.
+struct HeadMixArgs {
+  float* y; int ldy;
+  const float* bias;
+  int n_low;
+  const float* low[3]; int ld_low[3]; int Hi[3], Wi[3];
+  float sh[3], sw[3];
+  int B, H, W, C, align, lanes;
+  double* partial; int nchunks;
+};
+static int head_mix_lanes(int C) { const int p = 1024 / (C / 4); return p > 16 ? 16 : p; }      // (ops.head_mix sizes nchunks by it)
+__global__ __launch_bounds__(1024) void head_mix_kernel(HeadMixArgs a) {
+  __shared__ float red[1024 * 8];
+  Lanes L;
+  L.Q = a.C >> 2; L.P = a.lanes; L.cq = threadIdx.x % L.Q; L.pl = threadIdx.x / L.Q; L.active = L.pl < L.P;
+  const long npix = (long)a.B * a.H * a.W;
+  const long per = (npix + a.nchunks - 1) / a.nchunks;
+  const long lo = (long)blockIdx.x * per;
+  const long hi = (lo + per < npix) ? lo + per : npix;
+  f32x4 s = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
+  if (L.active) {
+    f32x4 bias = {0.f, 0.f, 0.f, 0.f};
+    if (a.bias) bias = ld4(a.bias + 4 * L.cq);
+    // A pixel lane walks a contiguous piece of the chunk, left to right along the image rows, and keeps the two columns
+    // (x0, x1) x two rows (y0, y1) of every low-resolution term in registers: at a 2x .. 8x resize the next pixel needs the
+    // same columns or one new one, so a pixel costs 1.75 low-resolution loads on average instead of 12 (re-reads that would
+    // come from beyond L2: the pass would be bound by them, not by HBM)
+    const long len = (hi - lo + L.P - 1) / L.P;
+    const long p0 = lo + (long)L.pl * len, p1 = (p0 + len < hi) ? p0 + len : hi;
+    int cb[3], cy0[3], cy1[3], cxa[3], cxb[3];
+    f32x4 ca0[3], ca1[3], cb0[3], cb1[3];            // rows y0 / y1 of column xa, of column xb
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      cb[j] = cy0[j] = cy1[j] = cxa[j] = cxb[j] = -1;
+      ca0[j] = ca1[j] = cb0[j] = cb1[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    f32x4 nxt = {0.f, 0.f, 0.f, 0.f};
+    if (p0 < p1) nxt = ld4(a.y + p0 * a.ldy + 4 * L.cq);
+    for (long pix = p0; pix < p1; ++pix) {
+      float* o = a.y + pix * a.ldy + 4 * L.cq;
+      f32x4 v = nxt;
+      if (pix + 1 < p1) nxt = ld4(o + a.ldy);        // the next pixel's t0 is in flight across this pixel's arithmetic
+      const int b = (int)(pix / ((long)a.H * a.W));
+      const int rem = (int)(pix - (long)b * a.H * a.W);
+      const int oy = rem / a.W, ox = rem - oy * a.W;
+#pragma unroll
+      for (int j = 0; j < 3; ++j)
+        if (j < a.n_low) {
+          int y0, y1, x0, x1;
+          float ly0, ly1, lx0, lx1;
+          src_index(oy, a.sh[j], a.Hi[j], a.align, y0, y1, ly0, ly1);
+          src_index(ox, a.sw[j], a.Wi[j], a.align, x0, x1, lx0, lx1);
+          const int ld = a.ld_low[j], Wi = a.Wi[j];
+          const float* p = a.low[j] + (size_t)b * a.Hi[j] * Wi * ld + 4 * L.cq;
+          if (b != cb[j] || y0 != cy0[j] || y1 != cy1[j]) {
+            cb[j] = b; cy0[j] = y0; cy1[j] = y1;
+            cxa[j] = cxb[j] = -1;
+          }
+          if (x0 != cxa[j]) {
+            if (x0 == cxb[j]) {
+              ca0[j] = cb0[j]; ca1[j] = cb1[j];
+            } else {
+              ca0[j] = ld4(p + ((size_t)y0 * Wi + x0) * ld);
+              ca1[j] = ld4(p + ((size_t)y1 * Wi + x0) * ld);
+            }
+            cxa[j] = x0;
+          }
+          if (x1 != cxb[j]) {
+            if (x1 == cxa[j]) {
+              cb0[j] = ca0[j]; cb1[j] = ca1[j];
+            } else {
+              cb0[j] = ld4(p + ((size_t)y0 * Wi + x1) * ld);
+              cb1[j] = ld4(p + ((size_t)y1 * Wi + x1) * ld);
+            }
+            cxb[j] = x1;
+          }
+          v += ly0 * (lx0 * ca0[j] + lx1 * cb0[j]) + ly1 * (lx0 * ca1[j] + lx1 * cb1[j]);
+        }
+      v += bias;
+      st4(o, v);
+      s += v;
+      s2 += v * v;
+    }
+  }
+  if (!a.partial) return;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    red[threadIdx.x * 8 + j] = s[j];
+    red[threadIdx.x * 8 + 4 + j] = s2[j];
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < a.C; c += blockDim.x) {
+    double sa = 0.0, sb = 0.0;
+    for (int pl = 0; pl < L.P; ++pl) {
+      const int t = pl * L.Q + (c >> 2);
+      sa += red[t * 8 + (c & 3)];
+      sb += red[t * 8 + 4 + (c & 3)];
+    }
+    a.partial[((size_t)blockIdx.x * 2 + 0) * a.C + c] = sa;
+    a.partial[((size_t)blockIdx.x * 2 + 1) * a.C + c] = sb;
+  }
+}
+
 // gather form of the transpose: every input pixel sums the output pixels that read it (no atomics,
 // deterministic).  An 8x resize gives each input pixel an ~18x18 footprint and only a few thousand input
 // pixels: RS sub-lanes per pixel split the footprint rows (thread = channel quad x pixel lane x row split)
@@ -233,7 +343,149 @@ __global__ __launch_bounds__(256) void bilinear_bwd_kernel(const float* __restri
   }
 }
 
+// The same transpose onto up to three targets in ONE launch (hrseg_bilinear_bwd_multi: the backward of head_mix_kernel, all
+// C channels of dout onto every target).  Gather form, bilinear_bwd_kernel's weights, (wy * wx) * g products and row order.
+// Threads = `qs` channel quads (one of C / 4 / qs channel slabs) x `lanes`; a block works on one target: rs[t] lanes split
+// the footprint rows of a pixel and are added in lane order through LDS, lanes / rs[t] pixels per block.  Every element of
+// dout is read four times per target; what that costs is decided by where the re-reads are served from.  The work list is
+// ordered by (channel slab, image, band of output rows) -- the blocks of all targets whose pixels centre on a band follow each
+// other -- and dealt to the XCDs in contiguous pieces (xcd_remap): the rows of dout an XCD's blocks work on at one time are a
+// few MB of one slab and dout comes from HBM about once (measured: the re-reads still miss L2 and are served by the Infinity
+// Cache at about 8 TB/s, profiles/README.md "Shared head at branch resolution").  absmax (optional, [n][64], zeroed by the
+// caller): max|din| per target as hrseg_absmax leaves it (an integer maximum: order-independent).
+struct BilinearBwdMultiArgs {
+  const float* dout; int lddout;
+  int B, Hout, Wout, C, n, align, lanes, nbands, qs;
+  float* din[3]; int lddin[3]; int Hi[3], Wi[3];
+  float sh[3], sw[3];
+  int rs[3];             // row splits per pixel (power of two, divides lanes)
+  int nx[3], ny[3];      // most columns / rows of a footprint (table sizes)
+  int blk_end[3];        // blocks per (image, band): running sum over the targets
+  float* absmax;
+};
+__global__ __launch_bounds__(1024) void bilinear_bwd_multi_kernel(BilinearBwdMultiArgs a) {
+  __shared__ f32x4 red[1024];
+  __shared__ int meta[16][4];            // per pixel lane: first live row, rows, first live column, columns
+  extern __shared__ float wtab[];        // per pixel lane: wx[nx[t]], wy[ny[t]]
+  const int Q = a.qs;
+  const int ln = threadIdx.x / Q;
+  const bool active = ln < a.lanes;
+  const int per = a.blk_end[a.n - 1];
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);
+  const int bk = bid / per;
+  int r = bid - bk * per;
+  const int slab = bk / (a.B * a.nbands), ib = bk - slab * (a.B * a.nbands);
+  const int b = ib / a.nbands, band = ib - b * a.nbands;
+  const int cq = slab * Q + threadIdx.x % Q;
+  int t = 0;
+  while (t + 1 < a.n && r >= a.blk_end[t]) ++t;
+  if (t) r -= a.blk_end[t - 1];
+  const int Hi = a.Hi[t], Wi = a.Wi[t], RS = a.rs[t], PL = a.lanes / RS;
+  const float sh = a.sh[t], sw = a.sw[t];
+  const int Hr = a.Hout, Wr = a.Wout, align = a.align;
+  const int pl = ln % PL, rsi = ln / PL;
+  // target rows of this band: [ceil(band * Hi / nbands), ceil((band + 1) * Hi / nbands))
+  const int r0 = (band * Hi + a.nbands - 1) / a.nbands, r1 = ((band + 1) * Hi + a.nbands - 1) / a.nbands;
+  const int q = r * PL + pl;
+  const bool valid = active && q < (r1 - r0) * Wi;
+  const int iy = r0 + q / Wi, ix = q % Wi;
+  const float ish = sh > 0.f ? 1.f / sh : 0.f, isw = sw > 0.f ? 1.f / sw : 0.f;
+  // The weights of a pixel's footprint depend on the pixel alone, not on the channel or (wx) the row: the first thread of a
+  // pixel lane tabulates them in LDS once -- first live column and row, their counts, wx[] and wy[] with the zero weights at
+  // the edges trimmed (bilinear_bwd_kernel skips those terms) -- instead of every thread evaluating src_index for every
+  // (row, column) it visits, which is what bounded this kernel (instruction issue, not memory)
+  float* wxt = wtab + pl * (a.nx[t] + a.ny[t]);
+  float* wyt = wxt + a.nx[t];
+  if (valid && rsi == 0 && threadIdx.x % Q == 0) {
+    int oy_lo = 0, oy_hi = Hr - 1, ox_lo = 0, ox_hi = Wr - 1;
+    if (sh > 0.f) {
+      oy_lo = max(0, (int)floorf(((float)iy - 1.f + (align ? 0.f : 0.5f)) * ish - (align ? 0.f : 0.5f)) - 1);
+      oy_hi = min(Hr - 1, (int)ceilf(((float)iy + 1.f + (align ? 0.f : 0.5f)) * ish - (align ? 0.f : 0.5f)) + 1);
+    }
+    if (sw > 0.f) {
+      ox_lo = max(0, (int)floorf(((float)ix - 1.f + (align ? 0.f : 0.5f)) * isw - (align ? 0.f : 0.5f)) - 1);
+      ox_hi = min(Wr - 1, (int)ceilf(((float)ix + 1.f + (align ? 0.f : 0.5f)) * isw - (align ? 0.f : 0.5f)) + 1);
+    }
+    int ya = -1, ny = 0, xa = -1, nx = 0;
+    for (int oy = oy_lo; oy <= oy_hi; ++oy) {
+      int y0, y1;
+      float ly0, ly1;
+      src_index(oy, sh, Hi, align, y0, y1, ly0, ly1);
+      const float wy = (y0 == iy ? ly0 : 0.f) + (y1 == iy ? ly1 : 0.f);
+      if (ya < 0 && wy != 0.f) ya = oy;
+      if (ya >= 0 && oy - ya < a.ny[t]) {
+        wyt[oy - ya] = wy;
+        if (wy != 0.f) ny = oy - ya + 1;
+      }
+    }
+    for (int ox = ox_lo; ox <= ox_hi; ++ox) {
+      int x0, x1;
+      float lx0, lx1;
+      src_index(ox, sw, Wi, align, x0, x1, lx0, lx1);
+      const float wx = (x0 == ix ? lx0 : 0.f) + (x1 == ix ? lx1 : 0.f);
+      if (xa < 0 && wx != 0.f) xa = ox;
+      if (xa >= 0 && ox - xa < a.nx[t]) {
+        wxt[ox - xa] = wx;
+        if (wx != 0.f) nx = ox - xa + 1;
+      }
+    }
+    meta[pl][0] = ya; meta[pl][1] = ny; meta[pl][2] = xa; meta[pl][3] = nx;
+  }
+  __syncthreads();
+  f32x4 s = {0.f, 0.f, 0.f, 0.f};
+  if (valid) {
+    const int ya = meta[pl][0], ny = meta[pl][1], xa = meta[pl][2], nx = meta[pl][3];
+    for (int i = rsi; i < ny; i += RS) {
+      const float wy = wyt[i];
+      if (wy == 0.f) continue;
+      const float* row = a.dout + (((size_t)b * Hr + ya + i) * Wr + xa) * a.lddout + 4 * cq;
+#pragma unroll 4
+      for (int k = 0; k < nx; ++k) s += (wy * wxt[k]) * ld4(row + (size_t)k * a.lddout);
+    }
+  }
+  if (RS > 1) {                            // (one target per block: the branch is uniform)
+    red[threadIdx.x] = s;
+    __syncthreads();
+    if (valid && rsi == 0) {
+      for (int k = 1; k < RS; ++k) s += red[threadIdx.x + k * Q * PL];
+    }
+  }
+  float amax = 0.f;
+  if (valid && rsi == 0) {
+    st4(a.din[t] + (((size_t)b * Hi + iy) * Wi + ix) * a.lddin[t] + 4 * cq, s);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) amax = fmaxf(amax, (s[j] != s[j]) ? __builtin_inff() : fabsf(s[j]));
+  }
+  if (a.absmax) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+    if ((threadIdx.x & 63) == 0 && amax > 0.f)
+      atomicMax(reinterpret_cast<unsigned*>(a.absmax) + t * 64 + (bid & 63), __float_as_uint(amax));
+  }
+}
+
 // --------------------------------------------------------------------------- small glue
+// column blocks of a convolution weight [rows = Cout * taps][Cin] <-> n contiguous [rows][width_j] blocks laid end to end
+// (hrseg_weight_cols_gather / hrseg_weight_cols_scatter_add): the operands and the gradient staging of a layer that is
+// computed per input-channel block (the HRNet head at branch resolution)
+struct WeightColsArgs {
+  int n, rows, Cin;
+  int col0[9];           // first column of block j (col0[n] = Cin), all multiples of 4
+};
+__global__ __launch_bounds__(256) void weight_cols_kernel(const float* __restrict__ src, float* __restrict__ dst,
+                                                          WeightColsArgs a, int scatter_add) {
+  const int Q = a.Cin >> 2;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)a.rows * Q) return;
+  const int row = (int)(i / Q), c = 4 * (int)(i - (long)row * Q);
+  int j = 0;
+  while (j + 1 < a.n && c >= a.col0[j + 1]) ++j;
+  const int w = a.col0[j + 1] - a.col0[j];
+  const size_t full = (size_t)row * a.Cin + c, blk = (size_t)a.rows * a.col0[j] + (size_t)row * w + (c - a.col0[j]);
+  if (scatter_add) st4(dst + full, ld4(dst + full) + ld4(src + blk));
+  else st4(dst + blk, ld4(src + full));
+}
+
 __global__ __launch_bounds__(256) void add_kernel(const float* __restrict__ a, int lda, const float* __restrict__ b,
                                                   int ldb, float* __restrict__ out, int ldo, int relu, long npix,
                                                   int C) {
@@ -400,6 +652,111 @@ extern "C" int hrseg_fuse_sum(int n_same, const float* const* same, const int* l
   hipLaunchKernelGGL(fuse_sum_kernel, dim3(elem_grid(npix, C)), dim3(256), 0, (hipStream_t)stream, a);
   HRSEG_LAUNCH_CHECK("fuse_sum");
   return 0;
+}
+
+extern "C" int hrseg_head_mix(float* y, int ldy, const float* bias, int n_low, const float* const* low, const int* ld_low,
+                              const int* Hi, const int* Wi, int B, int H, int W, int C, int align_corners, double* partial,
+                              int nchunks, hrseg_stream_t stream) {
+  if (int e = check_c(C, "hrseg_head_mix")) return e;
+  HRSEG_CHECK_ARG(y && ldy >= C && ldy % 4 == 0 && n_low >= 0 && n_low <= 3 && B > 0 && H > 0 && W > 0,
+                  "hrseg_head_mix: bad arguments (0..3 low-resolution terms, ldy=%d C=%d)", ldy, C);
+  HRSEG_CHECK_ARG(n_low == 0 || (low && ld_low && Hi && Wi), "hrseg_head_mix: low-resolution terms need their geometry");
+  const long npix = (long)B * H * W;
+  HRSEG_CHECK_ARG(nchunks >= 1 && nchunks <= npix && nchunks <= 65535, "hrseg_head_mix: nchunks=%d must be in [1, min(pixels, 65535)]", nchunks);
+  HeadMixArgs a{};
+  a.y = y; a.ldy = ldy; a.bias = bias; a.n_low = n_low;
+  for (int j = 0; j < n_low; ++j) {
+    HRSEG_CHECK_ARG(low[j] && ld_low[j] >= C && ld_low[j] % 4 == 0 && Hi[j] > 0 && Wi[j] > 0, "hrseg_head_mix: bad low-resolution term %d", j);
+    a.low[j] = low[j]; a.ld_low[j] = ld_low[j]; a.Hi[j] = Hi[j]; a.Wi[j] = Wi[j];
+    a.sh[j] = resize_scale(Hi[j], H, align_corners);
+    a.sw[j] = resize_scale(Wi[j], W, align_corners);
+  }
+  a.B = B; a.H = H; a.W = W; a.C = C; a.align = align_corners; a.partial = partial; a.nchunks = nchunks;
+  a.lanes = head_mix_lanes(C);
+  hipLaunchKernelGGL(head_mix_kernel, dim3(nchunks), dim3((C / 4 * a.lanes + 63) / 64 * 64), 0, (hipStream_t)stream, a);
+  HRSEG_LAUNCH_CHECK("head_mix");
+  return 0;
+}
+
+extern "C" int hrseg_bilinear_bwd_multi(const float* dout, int lddout, int B, int Hout, int Wout, int C, int n,
+                                        float* const* din, const int* lddin, const int* Hi, const int* Wi, int align_corners,
+                                        float* absmax, hrseg_stream_t stream) {
+  if (int e = check_c(C, "hrseg_bilinear_bwd_multi")) return e;
+  HRSEG_CHECK_ARG(dout && lddout >= C && lddout % 4 == 0 && B > 0 && Hout > 0 && Wout > 0 && n >= 1 && n <= 3 && din && lddin &&
+                      Hi && Wi,
+                  "hrseg_bilinear_bwd_multi: bad arguments (1..3 targets, lddout=%d C=%d)", lddout, C);
+  BilinearBwdMultiArgs a{};
+  a.dout = dout; a.lddout = lddout; a.B = B; a.Hout = Hout; a.Wout = Wout; a.C = C; a.n = n; a.align = align_corners;
+  a.absmax = absmax;
+  // channel slabs of at most 32 quads (the largest such divisor of C / 4: 6 x 30 at 720 channels, 480 contiguous bytes per
+  // pixel); threads = quads of a slab x lanes (a power of two, at most 16, at most about 768 threads: 30 quads x 16)
+  int Q = C / 4;
+  const int nslab = [&] { int k = 1; while (Q % k || Q / k > 32) ++k; return k; }();
+  Q /= nslab;
+  a.qs = Q;
+  int lanes = 1;
+  while (lanes < 16 && Q * lanes * 2 <= 768) lanes *= 2;
+  a.lanes = lanes;
+  int nbands = Hi[0];
+  for (int j = 0; j < n; ++j) {
+    HRSEG_CHECK_ARG(din[j] && lddin[j] >= C && lddin[j] % 4 == 0 && Hi[j] > 0 && Wi[j] > 0, "hrseg_bilinear_bwd_multi: bad target %d", j);
+    if (Hi[j] < nbands) nbands = Hi[j];
+  }
+  a.nbands = nbands;
+  int end = 0, tab = 0;
+  for (int j = 0; j < n; ++j) {
+    a.din[j] = din[j]; a.lddin[j] = lddin[j]; a.Hi[j] = Hi[j]; a.Wi[j] = Wi[j];
+    a.sh[j] = resize_scale(Hi[j], Hout, align_corners);
+    a.sw[j] = resize_scale(Wi[j], Wout, align_corners);
+    // row splits: a quarter of the footprint rows, at most the lanes (an 8x resize has ~18 x 18 footprints and few pixels)
+    const int foot = (Hi[j] > 1 && Hout > 1) ? (int)(2.0 * (Hout - 1) / (Hi[j] - 1)) + 3 : Hout;
+    int rs = 1;
+    while (rs * 2 <= lanes && rs * 2 <= foot / 4) rs *= 2;
+    a.rs[j] = rs;
+    // a footprint spans the outputs whose source lies within one input pixel of the target: 2 / scale of them + the rounding
+    // of both ends (the kernel's candidate range); scale 0: one input row / column feeds every output
+    a.nx[j] = a.sw[j] > 0.f ? min(Wout, (int)(2.0 / a.sw[j]) + 6) : Wout;
+    a.ny[j] = a.sh[j] > 0.f ? min(Hout, (int)(2.0 / a.sh[j]) + 6) : Hout;
+    if (a.nx[j] + a.ny[j] > tab) tab = a.nx[j] + a.ny[j];
+    const int rows = ceil_div(Hi[j], nbands);              // most target rows in a band
+    end += ceil_div((long)rows * Wi[j], lanes / rs);
+    a.blk_end[j] = end;
+  }
+  const long blocks = (long)nslab * B * nbands * end;
+  HRSEG_CHECK_ARG(blocks < 2147483647L, "hrseg_bilinear_bwd_multi: %ld blocks exceed the grid", blocks);
+  const size_t lds = (size_t)lanes * tab * sizeof(float);
+  HRSEG_CHECK_ARG(lds <= 32768, "hrseg_bilinear_bwd_multi: footprints of %d weights per pixel exceed the weight table", tab);
+  hipLaunchKernelGGL(bilinear_bwd_multi_kernel, dim3((unsigned)blocks), dim3((Q * lanes + 63) / 64 * 64), lds, (hipStream_t)stream, a);
+  HRSEG_LAUNCH_CHECK("bilinear_bwd_multi");
+  return 0;
+}
+
+static int weight_cols(const char* who, const float* src, float* dst, int rows, int Cin, int n, const int* widths, int scatter_add,
+                       hrseg_stream_t stream) {
+  HRSEG_CHECK_ARG(src && dst && rows > 0 && Cin > 0 && Cin % 4 == 0 && n >= 1 && n <= 8 && widths && al16(src) && al16(dst),
+                  "%s: bad arguments (1..8 column blocks, 16-byte aligned buffers, Cin=%d)", who, Cin);
+  WeightColsArgs a{};
+  a.n = n; a.rows = rows; a.Cin = Cin;
+  int c = 0;
+  for (int j = 0; j < n; ++j) {
+    HRSEG_CHECK_ARG(widths[j] > 0 && widths[j] % 4 == 0, "%s: block width %d must be a positive multiple of 4", who, widths[j]);
+    a.col0[j] = c;
+    c += widths[j];
+  }
+  HRSEG_CHECK_ARG(c == Cin, "%s: block widths sum to %d, the weight has %d input channels", who, c, Cin);
+  a.col0[n] = Cin;
+  const long n4 = (long)rows * (Cin / 4);
+  hipLaunchKernelGGL(weight_cols_kernel, dim3(ceil_div(n4, 256)), dim3(256), 0, (hipStream_t)stream, src, dst, a, scatter_add);
+  HRSEG_LAUNCH_CHECK(who);
+  return 0;
+}
+extern "C" int hrseg_weight_cols_gather(const float* w, int rows, int Cin, int n, const int* widths, float* blocks,
+                                        hrseg_stream_t stream) {
+  return weight_cols("hrseg_weight_cols_gather", w, blocks, rows, Cin, n, widths, 0, stream);
+}
+extern "C" int hrseg_weight_cols_scatter_add(const float* blocks, int rows, int Cin, int n, const int* widths, float* dw,
+                                             hrseg_stream_t stream) {
+  return weight_cols("hrseg_weight_cols_scatter_add", blocks, dw, rows, Cin, n, widths, 1, stream);
 }
 
 extern "C" int hrseg_add(const float* a, int lda, const float* b, int ldb, float* out, int ldo, int relu, long npix,

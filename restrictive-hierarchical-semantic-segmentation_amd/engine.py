@@ -334,11 +334,80 @@ class Recorder:
                 ys, stats = ys
         if stats is not None and any(st is None for st in stats):
             stats = None                                 # (one statistics plan per grouped BatchNorm call)
+
+        def conv_backward(dys, gmax_all, gmaxs):
+            # the weight gradient is issued on the side stream BEFORE the data gradient of the same layer (issuing it behind,
+            # so that it would run beside the next BatchNorm backward, measured 55.9 vs 53.8 ms per step)
+            def weight_gradients():
+                if "skip_wgrad" in _EXPERIMENT:      # (measurement only: what the weight gradients cost the step beside the main chain)
+                    return
+                side = wgrad_stream(dys[0].device)
+                if side is not None:
+                    _lib.stream_wait(side, None)
+                with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
+                    if n == 1:
+                        ops.conv_wgrad(xs[0].data, dys[0], items[0][1].weight._hr_gstore, k, s, prec=self.prec, gmax=gmaxs[0],
+                                       x_split=xs[0].split)
+                    else:
+                        ops.conv_wgrad_group([x.data for x in xs], dys, [c.weight._hr_gstore for _, c, _, _ in items], k, s,
+                                             prec=self.prec, gmaxs=gmaxs, x_splits=[x.split for x in xs])
+                if side is not None:
+                    self._keep_for_side(side, gmax_all, *dys, *[x.data for x in xs])
+            weight_gradients()
+            # data gradients: rounds of problems whose inputs are distinct tensors
+            todo = [i for i, x in enumerate(xs) if x.needs_grad]
+            while todo:
+                seen, rnd, rest = set(), [], []
+                for i in todo:
+                    (rest if id(xs[i]) in seen else rnd).append(i)
+                    seen.add(id(xs[i]))
+                if len(rnd) == 1:
+                    i = rnd[0]
+                    x = xs[i]
+                    wp = self.wpersist and hasattr(items[i][1].weight, "_hr_tstore_range")
+                    if x.grad is None:
+                        x.grad = ops.conv_dgrad(dys[i], self._wt(items[i][1]), x.data.shape, k, s, prec=self.prec,
+                                                gmax=gmaxs[i], wpersist=wp)
+                    else:
+                        ops.conv_dgrad(dys[i], self._wt(items[i][1]), x.data.shape, k, s, out=x.grad, accumulate=True,
+                                       prec=self.prec, gmax=gmaxs[i], wpersist=wp)
+                else:
+                    got = ops.conv_dgrad_group([dys[i] for i in rnd], [self._wt(items[i][1]) for i in rnd],
+                                               [xs[i].data.shape for i in rnd], k, s, [xs[i].grad for i in rnd],
+                                               [xs[i].grad is not None for i in rnd], prec=self.prec,
+                                               gmaxs=[gmaxs[i] for i in rnd],
+                                               wpersist=self.wpersist and all(hasattr(items[i][1].weight, "_hr_tstore_range")
+                                                                              for i in rnd))
+                    for i, o in zip(rnd, got):
+                        xs[i].grad = o
+                todo = rest
+        return self._bn_tail([(bn, res) for _, _, bn, res in items], ys, stats, relus, conv_backward, outs=outs,
+                             single_reader=single_reader, split_for=split_for, split_level=split_level, defer=defer)
+
+    def _keep_for_side(self, side, *tensors):
+        """`tensors` (None entries skipped) are read by work just issued on the side stream: they stay allocated until it is done"""
+        tensors = [t for t in tensors if t is not None]
+        if _lib.taping():
+            # a recorded step is replayed without the allocator: what the side stream reads stays allocated
+            # until the streams join at the end of the reverse pass (_Run.backward)
+            _lib.tape_keep(*tensors)
+        else:
+            for t in tensors:
+                t.record_stream(side)     # not reused before the side stream is done reading it
+        self.used_side = True
+
+    def _bn_tail(self, bns, ys, stats, relus, backward, outs=None, single_reader=False, split_for=None, split_level=1,
+                 defer=False):
+        """The BatchNorm (+ residual) (+ ReLU) behind a group of convolution outputs `ys`, training or unfolded inference.
+        bns: one (bn, residual Act or None) per output; stats: the BatchNorm partial sums of each y where its producer left
+        them (the statistics launch is skipped), else None; backward(dys, gmax_all, gmaxs): the producer's reverse pass,
+        called with the gradients of the ys and their 64-slot |max| arrays (None outside fp16x2).  -> the output Acts"""
+        n = len(ys)
         # layers with a residual and a ReLU: the backward's mask is not recomputable from y; the forward leaves it as one
         # byte per channel quad (hrseg_bn_fwd_t.relu_mask) so that the backward reads 1/16 of what reading z costs
         masks = [torch.empty((y.shape[0] * y.shape[1] * y.shape[2], y.shape[3] // 4), dtype=torch.uint8, device=y.device)
-                 if (self.record and _RELU_MASK and relus[i] and it[3] is not None) else None
-                 for i, (it, y) in enumerate(zip(items, ys))]
+                 if (self.record and _RELU_MASK and relus[i] and res is not None) else None
+                 for i, ((_, res), y) in enumerate(zip(bns, ys))]
         z_split = False
         if split_for is not None and _X_SPLIT >= split_level and not _EXPERIMENT and (outs is None or all(o is None for o in outs)) \
                 and all(c is not None for c in split_for):
@@ -346,8 +415,8 @@ class Recorder:
             if all(c.kernel_size[0] == k2 and c.stride[0] == s2 for c in split_for):
                 z_split = ops.conv_x_split_ok([tuple(y.shape) for y in ys], [c.out_channels for c in split_for], k2, s2, self.prec)
                 # (a layer with residual + ReLU hands its backward the mask bytes; without them the backward would read z as fp32)
-                z_split = z_split and all(m is not None or not (relus[i] and it[3] is not None)
-                                          for i, (it, m) in enumerate(zip(items, masks)))
+                z_split = z_split and all(m is not None or not (relus[i] and res is not None)
+                                          for i, ((_, res), m) in enumerate(zip(bns, masks)))
         bn_items = [dict(y=y, gamma=bn.weight._hr_store, beta=bn.bias._hr_store, rm=bn.running_mean, rv=bn.running_var,
                          nbt=bn.num_batches_tracked, momentum=bn.momentum, eps=bn.eps,
                          residual=res.data if res is not None else None, residual_split=bool(res is not None and res.split),
@@ -355,8 +424,8 @@ class Recorder:
                          stat_div=self.bn_segments, relu_mask=masks[i],
                          out=outs[i] if outs is not None else None, z_split=z_split,
                          partial=stats[i] if stats is not None else None)
-                    for i, ((x, conv, bn, res), y) in enumerate(zip(items, ys))]
-        defer = (defer and self.defer_head and n == 1 and relus[0] and items[0][3] is None and not z_split
+                    for i, ((bn, res), y) in enumerate(zip(bns, ys))]
+        defer = (defer and self.defer_head and n == 1 and relus[0] and bns[0][1] is None and not z_split
                  and (outs is None or outs[0] is None) and not _lib.deterministic())
         if defer:
             # statistics + finalize only; the apply phase runs on demand (DeferredAct.data).  `out` = y satisfies the library's
@@ -394,7 +463,7 @@ class Recorder:
             # fp16x2: the BN backward records max|dy| per problem; the data / weight gradients scale dy by it
             gmax_all = torch.empty((n, 64), dtype=torch.float32, device=ys[0].device) if want_gmax else None    # reset by bn_bwd
             gmaxs = [gmax_all[i] for i in range(n)] if want_gmax else [None] * n
-            for i, ((x, conv, bn, res), y, z, coef) in enumerate(zip(items, ys, zs, coefs)):
+            for i, ((bn, res), y, z, coef) in enumerate(zip(bns, ys, zs, coefs)):
                 dz = z.grad
                 z.grad = None
                 dres, dres_acc = None, False
@@ -420,62 +489,7 @@ class Recorder:
                 gmaxs = [gmax_all[0] if gmax_all is not None else None]
             else:
                 dys, gmax_all, gmaxs = bn_backward()
-            # the weight gradient is issued on the side stream BEFORE the data gradient of the same layer (issuing it behind,
-            # so that it would run beside the next BatchNorm backward, measured 55.9 vs 53.8 ms per step)
-            def weight_gradients():
-                if "skip_wgrad" in _EXPERIMENT:      # (measurement only: what the weight gradients cost the step beside the main chain)
-                    return
-                side = wgrad_stream(dys[0].device)
-                if side is not None:
-                    _lib.stream_wait(side, None)
-                with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
-                    if n == 1:
-                        ops.conv_wgrad(xs[0].data, dys[0], items[0][1].weight._hr_gstore, k, s, prec=self.prec, gmax=gmaxs[0],
-                                       x_split=xs[0].split)
-                    else:
-                        ops.conv_wgrad_group([x.data for x in xs], dys, [c.weight._hr_gstore for _, c, _, _ in items], k, s,
-                                             prec=self.prec, gmaxs=gmaxs, x_splits=[x.split for x in xs])
-                if side is not None:
-                    if _lib.taping():
-                        # a recorded step is replayed without the allocator: what the side stream reads stays allocated
-                        # until the streams join at the end of the reverse pass (_Run.backward)
-                        _lib.tape_keep(gmax_all, *dys, *[x.data for x in xs])
-                    else:
-                        if gmax_all is not None:
-                            gmax_all.record_stream(side)
-                        for t in dys:
-                            t.record_stream(side)     # not reused before the side stream is done reading it
-                        for x in xs:
-                            x.data.record_stream(side)
-                    self.used_side = True
-            weight_gradients()
-            # data gradients: rounds of problems whose inputs are distinct tensors
-            todo = [i for i, x in enumerate(xs) if x.needs_grad]
-            while todo:
-                seen, rnd, rest = set(), [], []
-                for i in todo:
-                    (rest if id(xs[i]) in seen else rnd).append(i)
-                    seen.add(id(xs[i]))
-                if len(rnd) == 1:
-                    i = rnd[0]
-                    x = xs[i]
-                    wp = self.wpersist and hasattr(items[i][1].weight, "_hr_tstore_range")
-                    if x.grad is None:
-                        x.grad = ops.conv_dgrad(dys[i], self._wt(items[i][1]), x.data.shape, k, s, prec=self.prec,
-                                                gmax=gmaxs[i], wpersist=wp)
-                    else:
-                        ops.conv_dgrad(dys[i], self._wt(items[i][1]), x.data.shape, k, s, out=x.grad, accumulate=True,
-                                       prec=self.prec, gmax=gmaxs[i], wpersist=wp)
-                else:
-                    got = ops.conv_dgrad_group([dys[i] for i in rnd], [self._wt(items[i][1]) for i in rnd],
-                                               [xs[i].data.shape for i in rnd], k, s, [xs[i].grad for i in rnd],
-                                               [xs[i].grad is not None for i in rnd], prec=self.prec,
-                                               gmaxs=[gmaxs[i] for i in rnd],
-                                               wpersist=self.wpersist and all(hasattr(items[i][1].weight, "_hr_tstore_range")
-                                                                              for i in rnd))
-                    for i, o in zip(rnd, got):
-                        xs[i].grad = o
-                todo = rest
+            backward(dys, gmax_all, gmaxs)
         self._push(bwd)
         return zs
 
@@ -560,6 +574,87 @@ class Recorder:
                         ops.copy(g, a.grad)
             self._push(bwd)
         return y
+
+    # ------------------------------------------------------------------ HRNet head at branch resolution
+    def head_conv_bn(self, xs, conv, bn, align_corners=True, defer=True):
+        """upsample_concat(xs) -> conv_bn(conv 1x1 + bias, bn, ReLU) of the HRNet head (training), without the concatenated
+        tensor: bilinear weights do not depend on the channel and sum to one, so
+            conv(cat_j up(x_j)) + b = W_0 x_0 + sum_{j>=1} up(W_j x_j) + b,     W_j = the weight's column block of branch j,
+        and every convolution runs at its branch's own resolution (1/8 of the multiply-adds at 48/96/192/384 channels).
+        Forward: column blocks gathered (hrseg_weight_cols_gather), t_0 = W_0 x_0 at full resolution, t_1.. grouped at branch
+        resolution, hrseg_head_mix adds them up in place and leaves the BatchNorm partial sums; then the BatchNorm tail of
+        conv_bn (returns what conv_bn(..., defer=defer) returns).  Backward, from the tail's dy: dW_0 on the side stream, the
+        bilinear transposes dt_j of dy in one launch, data gradients through the row blocks of the transposed weight, grouped
+        dW_j, and one scatter-add of the staged weight-gradient blocks into the layer's gradient columns."""
+        assert conv.kernel_size[0] == 1 and conv.stride[0] == 1 and self.training and 2 <= len(xs) <= 4
+        assert not any(x.split for x in xs)
+        x0, lows = xs[0], list(xs[1:])
+        chans = [x.data.shape[3] for x in xs]
+        Cout, nl = conv.out_channels, len(lows)
+        assert sum(chans) == conv.in_channels
+        wg = ops.weight_cols_gather(conv.weight._hr_store, Cout, chans)
+        t0 = ops.conv_fwd(x0.data, wg[0], None, 1, 1, cout=Cout, prec=self.prec)
+        if nl == 1:
+            ts = [ops.conv_fwd(lows[0].data, wg[1], None, 1, 1, cout=Cout, prec=self.prec)]
+        else:
+            ts = ops.conv_fwd_group([x.data for x in lows], wg[1:], [None] * nl, 1, 1, [Cout] * nl, prec=self.prec)
+        # (cross-rank statistics all-reduce the partial sums of a pool of their own: they keep their statistics launch)
+        stats = ops.head_mix(t0, ts, conv.bias._hr_store if conv.bias is not None else None, align_corners,
+                             stats=self.sync is None and not _EXPERIMENT)
+        want_gmax = self.prec in (_lib.CONV_PRECISION["fp16x2"], _lib.CONV_PRECISION["auto"])
+
+        def backward(dys, gmax_all, gmaxs):
+            dy, gmax = dys[0], gmaxs[0]
+            dev = dy.device
+            side = wgrad_stream(dev) if "skip_wgrad" not in _EXPERIMENT else None
+            on_side = (lambda: torch.cuda.stream(side)) if side is not None else contextlib.nullcontext
+            # weight gradients are staged per column block (contiguous [Cout][c_j], zeroed by the library's fill kernel)
+            stage = ops.zeros((Cout * sum(chans),), torch.float32, dev)
+            dws = ops._col_blocks(stage, Cout, chans)
+            if "skip_wgrad" not in _EXPERIMENT:
+                if side is not None:
+                    _lib.stream_wait(side, None)
+                with on_side():
+                    ops.conv_wgrad(x0.data, dy, dws[0], 1, 1, prec=self.prec, gmax=gmax)
+            dts, tmax = ops.bilinear_bwd_multi(dy, [tuple(x.data.shape[1:3]) for x in lows], align_corners, want_absmax=want_gmax)
+            tmaxs = [tmax[j] for j in range(nl)] if want_gmax else [None] * nl
+            # data gradients: the transposed weight [Cin][1][Cout] has one contiguous row block per branch
+            wt = self._wt(conv)
+            wts = ops._col_blocks(wt, Cout, chans)
+            if x0.needs_grad:
+                if x0.grad is None:
+                    x0.grad = ops.conv_dgrad(dy, wts[0], x0.data.shape, 1, 1, prec=self.prec, gmax=gmax)
+                else:
+                    ops.conv_dgrad(dy, wts[0], x0.data.shape, 1, 1, out=x0.grad, accumulate=True, prec=self.prec, gmax=gmax)
+            todo = [j for j, x in enumerate(lows) if x.needs_grad]
+            if len(todo) == 1:
+                j = todo[0]
+                x = lows[j]
+                if x.grad is None:
+                    x.grad = ops.conv_dgrad(dts[j], wts[j + 1], x.data.shape, 1, 1, prec=self.prec, gmax=tmaxs[j])
+                else:
+                    ops.conv_dgrad(dts[j], wts[j + 1], x.data.shape, 1, 1, out=x.grad, accumulate=True, prec=self.prec,
+                                   gmax=tmaxs[j])
+            elif todo:
+                got = ops.conv_dgrad_group([dts[j] for j in todo], [wts[j + 1] for j in todo], [lows[j].data.shape for j in todo],
+                                           1, 1, [lows[j].grad for j in todo], [lows[j].grad is not None for j in todo],
+                                           prec=self.prec, gmaxs=[tmaxs[j] for j in todo])
+                for j, o in zip(todo, got):
+                    lows[j].grad = o
+            if "skip_wgrad" in _EXPERIMENT:
+                return
+            if side is not None:
+                _lib.stream_wait(side, None)
+            with on_side():
+                if nl == 1:
+                    ops.conv_wgrad(lows[0].data, dts[0], dws[1], 1, 1, prec=self.prec, gmax=tmaxs[0])
+                else:
+                    ops.conv_wgrad_group([x.data for x in lows], dts, dws[1:], 1, 1, prec=self.prec, gmaxs=tmaxs)
+                # (inside this backward: ahead of the mark at which the layer's gradient bucket is declared final)
+                ops.weight_cols_scatter_add(stage, Cout, chans, conv.weight._hr_gstore)
+            if side is not None:
+                self._keep_for_side(side, gmax_all, tmax, dy, stage, *dts, *[x.data for x in xs])
+        return self._bn_tail([(bn, None)], [t0], [stats] if stats is not None else None, [True], backward, defer=defer)[0]
 
     # ------------------------------------------------------------------ HRNet head concat (models.py:743-747)
     def upsample_concat(self, xs, align_corners=True):

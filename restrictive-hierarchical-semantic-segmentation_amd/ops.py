@@ -484,6 +484,55 @@ def fuse_sum(same, lows, relu=True, align_corners=True):
     return out
 
 
+HEAD_MIX_MAX_CHUNKS = 1024       # pixel chunks (= blocks = partial-sum rows) of hrseg_head_mix
+
+
+def head_mix(y, lows, bias=None, align_corners=True, stats=True):
+    """y += sum of the bilinearly up-sampled lows + bias, in place (hrseg_head_mix: the HRNet head at branch resolution).
+    stats=True: -> (partial, rows), the BatchNorm partial sums of the result for bn_fwd_group's item "partial"; else None"""
+    B, H, W, Cn = y.shape
+    npix, q = B * H * W, Cn // 4
+    nch = max(1, min(HEAD_MIX_MAX_CHUNKS, npix // (4 * min(16, 1024 // q))))       # at least 4 pixels per pixel lane (csrc/elem.hip head_mix_lanes)
+    part = torch.empty(nch * 2 * Cn, dtype=torch.float64, device=y.device) if stats else None
+    call("hrseg_head_mix", ptr(y), _ld(y), ptr(bias), len(lows), _lib.ptr_array(lows) if lows else None,
+         _lib.int_array([_ld(t) for t in lows]) if lows else None, _lib.int_array([t.shape[1] for t in lows]) if lows else None,
+         _lib.int_array([t.shape[2] for t in lows]) if lows else None, B, H, W, Cn, int(align_corners), ptr(part), nch)
+    return (part, nch) if stats else None
+
+
+def bilinear_bwd_multi(dout, sizes, align_corners=True, want_absmax=False):
+    """the transpose of the bilinear resize of dout onto every (Hi, Wi) of `sizes` (1..3) in one launch, all channels each:
+    -> (dins, absmax [n][64] or None: max|din| per target as hrseg_absmax leaves it)"""
+    B, H, W, Cn = dout.shape
+    dins = [empty_nhwc(B, h, w, Cn, dout) for h, w in sizes]
+    amax = zeros((len(sizes), 64), torch.float32, dout.device) if want_absmax else None
+    call("hrseg_bilinear_bwd_multi", ptr(dout), _ld(dout), B, H, W, Cn, len(sizes), _lib.ptr_array(dins),
+         _lib.int_array([_ld(t) for t in dins]), _lib.int_array([h for h, _ in sizes]), _lib.int_array([w for _, w in sizes]),
+         int(align_corners), ptr(amax))
+    return dins, amax
+
+
+def _col_blocks(buf, rows, widths):
+    out, off = [], 0
+    for w in widths:
+        out.append(buf[off:off + rows * w])
+        off += rows * w
+    return out
+
+
+def weight_cols_gather(w_store, rows, widths):
+    """column blocks of a weight [rows][sum(widths)] as contiguous [rows][width] matrices -> list of flat tensors (views of
+    one buffer): the operands of a layer that is computed per input-channel block"""
+    buf = torch.empty(rows * sum(widths), dtype=torch.float32, device=w_store.device)
+    call("hrseg_weight_cols_gather", ptr(w_store), rows, sum(widths), len(widths), _lib.int_array(widths), ptr(buf))
+    return _col_blocks(buf, rows, widths)
+
+
+def weight_cols_scatter_add(blocks_buf, rows, widths, dw):
+    """dw[rows][sum(widths)] += the column blocks laid end to end in blocks_buf (the reverse of weight_cols_gather)"""
+    call("hrseg_weight_cols_scatter_add", ptr(blocks_buf), rows, sum(widths), len(widths), _lib.int_array(widths), ptr(dw))
+
+
 def add(a, b, relu=False, out=None):
     if out is None:
         out = torch.empty(a.shape, dtype=torch.float32, device=a.device)
