@@ -58,7 +58,7 @@ int hrseg_abi_version(void);
  * :579-582 stem, :614 shared_head 1x1, :656 downsample, :690,:701 transitions.
  * k in {1,3}, stride in {1,2}, pad = (k-1)/2.  Cin, Cout multiples of 16
  * (implicit GEMM on v_mfma_f32_16x16x4_f32) except the stem-style Cin<=4 layer,
- * which hrseg_conv_fwd/wgrad route to direct kernels.                        */
+ * which the forward and weight-gradient calls route to direct kernels.       */
 /* Arithmetic of the contraction (operands and results are fp32 in memory in every mode):
  *   F32     fp32 operands on v_mfma_f32_16x16x4_f32 (exact fp32 products)
  *   BF16X3  each operand split exactly into 3 bf16 pieces, the 6 largest of the 9 piece products on
@@ -109,31 +109,25 @@ typedef struct {
                                image instead of writing one in front of the launch.  0 (default): never cached            */
 } hrseg_conv_shape_t;
 
-/* 1 when the forward call hrseg_conv_fwd(_group)(n, shapes) would run the wave-specialised kernels for EVERY problem and
+/* 1 when the forward call hrseg_conv_fwd_group(n, shapes) would run the wave-specialised kernels for EVERY problem and
  * hrseg_conv_wgrad_group_ws would run the nine-tap kernel for all of them, i.e. when the producer of x may store it pre-split
  * (x_split); 0 otherwise.  Pure host logic on the shapes, the attached scratch / tuning state and the precision.           */
 int hrseg_conv_x_split_ok(int n, const hrseg_conv_shape_t* shapes);
-/* y = conv(x, w) + bias.  w: [Cout][k*k][Cin]; bias may be NULL. */
-int hrseg_conv_fwd(const float* x, const float* w, const float* bias, float* y,
-                   const hrseg_conv_shape_t* s, hrseg_stream_t stream);
-/* dx = conv_transpose(dy, w) (+ dx if accumulate).  wt: [Cin][k*k][Cout]
- * (hrseg_weight_transpose of w).  Shape as the forward conv's. */
-int hrseg_conv_dgrad(const float* dy, const float* wt, float* dx, int accumulate,
-                     const hrseg_conv_shape_t* s, hrseg_stream_t stream);
-/* dw += x (*) dy  (fp32 atomics; dw is [Cout][k*k][Cin] and must hold the
- * running gradient, zeroed by the caller at the start of a step). */
-int hrseg_conv_wgrad(const float* x, const float* dy, float* dw,
-                     const hrseg_conv_shape_t* s, hrseg_stream_t stream);
 /* all conv weights of a flat parameter buffer at once: `table` (device, 8 ints per entry) lists one
  * 32x32 (cout,cin) tile of one tap per entry {slot offset, Cout, taps, Cin, co0, ci0, tap, 0}; the
  * transposed weight of a slot is written at the same offset of flat_t. */
 int hrseg_weight_transpose_all(const float* flat, float* flat_t, const int* table, int nentries,
                                hrseg_stream_t stream);
-/* Grouped forms: n independent convolutions (the parallel HRNet branches, models.py:524-525; the
- * fuse paths of a module, :483-511) in ONE launch when n <= 8 and they can share a kernel instance
- * (channel counts all multiples of 48 or all of 64), else n separate launches; a stride-2 data
- * gradient is one launch per problem (its four parity classes grouped).  Problems of one data-gradient
- * call must write distinct dx buffers.  Pointer arrays are HOST arrays. */
+/* The convolution calls: n >= 1 independent convolutions (a single layer is a group of one; the parallel
+ * HRNet branches, models.py:524-525; the fuse paths of a module, :483-511) in ONE launch when 2 <= n <= 8
+ * and they can share a kernel instance (channel counts all multiples of 48 or all of 64), else n separate
+ * launches; a stride-2 data gradient is one launch per problem (its four parity classes grouped).  Problems
+ * of one data-gradient call must write distinct dx buffers.  Pointer arrays are HOST arrays.
+ *   fwd:   y = conv(x, w) + bias.  w: [Cout][k*k][Cin]; `bias`, or any bias[i], may be NULL.
+ *   dgrad: dx = conv_transpose(dy, w) (+ dx where accumulate[i]).  wt: [Cin][k*k][Cout]
+ *          (hrseg_weight_transpose of w).  Shape as the forward conv's.
+ *   wgrad: dw += x (*) dy  (fp32 atomics; dw is [Cout][k*k][Cin] and must hold the running gradient,
+ *          zeroed by the caller at the start of a step). */
 int hrseg_conv_fwd_group(int n, const float* const* x, const float* const* w,
                          const float* const* bias, float* const* y,
                          const hrseg_conv_shape_t* shapes, hrseg_stream_t stream);

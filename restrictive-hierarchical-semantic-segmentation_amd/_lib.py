@@ -68,9 +68,6 @@ class DecodeTree(C.Structure):
 
 # name -> argtypes, exactly the prototypes of include/hrseg.h
 PROTOTYPES = {
-    "hrseg_conv_fwd": [_p, _p, _p, _p, C.POINTER(ConvShape), _p],
-    "hrseg_conv_dgrad": [_p, _p, _p, _i, C.POINTER(ConvShape), _p],
-    "hrseg_conv_wgrad": [_p, _p, _p, C.POINTER(ConvShape), _p],
     "hrseg_conv_fwd_group": [_i, _p, _p, _p, _p, C.POINTER(ConvShape), _p],
     "hrseg_conv_dgrad_group": [_i, _p, _p, _p, _p, C.POINTER(ConvShape), _p],
     "hrseg_conv_wgrad_group": [_i, _p, _p, _p, C.POINTER(ConvShape), _p],
@@ -283,7 +280,7 @@ for _name, _args in PROTOTYPES.items():
     _fn[_name] = f
 
 
-ABI_VERSION = 16    # must equal hrseg_abi_version() of the built library (struct layouts above)
+ABI_VERSION = 17    # must equal hrseg_abi_version() of the built library (struct layouts above)
 
 
 raw = {}

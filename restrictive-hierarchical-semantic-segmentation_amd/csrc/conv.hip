@@ -936,143 +936,20 @@ static void resolve_wgrad_shapes(int n, const hrseg_conv_shape_t* in, hrseg_conv
   }
 }
 
-// ---- grouped entry points: n independent problems, one launch when they can share a kernel
-extern "C" int hrseg_conv_fwd_group(int n, const float* const* x, const float* const* w, const float* const* bias,
-                                    float* const* y, const hrseg_conv_shape_t* shapes, hrseg_stream_t stream) {
-  HRSEG_CHECK_ARG(n >= 1 && x && w && y && shapes, "hrseg_conv_fwd_group: bad arguments");
-  hipStream_t st = (hipStream_t)stream;
-  bool ok = n <= MAXG;
-  for (int i = 0; i < n; ++i) {
-    if (int e = check_shape(&shapes[i], "hrseg_conv_fwd_group")) return e;
-    ok = ok && mfma_shape(&shapes[i]) && shapes[i].precision == shapes[0].precision;
-  }
-  if (ok && n >= 2) {
-    IgemmArgs a[MAXG];
-    for (int i = 0; i < n; ++i) fill_fwd_args(a[i], x[i], w[i], bias ? bias[i] : nullptr, y[i], &shapes[i]);
-    const int rc = launch_group_checked(a, n, shapes[0].precision, st, "igemm_group(fwd)");
-    if (rc <= 0) return rc;
-  }
-  for (int i = 0; i < n; ++i)
-    if (int e = hrseg_conv_fwd(x[i], w[i], bias ? bias[i] : nullptr, y[i], &shapes[i], stream)) return e;
-  return 0;
-}
-
-extern "C" int hrseg_conv_dgrad_group(int n, const float* const* dy, const float* const* wt, float* const* dx,
-                                      const int* accumulate, const hrseg_conv_shape_t* shapes,
-                                      hrseg_stream_t stream) {
-  HRSEG_CHECK_ARG(n >= 1 && dy && wt && dx && accumulate && shapes, "hrseg_conv_dgrad_group: bad arguments");
-  hipStream_t st = (hipStream_t)stream;
-  bool ok = n <= MAXG;
-  for (int i = 0; i < n; ++i) {
-    if (int e = check_shape(&shapes[i], "hrseg_conv_dgrad_group")) return e;
-    ok = ok && mfma_shape(&shapes[i]) && shapes[i].stride == 1 && shapes[i].precision == shapes[0].precision;
-  }
-  if (ok && n >= 2) {
-    IgemmArgs a[MAXG];
-    for (int i = 0; i < n; ++i) fill_dgrad_s1_args(a[i], dy[i], wt[i], dx[i], accumulate[i], &shapes[i]);
-    const int rc = launch_group_checked(a, n, shapes[0].precision, st, "igemm_group(dgrad)");
-    if (rc <= 0) return rc;
-  }
-  for (int i = 0; i < n; ++i)
-    if (int e = hrseg_conv_dgrad(dy[i], wt[i], dx[i], accumulate[i], &shapes[i], stream)) return e;
-  return 0;
-}
-
-extern "C" int hrseg_conv_wgrad_group(int n, const float* const* x, const float* const* dy, float* const* dw,
-                                      const hrseg_conv_shape_t* shapes, hrseg_stream_t stream) {
-  HRSEG_CHECK_ARG(n >= 1 && x && dy && dw && shapes, "hrseg_conv_wgrad_group: bad arguments");
-  for (int i = 0; i < n; ++i)
-    if (shapes[i].x_split) return x_split_unsupported("hrseg_conv_wgrad_group");
-  hipStream_t st = (hipStream_t)stream;
-  bool ok = n <= MAXG;
-  for (int i = 0; i < n; ++i) {
-    if (int e = check_shape(&shapes[i], "hrseg_conv_wgrad_group")) return e;
-    ok = ok && mfma_shape(&shapes[i]);
-  }
-  if (ok && n >= 2) {
-    WgradArgs a[MAXG];
-    hrseg_conv_shape_t rs[MAXG];
-    resolve_wgrad_shapes(n, shapes, rs);
-    int prec = rs[0].precision;
-    for (int i = 0; i < n; ++i) {
-      fill_wgrad_args(a[i], x[i], dy[i], dw[i], &rs[i]);
-      if (rs[i].precision != prec) prec = HRSEG_CONV_F32;
-    }
-    if (dispatch_wgrad_group(a, n, prec, st) == 0) {
-      HRSEG_LAUNCH_CHECK("wgrad_group");
-      return 0;
-    }
-  }
-  for (int i = 0; i < n; ++i)
-    if (int e = hrseg_conv_wgrad(x[i], dy[i], dw[i], &shapes[i], stream)) return e;
-  return 0;
-}
-
-extern "C" size_t hrseg_conv_wgrad_workspace_bytes(int n, const hrseg_conv_shape_t* shapes_in) {
-  if (!shapes_in || n < 1 || n > WG9_MAXG) return 0;
-  hrseg_conv_shape_t shapes[WG9_MAXG];
-  resolve_wgrad_shapes(n, shapes_in, shapes);
-  for (int i = 0; i < n; ++i)
-    if (check_shape(&shapes[i], "hrseg_conv_wgrad_workspace_bytes")) return 0;
-  return wgrad9_ws_bytes(n, shapes);
-}
-
-// Yes only when EVERY problem of the forward call goes out through the wave-specialised kernels (fp16x2 arithmetic) and the
-// weight gradients through the nine-tap kernel.  It asks the predicates hrseg_conv_fwd(_group) and hrseg_conv_wgrad_group_ws
-// route by (ws_take, igemm_overridden, wgrad9_ws_bytes, wgrad9_reads_x_split) and adds only what is its own: which calls it
-// vouches for.  The calls themselves refuse x_split on any other route, so a mismatch is an error, never a misread tensor.
-extern "C" int hrseg_conv_x_split_ok(int n, const hrseg_conv_shape_t* shapes) {
-  if (!hrseg_g_x_split || !shapes || n < 1 || n > MAXG || n > WG9_MAXG) return 0;
-  // (the overrides make a grouped call issue its problems one by one: not vouched for, whatever n)
-  if (!ws_route_open() || igemm_overridden()) return 0;
-  for (int i = 0; i < n; ++i) {
-    const hrseg_conv_shape_t& s = shapes[i];
-    if (s.ksize != 3 || s.stride != 1 || s.residual || s.relu || !mfma_shape(&s) || s.precision != shapes[0].precision) return 0;
-    if (s.precision != HRSEG_CONV_AUTO && !(s.precision == HRSEG_CONV_FP16X2 && n == 1)) return 0;      // (explicit fp16x2 GROUPS run the block-synchronous kernels)
-    if (s.B < 1 || s.Hi < 1 || s.Wi < 1 || s.Ho != s.Hi || s.Wo != s.Wi) return 0;
-    IgemmArgs a;
-    fill_fwd_args(a, reinterpret_cast<const float*>(256), reinterpret_cast<const float*>(256), nullptr, reinterpret_cast<float*>(256), &s);
-    a.stat_partial = nullptr; a.stat_rows = nullptr;
-    if (finalize_args(a) || !ws_take(a)) return 0;
-  }
-  hrseg_conv_shape_t rs[WG9_MAXG];
-  resolve_wgrad_shapes(n, shapes, rs);
-  for (int i = 0; i < n; ++i)
-    if (!wgrad9_reads_x_split(rs[i].precision)) return 0;
-  return wgrad9_ws_bytes(n, rs) > 0 ? 1 : 0;
-}
-
-extern "C" int hrseg_conv_wgrad_group_ws(int n, const float* const* x, const float* const* dy, float* const* dw,
-                                         const hrseg_conv_shape_t* shapes_in, void* workspace, size_t workspace_bytes,
-                                         hrseg_stream_t stream) {
-  HRSEG_CHECK_ARG(n >= 1 && x && dy && dw && shapes_in, "hrseg_conv_wgrad_group_ws: bad arguments");
-  if (n > WG9_MAXG) return hrseg_conv_wgrad_group(n, x, dy, dw, shapes_in, stream);
-  hrseg_conv_shape_t shapes[WG9_MAXG];
-  resolve_wgrad_shapes(n, shapes_in, shapes);
-  for (int i = 0; i < n; ++i)
-    if (int e = check_shape(&shapes[i], "hrseg_conv_wgrad_group_ws")) return e;
-  const size_t need = wgrad9_ws_bytes(n, shapes);
-  if (need && workspace && workspace_bytes >= need) {
-    for (int i = 0; i < n; ++i) HRSEG_CHECK_ARG(x[i] && dy[i] && dw[i], "hrseg_conv_wgrad_group_ws: null pointer");
-    return dispatch_wgrad9(n, x, dy, dw, shapes, (float*)workspace, (hipStream_t)stream);
-  }
-  return hrseg_conv_wgrad_group(n, x, dy, dw, shapes, stream);
-}
-
-extern "C" int hrseg_conv_fwd(const float* x, const float* w, const float* bias, float* y,
-                              const hrseg_conv_shape_t* s, hrseg_stream_t stream) {
-  if (int e = check_shape(s, "hrseg_conv_fwd")) return e;
-  HRSEG_CHECK_ARG(x && w && y, "hrseg_conv_fwd: null pointer");
-  hipStream_t st = (hipStream_t)stream;
-  HRSEG_CHECK_ARG(s->Cout % 16 == 0 || s->Cin <= HRSEG_SMALL_CIN_MAX, "hrseg_conv_fwd: Cout %d not a multiple of 16", s->Cout);
+// ---- one problem on its own: what a group of one is, and what every problem of a group that cannot share a launch becomes.
+// The group entry has run check_shape; `who` names it in the messages.
+static int fwd_one(const float* x, const float* w, const float* bias, float* y, const hrseg_conv_shape_t* s,
+                   hipStream_t st, const char* who) {
+  HRSEG_CHECK_ARG(x && w && y, "%s: null pointer", who);
+  HRSEG_CHECK_ARG(s->Cout % 16 == 0 || s->Cin <= HRSEG_SMALL_CIN_MAX, "%s: Cout %d not a multiple of 16", who, s->Cout);
   if (s->Cin <= HRSEG_SMALL_CIN_MAX) {
     launch_small_cin_fwd(x, w, bias, y, s, st);
     hrseg_count(CNT_SMALL_CIN);
     HRSEG_LAUNCH_CHECK("conv_small_cin_fwd");
     return 0;
   }
-  HRSEG_CHECK_ARG(s->Cin % 16 == 0, "hrseg_conv_fwd: Cin %d not a multiple of 16", s->Cin);
-  HRSEG_CHECK_ARG(s->ldx % 4 == 0 && s->ldy % 4 == 0, "hrseg_conv_fwd: ld must be a multiple of 4");
+  HRSEG_CHECK_ARG(s->Cin % 16 == 0, "%s: Cin %d not a multiple of 16", who, s->Cin);
+  HRSEG_CHECK_ARG(s->ldx % 4 == 0 && s->ldy % 4 == 0, "%s: ld must be a multiple of 4", who);
   IgemmArgs a;
   fill_fwd_args(a, x, w, bias, y, s);
   if (int e = dispatch_igemm(a, s->precision, st)) return e;
@@ -1080,26 +957,24 @@ extern "C" int hrseg_conv_fwd(const float* x, const float* w, const float* bias,
   return 0;
 }
 
-extern "C" int hrseg_conv_dgrad(const float* dy, const float* wt, float* dx, int accumulate,
-                                const hrseg_conv_shape_t* s, hrseg_stream_t stream) {
-  if (int e = check_shape(s, "hrseg_conv_dgrad")) return e;
-  HRSEG_CHECK_ARG(dy && wt && dx, "hrseg_conv_dgrad: null pointer");
+static int dgrad_one(const float* dy, const float* wt, float* dx, int accumulate, const hrseg_conv_shape_t* s,
+                     hipStream_t st, const char* who) {
+  HRSEG_CHECK_ARG(dy && wt && dx, "%s: null pointer", who);
   if (s->Cin <= HRSEG_SMALL_CIN_MAX) {
     // first layer with a differentiable input (logit-concatenated re-encoding): `wt` is the FORWARD weight [Cout][k*k][Cin]
-    launch_small_cin_dgrad(dy, wt, dx, accumulate, s, (hipStream_t)stream);
+    launch_small_cin_dgrad(dy, wt, dx, accumulate, s, st);
     hrseg_count(CNT_SMALL_CIN);
     HRSEG_LAUNCH_CHECK("conv_small_cin_dgrad");
     return 0;
   }
-  HRSEG_CHECK_ARG(s->Cin % 16 == 0 && s->Cout % 16 == 0, "hrseg_conv_dgrad: channels (%d,%d) must be multiples of 16",
-                  s->Cin, s->Cout);
-  HRSEG_CHECK_ARG(s->ldx % 4 == 0 && s->ldy % 4 == 0, "hrseg_conv_dgrad: ld must be a multiple of 4");
-  hipStream_t st = (hipStream_t)stream;
+  HRSEG_CHECK_ARG(s->Cin % 16 == 0 && s->Cout % 16 == 0, "%s: channels (%d,%d) must be multiples of 16", who, s->Cin, s->Cout);
+  HRSEG_CHECK_ARG(s->ldx % 4 == 0 && s->ldy % 4 == 0, "%s: ld must be a multiple of 4", who);
   IgemmArgs a;
   if (s->stride == 1) {
     fill_dgrad_s1_args(a, dy, wt, dx, accumulate, s);
-    // This entry point does not pass w_persistent on (the grouped one does): a single data gradient builds its weight
-    // image in the scratch ring at every call and registers nothing in the caller's arena.
+    // A problem issued on its own does not pass w_persistent on (the grouped launch does): it builds its weight image in
+    // the scratch ring at every call and registers nothing in the caller's arena.  That is what a single data gradient has
+    // always done; honouring the flag here would change which weight image these launches read, and nobody has timed that.
     a.w_persistent = 0;
     if (int e = dispatch_igemm(a, s->precision, st)) return e;
     HRSEG_LAUNCH_CHECK("igemm_conv(dgrad)");
@@ -1142,16 +1017,12 @@ extern "C" int hrseg_conv_dgrad(const float* dy, const float* wt, float* dx, int
   return 0;
 }
 
-extern "C" int hrseg_conv_wgrad(const float* x, const float* dy, float* dw, const hrseg_conv_shape_t* s_in,
-                                hrseg_stream_t stream) {
-  if (s_in && s_in->x_split) return x_split_unsupported("hrseg_conv_wgrad");
-  HRSEG_CHECK_ARG(s_in != nullptr, "hrseg_conv_wgrad: null shape");
+static int wgrad_one(const float* x, const float* dy, float* dw, const hrseg_conv_shape_t* s_in, hipStream_t st,
+                     const char* who) {
   hrseg_conv_shape_t sh;
   resolve_wgrad_shapes(1, s_in, &sh);
   const hrseg_conv_shape_t* s = &sh;
-  if (int e = check_shape(s, "hrseg_conv_wgrad")) return e;
-  HRSEG_CHECK_ARG(x && dy && dw, "hrseg_conv_wgrad: null pointer");
-  hipStream_t st = (hipStream_t)stream;
+  HRSEG_CHECK_ARG(x && dy && dw, "%s: null pointer", who);
   if (s->Cin <= HRSEG_SMALL_CIN_MAX) {
     const long M = (long)s->B * s->Ho * s->Wo;
     // ~512 blocks (measured, tools/misc_bench.py): every block adds into the same Cout*T*Cin
@@ -1163,9 +1034,8 @@ extern "C" int hrseg_conv_wgrad(const float* x, const float* dy, float* dw, cons
     HRSEG_LAUNCH_CHECK("conv_small_cin_wgrad");
     return 0;
   }
-  HRSEG_CHECK_ARG(s->Cin % 16 == 0 && s->Cout % 16 == 0, "hrseg_conv_wgrad: channels (%d,%d) must be multiples of 16",
-                  s->Cin, s->Cout);
-  HRSEG_CHECK_ARG(s->ldx % 4 == 0 && s->ldy % 4 == 0, "hrseg_conv_wgrad: ld must be a multiple of 4");
+  HRSEG_CHECK_ARG(s->Cin % 16 == 0 && s->Cout % 16 == 0, "%s: channels (%d,%d) must be multiples of 16", who, s->Cin, s->Cout);
+  HRSEG_CHECK_ARG(s->ldx % 4 == 0 && s->ldy % 4 == 0, "%s: ld must be a multiple of 4", who);
   WgradArgs a;
   fill_wgrad_args(a, x, dy, dw, s);
   if (const int ns = sp_pieces(s->precision)) {
@@ -1183,6 +1053,129 @@ extern "C" int hrseg_conv_wgrad(const float* x, const float* dy, float* dw, cons
   hrseg_count(CNT_WGRAD_F32);
   HRSEG_LAUNCH_CHECK("wgrad");
   return 0;
+}
+
+// ---- grouped entry points: n independent problems, one launch when they can share a kernel
+extern "C" int hrseg_conv_fwd_group(int n, const float* const* x, const float* const* w, const float* const* bias,
+                                    float* const* y, const hrseg_conv_shape_t* shapes, hrseg_stream_t stream) {
+  HRSEG_CHECK_ARG(n >= 1 && x && w && y && shapes, "hrseg_conv_fwd_group: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  bool ok = n <= MAXG;
+  for (int i = 0; i < n; ++i) {
+    if (int e = check_shape(&shapes[i], "hrseg_conv_fwd_group")) return e;
+    ok = ok && mfma_shape(&shapes[i]) && shapes[i].precision == shapes[0].precision;
+  }
+  if (ok && n >= 2) {
+    IgemmArgs a[MAXG];
+    for (int i = 0; i < n; ++i) fill_fwd_args(a[i], x[i], w[i], bias ? bias[i] : nullptr, y[i], &shapes[i]);
+    const int rc = launch_group_checked(a, n, shapes[0].precision, st, "igemm_group(fwd)");
+    if (rc <= 0) return rc;
+  }
+  for (int i = 0; i < n; ++i)
+    if (int e = fwd_one(x[i], w[i], bias ? bias[i] : nullptr, y[i], &shapes[i], st, "hrseg_conv_fwd_group")) return e;
+  return 0;
+}
+
+extern "C" int hrseg_conv_dgrad_group(int n, const float* const* dy, const float* const* wt, float* const* dx,
+                                      const int* accumulate, const hrseg_conv_shape_t* shapes,
+                                      hrseg_stream_t stream) {
+  HRSEG_CHECK_ARG(n >= 1 && dy && wt && dx && accumulate && shapes, "hrseg_conv_dgrad_group: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  bool ok = n <= MAXG;
+  for (int i = 0; i < n; ++i) {
+    if (int e = check_shape(&shapes[i], "hrseg_conv_dgrad_group")) return e;
+    ok = ok && mfma_shape(&shapes[i]) && shapes[i].stride == 1 && shapes[i].precision == shapes[0].precision;
+  }
+  if (ok && n >= 2) {
+    IgemmArgs a[MAXG];
+    for (int i = 0; i < n; ++i) fill_dgrad_s1_args(a[i], dy[i], wt[i], dx[i], accumulate[i], &shapes[i]);
+    const int rc = launch_group_checked(a, n, shapes[0].precision, st, "igemm_group(dgrad)");
+    if (rc <= 0) return rc;
+  }
+  for (int i = 0; i < n; ++i)
+    if (int e = dgrad_one(dy[i], wt[i], dx[i], accumulate[i], &shapes[i], st, "hrseg_conv_dgrad_group")) return e;
+  return 0;
+}
+
+extern "C" int hrseg_conv_wgrad_group(int n, const float* const* x, const float* const* dy, float* const* dw,
+                                      const hrseg_conv_shape_t* shapes, hrseg_stream_t stream) {
+  HRSEG_CHECK_ARG(n >= 1 && x && dy && dw && shapes, "hrseg_conv_wgrad_group: bad arguments");
+  for (int i = 0; i < n; ++i)
+    if (shapes[i].x_split) return x_split_unsupported("hrseg_conv_wgrad_group");
+  hipStream_t st = (hipStream_t)stream;
+  bool ok = n <= MAXG;
+  for (int i = 0; i < n; ++i) {
+    if (int e = check_shape(&shapes[i], "hrseg_conv_wgrad_group")) return e;
+    ok = ok && mfma_shape(&shapes[i]);
+  }
+  if (ok && n >= 2) {
+    WgradArgs a[MAXG];
+    hrseg_conv_shape_t rs[MAXG];
+    resolve_wgrad_shapes(n, shapes, rs);
+    int prec = rs[0].precision;
+    for (int i = 0; i < n; ++i) {
+      fill_wgrad_args(a[i], x[i], dy[i], dw[i], &rs[i]);
+      if (rs[i].precision != prec) prec = HRSEG_CONV_F32;
+    }
+    if (dispatch_wgrad_group(a, n, prec, st) == 0) {
+      HRSEG_LAUNCH_CHECK("wgrad_group");
+      return 0;
+    }
+  }
+  for (int i = 0; i < n; ++i)
+    if (int e = wgrad_one(x[i], dy[i], dw[i], &shapes[i], st, "hrseg_conv_wgrad_group")) return e;
+  return 0;
+}
+
+extern "C" size_t hrseg_conv_wgrad_workspace_bytes(int n, const hrseg_conv_shape_t* shapes_in) {
+  if (!shapes_in || n < 1 || n > WG9_MAXG) return 0;
+  hrseg_conv_shape_t shapes[WG9_MAXG];
+  resolve_wgrad_shapes(n, shapes_in, shapes);
+  for (int i = 0; i < n; ++i)
+    if (check_shape(&shapes[i], "hrseg_conv_wgrad_workspace_bytes")) return 0;
+  return wgrad9_ws_bytes(n, shapes);
+}
+
+// Yes only when EVERY problem of the forward call goes out through the wave-specialised kernels (fp16x2 arithmetic) and the
+// weight gradients through the nine-tap kernel.  It asks the predicates hrseg_conv_fwd_group and hrseg_conv_wgrad_group_ws
+// route by (ws_take, igemm_overridden, wgrad9_ws_bytes, wgrad9_reads_x_split) and adds only what is its own: which calls it
+// vouches for.  The calls themselves refuse x_split on any other route, so a mismatch is an error, never a misread tensor.
+extern "C" int hrseg_conv_x_split_ok(int n, const hrseg_conv_shape_t* shapes) {
+  if (!hrseg_g_x_split || !shapes || n < 1 || n > MAXG || n > WG9_MAXG) return 0;
+  // (the overrides make a grouped call issue its problems one by one: not vouched for, whatever n)
+  if (!ws_route_open() || igemm_overridden()) return 0;
+  for (int i = 0; i < n; ++i) {
+    const hrseg_conv_shape_t& s = shapes[i];
+    if (s.ksize != 3 || s.stride != 1 || s.residual || s.relu || !mfma_shape(&s) || s.precision != shapes[0].precision) return 0;
+    if (s.precision != HRSEG_CONV_AUTO && !(s.precision == HRSEG_CONV_FP16X2 && n == 1)) return 0;      // (explicit fp16x2 GROUPS run the block-synchronous kernels)
+    if (s.B < 1 || s.Hi < 1 || s.Wi < 1 || s.Ho != s.Hi || s.Wo != s.Wi) return 0;
+    IgemmArgs a;
+    fill_fwd_args(a, reinterpret_cast<const float*>(256), reinterpret_cast<const float*>(256), nullptr, reinterpret_cast<float*>(256), &s);
+    a.stat_partial = nullptr; a.stat_rows = nullptr;
+    if (finalize_args(a) || !ws_take(a)) return 0;
+  }
+  hrseg_conv_shape_t rs[WG9_MAXG];
+  resolve_wgrad_shapes(n, shapes, rs);
+  for (int i = 0; i < n; ++i)
+    if (!wgrad9_reads_x_split(rs[i].precision)) return 0;
+  return wgrad9_ws_bytes(n, rs) > 0 ? 1 : 0;
+}
+
+extern "C" int hrseg_conv_wgrad_group_ws(int n, const float* const* x, const float* const* dy, float* const* dw,
+                                         const hrseg_conv_shape_t* shapes_in, void* workspace, size_t workspace_bytes,
+                                         hrseg_stream_t stream) {
+  HRSEG_CHECK_ARG(n >= 1 && x && dy && dw && shapes_in, "hrseg_conv_wgrad_group_ws: bad arguments");
+  if (n > WG9_MAXG) return hrseg_conv_wgrad_group(n, x, dy, dw, shapes_in, stream);
+  hrseg_conv_shape_t shapes[WG9_MAXG];
+  resolve_wgrad_shapes(n, shapes_in, shapes);
+  for (int i = 0; i < n; ++i)
+    if (int e = check_shape(&shapes[i], "hrseg_conv_wgrad_group_ws")) return e;
+  const size_t need = wgrad9_ws_bytes(n, shapes);
+  if (need && workspace && workspace_bytes >= need) {
+    for (int i = 0; i < n; ++i) HRSEG_CHECK_ARG(x[i] && dy[i] && dw[i], "hrseg_conv_wgrad_group_ws: null pointer");
+    return dispatch_wgrad9(n, x, dy, dw, shapes, (float*)workspace, (hipStream_t)stream);
+  }
+  return hrseg_conv_wgrad_group(n, x, dy, dw, shapes, stream);
 }
 
 extern "C" int hrseg_weight_transpose(const float* w, float* wt, int Cout, int taps, int Cin,

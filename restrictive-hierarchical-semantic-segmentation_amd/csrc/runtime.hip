@@ -15,7 +15,7 @@ void hrseg_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* hrseg_last_error_string(void) { return g_err; }
-extern "C" int hrseg_abi_version(void) { return 16; }
+extern "C" int hrseg_abi_version(void) { return 17; }
 
 // ---- launch counters
 long hrseg_g_cnt[CNT_N];

@@ -283,15 +283,15 @@ class Recorder:
                                   split_for=[split_for] if split_for is not None else None, defer=defer)[0]
 
     def conv_bn_group(self, items, relu, outs=None, single_reader=False, split_for=None, split_level=1, defer=False):
-        """... split_for: one convolution per item that is the ONLY reader of that item's output (conv1 -> conv2 of a block).
-        Where the library will run those readers on the kernels that take a pre-split pixel operand (hrseg_conv_x_split_ok:
-        wave-specialised forward + nine-tap weight gradient, fp16x2 arithmetic) the BatchNorm apply writes the output
-        pre-split -- the same bytes the readers' staging waves would compute from the fp32 tensor, computed once."""
         """items: list of (x, conv, bn, residual-or-None), independent of each other (the parallel
         HRNet branches, the fuse paths of a module; a single layer is a group of one); relu: one flag or
         one per item.  Per group: one conv launch, three BN launches; backward: three BN launches, one
         wgrad launch and one dgrad launch per round of problems with DISTINCT inputs (two problems
-        that read the same tensor must not write its gradient in one launch)."""
+        that read the same tensor must not write its gradient in one launch).
+        split_for: one convolution per item that is the ONLY reader of that item's output (conv1 -> conv2 of a block).
+        Where the library will run those readers on the kernels that take a pre-split pixel operand (hrseg_conv_x_split_ok:
+        wave-specialised forward + nine-tap weight gradient, fp16x2 arithmetic) the BatchNorm apply writes the output
+        pre-split -- the same bytes the readers' staging waves would compute from the fp32 tensor, computed once."""
         n = len(items)
         relus = list(relu) if isinstance(relu, (list, tuple)) else [relu] * n
         k, s = items[0][1].kernel_size[0], items[0][1].stride[0]
@@ -303,35 +303,19 @@ class Recorder:
             folded = [self.fold(conv, bn) for _, conv, bn, _ in items]
             res = [it[3].data if it[3] is not None else None for it in items]
             prec = self.prec if all(f[2] for f in folded) else _lib.CONV_PRECISION["f32"]    # (a folded weight out of fp16x2's range)
-            if n == 1:
-                conv = items[0][1]
-                zs = [ops.conv_fwd(xs[0].data, folded[0][0], folded[0][1], k, s, cout=conv.out_channels, prec=prec,
-                                   residual=res[0], relu=relus[0], out=outs[0] if outs is not None else None)]
-            else:
-                assert outs is None or all(o is None for o in outs)
-                zs = ops.conv_fwd_group([x.data for x in xs], [f[0] for f in folded], [f[1] for f in folded], k, s,
-                                        [c.out_channels for _, c, _, _ in items], prec=prec, residuals=res, relus=relus)
+            zs = ops.conv_fwd_group([x.data for x in xs], [f[0] for f in folded], [f[1] for f in folded], k, s,
+                                    [c.out_channels for _, c, _, _ in items], prec=prec, residuals=res, relus=relus, outs=outs)
             return [Act(z) for z in zs]
         # training: the convolution kernels that can leave the BatchNorm partial sums of their output behind (the
         # wave-specialised 3x3 kernels: hrseg_conv_shape_t.stat_partial) -- the statistics launch is then skipped below
         want_stats = self.training and _CONV_STATS and self.sync is None and not _lib.deterministic() and not _EXPERIMENT
         stats = None
-        if n == 1:
-            conv = items[0][1]
-            ys = ops.conv_fwd(xs[0].data, conv.weight._hr_store, conv.bias._hr_store if conv.bias is not None else None,
-                              k, s, cout=conv.out_channels, prec=self.prec, stats=want_stats, wpersist=self.wpersist,
-                              x_split=xs[0].split)
-            if want_stats:
-                ys, st = ys
-                stats = [st]
-            ys = [ys]
-        else:
-            ys = ops.conv_fwd_group([x.data for x in xs], [c.weight._hr_store for _, c, _, _ in items],
-                                    [c.bias._hr_store if c.bias is not None else None for _, c, _, _ in items], k, s,
-                                    [c.out_channels for _, c, _, _ in items], prec=self.prec, stats=want_stats,
-                                    wpersist=self.wpersist, x_splits=[x.split for x in xs])
-            if want_stats:
-                ys, stats = ys
+        ys = ops.conv_fwd_group([x.data for x in xs], [c.weight._hr_store for _, c, _, _ in items],
+                                [c.bias._hr_store if c.bias is not None else None for _, c, _, _ in items], k, s,
+                                [c.out_channels for _, c, _, _ in items], prec=self.prec, stats=want_stats,
+                                wpersist=self.wpersist, x_splits=[x.split for x in xs])
+        if want_stats:
+            ys, stats = ys
         if stats is not None and any(st is None for st in stats):
             stats = None                                 # (one statistics plan per grouped BatchNorm call)
 
@@ -345,12 +329,8 @@ class Recorder:
                 if side is not None:
                     _lib.stream_wait(side, None)
                 with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
-                    if n == 1:
-                        ops.conv_wgrad(xs[0].data, dys[0], items[0][1].weight._hr_gstore, k, s, prec=self.prec, gmax=gmaxs[0],
-                                       x_split=xs[0].split)
-                    else:
-                        ops.conv_wgrad_group([x.data for x in xs], dys, [c.weight._hr_gstore for _, c, _, _ in items], k, s,
-                                             prec=self.prec, gmaxs=gmaxs, x_splits=[x.split for x in xs])
+                    ops.conv_wgrad_group([x.data for x in xs], dys, [c.weight._hr_gstore for _, c, _, _ in items], k, s,
+                                         prec=self.prec, gmaxs=gmaxs, x_splits=[x.split for x in xs])
                 if side is not None:
                     self._keep_for_side(side, gmax_all, *dys, *[x.data for x in xs])
             weight_gradients()
@@ -361,25 +341,14 @@ class Recorder:
                 for i in todo:
                     (rest if id(xs[i]) in seen else rnd).append(i)
                     seen.add(id(xs[i]))
-                if len(rnd) == 1:
-                    i = rnd[0]
-                    x = xs[i]
-                    wp = self.wpersist and hasattr(items[i][1].weight, "_hr_tstore_range")
-                    if x.grad is None:
-                        x.grad = ops.conv_dgrad(dys[i], self._wt(items[i][1]), x.data.shape, k, s, prec=self.prec,
-                                                gmax=gmaxs[i], wpersist=wp)
-                    else:
-                        ops.conv_dgrad(dys[i], self._wt(items[i][1]), x.data.shape, k, s, out=x.grad, accumulate=True,
-                                       prec=self.prec, gmax=gmaxs[i], wpersist=wp)
-                else:
-                    got = ops.conv_dgrad_group([dys[i] for i in rnd], [self._wt(items[i][1]) for i in rnd],
-                                               [xs[i].data.shape for i in rnd], k, s, [xs[i].grad for i in rnd],
-                                               [xs[i].grad is not None for i in rnd], prec=self.prec,
-                                               gmaxs=[gmaxs[i] for i in rnd],
-                                               wpersist=self.wpersist and all(hasattr(items[i][1].weight, "_hr_tstore_range")
-                                                                              for i in rnd))
-                    for i, o in zip(rnd, got):
-                        xs[i].grad = o
+                # (a round of one runs as a single problem, which builds its weight image per call whatever wpersist says)
+                wp = self.wpersist and all(hasattr(items[i][1].weight, "_hr_tstore_range") for i in rnd)
+                got = ops.conv_dgrad_group([dys[i] for i in rnd], [self._wt(items[i][1]) for i in rnd],
+                                           [xs[i].data.shape for i in rnd], k, s, [xs[i].grad for i in rnd],
+                                           [xs[i].grad is not None for i in rnd], prec=self.prec,
+                                           gmaxs=[gmaxs[i] for i in rnd], wpersist=wp)
+                for i, o in zip(rnd, got):
+                    xs[i].grad = o
                 todo = rest
         return self._bn_tail([(bn, res) for _, _, bn, res in items], ys, stats, relus, conv_backward, outs=outs,
                              single_reader=single_reader, split_for=split_for, split_level=split_level, defer=defer)
@@ -593,11 +562,8 @@ class Recorder:
         Cout, nl = conv.out_channels, len(lows)
         assert sum(chans) == conv.in_channels
         wg = ops.weight_cols_gather(conv.weight._hr_store, Cout, chans)
-        t0 = ops.conv_fwd(x0.data, wg[0], None, 1, 1, cout=Cout, prec=self.prec)
-        if nl == 1:
-            ts = [ops.conv_fwd(lows[0].data, wg[1], None, 1, 1, cout=Cout, prec=self.prec)]
-        else:
-            ts = ops.conv_fwd_group([x.data for x in lows], wg[1:], [None] * nl, 1, 1, [Cout] * nl, prec=self.prec)
+        t0 = ops.conv_fwd_group([x0.data], wg[:1], [None], 1, 1, [Cout], prec=self.prec)[0]
+        ts = ops.conv_fwd_group([x.data for x in lows], wg[1:], [None] * nl, 1, 1, [Cout] * nl, prec=self.prec)
         # (cross-rank statistics all-reduce the partial sums of a pool of their own: they keep their statistics launch)
         stats = ops.head_mix(t0, ts, conv.bias._hr_store if conv.bias is not None else None, align_corners,
                              stats=self.sync is None and not _EXPERIMENT)
@@ -615,27 +581,17 @@ class Recorder:
                 if side is not None:
                     _lib.stream_wait(side, None)
                 with on_side():
-                    ops.conv_wgrad(x0.data, dy, dws[0], 1, 1, prec=self.prec, gmax=gmax)
+                    ops.conv_wgrad_group([x0.data], [dy], dws[:1], 1, 1, prec=self.prec, gmaxs=[gmax])
             dts, tmax = ops.bilinear_bwd_multi(dy, [tuple(x.data.shape[1:3]) for x in lows], align_corners, want_absmax=want_gmax)
             tmaxs = [tmax[j] for j in range(nl)] if want_gmax else [None] * nl
             # data gradients: the transposed weight [Cin][1][Cout] has one contiguous row block per branch
             wt = self._wt(conv)
             wts = ops._col_blocks(wt, Cout, chans)
             if x0.needs_grad:
-                if x0.grad is None:
-                    x0.grad = ops.conv_dgrad(dy, wts[0], x0.data.shape, 1, 1, prec=self.prec, gmax=gmax)
-                else:
-                    ops.conv_dgrad(dy, wts[0], x0.data.shape, 1, 1, out=x0.grad, accumulate=True, prec=self.prec, gmax=gmax)
+                x0.grad = ops.conv_dgrad_group([dy], wts[:1], [x0.data.shape], 1, 1, [x0.grad], [x0.grad is not None],
+                                               prec=self.prec, gmaxs=[gmax])[0]
             todo = [j for j, x in enumerate(lows) if x.needs_grad]
-            if len(todo) == 1:
-                j = todo[0]
-                x = lows[j]
-                if x.grad is None:
-                    x.grad = ops.conv_dgrad(dts[j], wts[j + 1], x.data.shape, 1, 1, prec=self.prec, gmax=tmaxs[j])
-                else:
-                    ops.conv_dgrad(dts[j], wts[j + 1], x.data.shape, 1, 1, out=x.grad, accumulate=True, prec=self.prec,
-                                   gmax=tmaxs[j])
-            elif todo:
+            if todo:
                 got = ops.conv_dgrad_group([dts[j] for j in todo], [wts[j + 1] for j in todo], [lows[j].data.shape for j in todo],
                                            1, 1, [lows[j].grad for j in todo], [lows[j].grad is not None for j in todo],
                                            prec=self.prec, gmaxs=[tmaxs[j] for j in todo])
@@ -646,10 +602,7 @@ class Recorder:
             if side is not None:
                 _lib.stream_wait(side, None)
             with on_side():
-                if nl == 1:
-                    ops.conv_wgrad(lows[0].data, dts[0], dws[1], 1, 1, prec=self.prec, gmax=tmaxs[0])
-                else:
-                    ops.conv_wgrad_group([x.data for x in lows], dts, dws[1:], 1, 1, prec=self.prec, gmaxs=tmaxs)
+                ops.conv_wgrad_group([x.data for x in lows], dts, dws[1:], 1, 1, prec=self.prec, gmaxs=tmaxs)
                 # (inside this backward: ahead of the mark at which the layer's gradient bucket is declared final)
                 ops.weight_cols_scatter_add(stage, Cout, chans, conv.weight._hr_gstore)
             if side is not None:

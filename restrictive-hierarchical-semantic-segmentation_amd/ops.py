@@ -129,65 +129,27 @@ def _guard_prec(x, prec):
 range_fallbacks = 0
 
 
-def conv_fwd(x, w, bias, k, s, out=None, cout=None, prec=0, residual=None, relu=False, stats=False, wpersist=False,
-             x_split=False):
-    """x NHWC, w storage [Cout][k*k][Cin] (a channels_last [Cout,Cin,k,k] parameter);
-    pass `cout` when w is the flat 1-D parameter slot.  `prec`: _lib.CONV_PRECISION code (all conv functions).
-    stats=True: -> (out, (partial, rows) or None): the BatchNorm partial sums of the output where the kernel that ran
-    produces them in its epilogue (hrseg_conv_shape_t.stat_partial), else None"""
-    _lib.ensure_scratch(x.device)
-    if not x_split:                        # (a pre-split tensor is not fp32 data: its producer's fp32 values were in range)
-        prec = _guard_prec(x, prec)
-    B, Hi, Wi, Cin = x.shape
-    Cout = cout if cout is not None else w.shape[0]
-    if out is None:
-        out = empty_nhwc(B, conv_out_size(Hi, k, s), conv_out_size(Wi, k, s), Cout, x)
-    st = _stat_buffer(Cout, x.device) if stats else None
-    sh = _shape(x.shape, _ld(x), Cout, _ld(out), k, s, prec, residual=residual, relu=relu, stat=st, wpersist=wpersist,
-                x_split=x_split)
-    call("hrseg_conv_fwd", ptr(x), ptr(w), ptr(bias), ptr(out), C.byref(sh))
-    if stats:
-        return out, ((st[0], st[1].value) if st[1].value > 0 else None)
-    return out
-
-
-def conv_dgrad(dy, wt, x_shape, k, s, out=None, accumulate=False, prec=0, gmax=None, wpersist=False):
-    """wt = weight_transpose(w): [Cin][k*k][Cout]."""
-    _lib.ensure_scratch(dy.device)
-    B, Hi, Wi, Cin = x_shape
-    if out is None:
-        out = empty_nhwc(B, Hi, Wi, Cin, dy)
-        accumulate = False
-    sh = _shape(x_shape, _ld(out), dy.shape[3], _ld(dy), k, s, prec, gmax, wpersist=wpersist)
-    call("hrseg_conv_dgrad", ptr(dy), ptr(wt), ptr(out), int(accumulate), C.byref(sh))
-    return out
-
-
-def conv_wgrad(x, dy, dw, k, s, prec=0, gmax=None, x_split=False):
-    """dw (+)= ; dw is the running gradient buffer [Cout][k*k][Cin]."""
-    if not x_split:
-        prec = _guard_prec(x, prec)
-    if prec and k == 3 and s == 1:
-        return conv_wgrad_group([x], [dy], [dw], k, s, prec, [gmax], x_splits=[x_split])
-    sh = _shape(x.shape, _ld(x), dy.shape[3], _ld(dy), k, s, prec, gmax, x_split=x_split)
-    call("hrseg_conv_wgrad", ptr(x), ptr(dy), ptr(dw), C.byref(sh))
-
-
 def _shape_array(shapes):
     return (ConvShape * len(shapes))(*shapes)
 
 
-def conv_fwd_group(xs, ws, biases, k, s, couts, prec=0, residuals=None, relus=None, stats=False, wpersist=False, x_splits=None):
-    """n independent convolutions (same k, s) in one launch when the library can group them; residuals / relus: the fused
-    epilogue per problem (inference with folded BatchNorm); stats=True: -> (outs, [(partial, rows) or None per problem])"""
+def conv_fwd_group(xs, ws, biases, k, s, couts, prec=0, residuals=None, relus=None, stats=False, wpersist=False, x_splits=None,
+                   outs=None):
+    """n independent convolutions (same k, s) in one launch when the library can group them.  xs NHWC, ws storage
+    [Cout][k*k][Cin] (a channels_last [Cout,Cin,k,k] parameter, or its flat 1-D slot: hence `couts`).  `prec`:
+    _lib.CONV_PRECISION code (all conv functions).  residuals / relus: the fused epilogue per problem (inference with folded
+    BatchNorm); outs: per problem a buffer to write (a channel slice of a wider NHWC tensor is fine) or None = allocated.
+    stats=True: -> (outs, [(partial, rows) or None per problem]): the BatchNorm partial sums of an output where the kernel
+    that ran produces them in its epilogue (hrseg_conv_shape_t.stat_partial), else None"""
     _lib.ensure_scratch(xs[0].device)
     if _lib.deterministic() and any(_guard_prec(x, prec) != prec for i, x in enumerate(xs) if not (x_splits and x_splits[i])):
         prec = _lib.CONV_PRECISION["f32"]        # (one precision per grouped call)
-    outs, shapes, sts = [], [], []
+    outs, shapes, sts = list(outs) if outs is not None else [None] * len(xs), [], []
     for i, (x, co) in enumerate(zip(xs, couts)):
         B, Hi, Wi, Cin = x.shape
-        y = empty_nhwc(B, conv_out_size(Hi, k, s), conv_out_size(Wi, k, s), co, x)
-        outs.append(y)
+        if outs[i] is None:
+            outs[i] = empty_nhwc(B, conv_out_size(Hi, k, s), conv_out_size(Wi, k, s), co, x)
+        y = outs[i]
         sts.append(_stat_buffer(co, x.device) if stats else None)
         shapes.append(_shape(x.shape, _ld(x), co, _ld(y), k, s, prec, residual=residuals[i] if residuals is not None else None,
                              relu=relus[i] if relus is not None else False, stat=sts[i], wpersist=wpersist,
@@ -201,7 +163,7 @@ def conv_fwd_group(xs, ws, biases, k, s, couts, prec=0, residuals=None, relus=No
 
 
 def conv_dgrad_group(dys, wts, x_shapes, k, s, outs, accumulate, prec=0, gmaxs=None, wpersist=False):
-    """outs[i] None -> allocated (accumulate ignored)"""
+    """wts[i] = weight_transpose(w): [Cin][k*k][Cout]; outs[i] None -> allocated (accumulate ignored)"""
     _lib.ensure_scratch(dys[0].device)
     outs, acc, shapes = list(outs), list(accumulate), []
     for i, (dy, xs) in enumerate(zip(dys, x_shapes)):
@@ -216,6 +178,7 @@ def conv_dgrad_group(dys, wts, x_shapes, k, s, outs, accumulate, prec=0, gmaxs=N
 
 
 def conv_wgrad_group(xs, dys, dws, k, s, prec=0, gmaxs=None, x_splits=None):
+    """dws[i] (+)= ; dws[i] is the running gradient buffer [Cout][k*k][Cin]."""
     if _lib.deterministic() and any(_guard_prec(x, prec) != prec for i, x in enumerate(xs) if not (x_splits and x_splits[i])):
         prec = _lib.CONV_PRECISION["f32"]
     gm = gmaxs if gmaxs is not None else [None] * len(xs)
@@ -230,6 +193,23 @@ def conv_wgrad_group(xs, dys, dws, k, s, prec=0, gmaxs=None, x_splits=None):
              ptr(ws), nbytes)
         return
     call("hrseg_conv_wgrad_group", len(xs), _lib.ptr_array(xs), _lib.ptr_array(dys), _lib.ptr_array(dws), shapes)
+
+
+# The single-problem forms: a group of one through the grouped wrappers (there is no second implementation).
+def conv_fwd(x, w, bias, k, s, out=None, cout=None, prec=0, residual=None, relu=False, stats=False, wpersist=False,
+             x_split=False):
+    """-> out, or with stats=True (out, (partial, rows) or None); pass `cout` when w is the flat 1-D parameter slot"""
+    got = conv_fwd_group([x], [w], [bias], k, s, [cout if cout is not None else w.shape[0]], prec, [residual], [relu], stats,
+                         wpersist, [x_split], [out])
+    return (got[0][0], got[1][0]) if stats else got[0]
+
+
+def conv_dgrad(dy, wt, x_shape, k, s, out=None, accumulate=False, prec=0, gmax=None, wpersist=False):
+    return conv_dgrad_group([dy], [wt], [x_shape], k, s, [out], [accumulate], prec, [gmax], wpersist)[0]
+
+
+def conv_wgrad(x, dy, dw, k, s, prec=0, gmax=None, x_split=False):
+    conv_wgrad_group([x], [dy], [dw], k, s, prec, [gmax], [x_split])
 
 
 def weight_transpose(w_store, Cout, taps, Cin, out=None):

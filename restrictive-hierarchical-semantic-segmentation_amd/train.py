@@ -571,7 +571,7 @@ class TapedTrainStep:
     bit-identical to it in deterministic mode (tests/test_tape_gpu.py).
 
     Needs the package's fused loss objects (losses.CrossEntropyLoss + losses.SoftDiceLoss per level) and fixed shapes;
-    `for_batch` of a TapedStepCache re-records per shape."""
+    `taped_step_for` keeps one recording per (model configuration, batch shape)."""
 
     def __init__(self, model, optimizer, lossFuncts, args, class_tree, data, target, epoch_num=1):
         from . import _lib

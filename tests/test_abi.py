@@ -44,7 +44,7 @@ def test_header_symbols_exported_and_prototypes_match():
         assert got == want, f"{name}: ctypes {got} != header {want}"
     for name in list(_lib.PROTOTYPES) + list(_lib.RAW_PROTOTYPES):
         assert name in decls, f"{name} bound in _lib.py but missing from hrseg.h"
-    assert _lib.abi_version() == _lib.ABI_VERSION == 16
+    assert _lib.abi_version() == _lib.ABI_VERSION == 17
     assert not any(n.startswith("hrseg_debug_") for n in decls), "experimental switches do not belong in the public header"
 
 
@@ -53,7 +53,9 @@ def test_invalid_arguments_are_reported_without_a_gpu():
     lib = ctypes.CDLL(_lib.LIB_PATH)
     lib.hrseg_last_error_string.restype = ctypes.c_char_p
     shape = _lib.ConvShape(B=1, Hi=8, Wi=8, Cin=16, ldx=16, Ho=7, Wo=8, Cout=16, ldy=16, ksize=3, stride=1)
-    rc = lib.hrseg_conv_fwd(None, None, None, None, ctypes.byref(shape), None)
+    one = (ctypes.c_void_p * 1)(None)
+    lib.hrseg_conv_fwd_group.argtypes = _lib.PROTOTYPES["hrseg_conv_fwd_group"]
+    rc = lib.hrseg_conv_fwd_group(1, one, one, None, one, (_lib.ConvShape * 1)(shape), None)
     assert rc == -1
     assert b"does not match" in lib.hrseg_last_error_string()
     lib.hrseg_set_scratch.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
@@ -85,6 +87,46 @@ def test_invalid_arguments_are_reported_without_a_gpu():
     lib.hrseg_tune.argtypes = [ctypes.c_char_p, ctypes.c_int]
     assert lib.hrseg_tune(b"igemm_wtm", 0) == 0
     assert lib.hrseg_tune(b"no_such_knob", 1) == -1 and b"unknown key" in lib.hrseg_last_error_string()
+
+
+def test_conv_group_of_one_refusals():
+    """A group of one through the three grouped convolution entry points: every refusal a single problem can earn, by return
+    code and by the text behind the `name:` prefix, before anything is launched (placeholder pointers, never dereferenced)"""
+    from hrseg_amd import _lib
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    lib.hrseg_last_error_string.restype = ctypes.c_char_p
+    for name in ("hrseg_conv_fwd_group", "hrseg_conv_dgrad_group", "hrseg_conv_wgrad_group"):
+        getattr(lib, name).argtypes = _lib.PROTOTYPES[name]
+    P, NULL = (ctypes.c_void_p * 1)(4096), (ctypes.c_void_p * 1)(None)
+
+    def refused(which, null=False, **over):
+        dims = dict(B=1, Hi=8, Wi=8, Cin=16, ldx=16, Ho=8, Wo=8, Cout=16, ldy=16, ksize=3, stride=1)
+        dims.update(over)
+        shapes = (_lib.ConvShape * 1)(_lib.ConvShape(**dims))
+        first = NULL if null else P         # (x resp. dy: the array is there, the problem's pointer is not)
+        if which == "fwd":
+            rc = lib.hrseg_conv_fwd_group(1, first, P, None, P, shapes, None)
+        elif which == "dgrad":
+            rc = lib.hrseg_conv_dgrad_group(1, first, P, P, _lib.int_array([0]), shapes, None)
+        else:
+            rc = lib.hrseg_conv_wgrad_group(1, first, P, P, shapes, None)
+        name, _, text = lib.hrseg_last_error_string().decode().partition(": ")
+        assert name == f"hrseg_conv_{which}_group", "a refusal names the entry point that was called"
+        return rc, text
+
+    mismatch = "output 7x8 does not match input 8x8 k3 s1 (expect 8x8)"
+    for which in ("fwd", "dgrad", "wgrad"):
+        assert refused(which, Ho=7) == (-1, mismatch), which
+        assert refused(which, null=True) == (-1, "null pointer"), which
+        assert refused(which, null=True, Ho=7) == (-1, mismatch), f"{which}: the shape is checked ahead of the pointers"
+        assert refused(which, ldx=18) == (-1, "ld must be a multiple of 4"), which
+    assert refused("fwd", Cout=24, ldy=24) == (-1, "Cout 24 not a multiple of 16")
+    assert refused("fwd", Cin=24, ldx=24) == (-1, "Cin 24 not a multiple of 16")
+    for which in ("dgrad", "wgrad"):
+        assert refused(which, Cin=24, ldx=24) == (-1, "channels (24,16) must be multiples of 16"), which
+    x_split = "x_split is set but this problem does not run the wave-specialised / nine-tap kernels (ask hrseg_conv_x_split_ok first)"
+    assert refused("wgrad", x_split=1) == (-3, x_split)
+    assert refused("wgrad", x_split=1, Ho=7) == (-3, x_split), "the weight gradient refuses x_split ahead of the shape"
 
 
 GROUP_TABLE_ENTRY_POINTS = ["hrseg_compose_fwd", "hrseg_compose_bwd", "hrseg_consistency", "hrseg_consistency_bwd", "hrseg_group_kl",

@@ -110,6 +110,33 @@ def test_conv_into_channel_slice(ops):
     assert float(buf[..., :64].abs().max()) == 0.0
 
 
+@pytest.mark.parametrize("prec", ["auto", "f32"])
+@pytest.mark.parametrize("k,H,W,n", [(3, 20, 24, 1), (3, 20, 24, 2), (1, 7, 9, 2)])
+def test_conv_fwd_group_into_given_outputs(ops, k, H, W, n, prec):
+    """conv_fwd_group(outs=...): every problem writes its channel slice of one wider NHWC buffer (ld = the buffer's width)
+    the bits the same call writes into buffers of its own, and no byte of the buffer outside the slices changes"""
+    from hrseg_amd import _lib
+    C, gap = 48, 8
+    g = torch.Generator().manual_seed(100 * k + n)
+    xs = [torch.randn(1, H, W, C, generator=g).cuda() for _ in range(n)]
+    ws = [(torch.randn(C, k * k, C, generator=g) / (C * k * k) ** 0.5).cuda() for _ in range(n)]
+    bias = [torch.randn(C, generator=g).cuda() for _ in range(n)]
+    code = _lib.CONV_PRECISION[prec]
+    want = ops.conv_fwd_group(xs, ws, bias, k, 1, [C] * n, prec=code)
+    width = gap + n * (C + gap)
+    fill = torch.randint(-2 ** 31, 2 ** 31 - 1, (1, H, W, width), dtype=torch.int32, generator=g).cuda()
+    buf = fill.clone().view(torch.float32)
+    outs = [buf[..., gap + i * (C + gap):gap + i * (C + gap) + C] for i in range(n)]
+    got = ops.conv_fwd_group(xs, ws, bias, k, 1, [C] * n, prec=code, outs=outs)
+    torch.cuda.synchronize()
+    outside = torch.ones(width, dtype=torch.bool, device="cuda")
+    for i in range(n):
+        assert got[i] is outs[i] and ops._ld(got[i]) == width
+        assert torch.equal(got[i], want[i]), i
+        outside[gap + i * (C + gap):gap + i * (C + gap) + C] = False
+    assert torch.equal(buf.view(torch.int32)[..., outside], fill[..., outside])
+
+
 @pytest.mark.parametrize("C,H,W,B,relu,res", [(48, 37, 41, 2, True, True), (64, 20, 20, 3, True, False),
                                               (720, 9, 9, 2, False, False), (96, 31, 17, 2, False, True),
                                               (1024, 5, 5, 2, True, False), (192, 13, 13, 1, True, True)])

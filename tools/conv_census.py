@@ -1,5 +1,6 @@
-"""Which convolution calls does one train step make, and what does each cost?  Records every ops.conv_* call of one
-step of the bench model (shapes only), then times each distinct call in isolation (same arithmetic mode).
+"""Which convolution calls does one train step make, and what does each cost?  Records every grouped ops.conv_* call
+of one step of the bench model (shapes only), then times each distinct call in isolation (same arithmetic mode, plain fp32
+inputs: a call that read a pre-split input in the step is timed on the fp32 form).
     python tools/conv_census.py [--size 620] [--batch 4]"""
 import argparse
 import collections
@@ -28,47 +29,27 @@ T.train_step(model, opt, x, t, loss_fns, ns, tree, [])          # warm-up (alloc
 torch.cuda.synchronize()
 
 calls = collections.Counter()
-orig = {n: getattr(ops, n) for n in ("conv_fwd", "conv_dgrad", "conv_wgrad", "conv_fwd_group", "conv_dgrad_group", "conv_wgrad_group")}
+# every convolution of the engine goes through the three grouped wrappers (the single-problem forms of ops.py are groups of
+# one); the wrappers below note the shapes and hand everything else through untouched
+orig = {n: getattr(ops, n) for n in ("conv_fwd_group", "conv_dgrad_group", "conv_wgrad_group")}
 
 
-def sig(t):
-    return tuple(t.shape)
+def w_fwd_g(xs, ws, biases, k, s, couts, prec=0, **kw):
+    calls[("fwd", tuple(tuple(x.shape) for x in xs), tuple(couts), k, s, prec)] += 1
+    return orig["conv_fwd_group"](xs, ws, biases, k, s, couts, prec=prec, **kw)
 
 
-def w_fwd(x, w, bias, k, s, out=None, cout=None, prec=0):
-    calls[("fwd", (sig(x),), (cout if cout is not None else w.shape[0],), k, s, prec)] += 1
-    return orig["conv_fwd"](x, w, bias, k, s, out=out, cout=cout, prec=prec)
-
-
-def w_dgrad(dy, wt, x_shape, k, s, out=None, accumulate=False, prec=0, gmax=None):
-    calls[("dgrad", (tuple(x_shape),), (dy.shape[3],), k, s, prec)] += 1
-    return orig["conv_dgrad"](dy, wt, x_shape, k, s, out=out, accumulate=accumulate, prec=prec, gmax=gmax)
-
-
-def w_wgrad(x, dy, dw, k, s, prec=0, gmax=None):
-    calls[("wgrad", (sig(x),), (dy.shape[3],), k, s, prec)] += 1
-    return orig["conv_wgrad"](x, dy, dw, k, s, prec=prec, gmax=gmax)
-
-
-def w_fwd_g(xs, ws, biases, k, s, couts, prec=0):
-    calls[("fwd", tuple(sig(x) for x in xs), tuple(couts), k, s, prec)] += 1
-    return orig["conv_fwd_group"](xs, ws, biases, k, s, couts, prec=prec)
-
-
-def w_dgrad_g(dys, wts, x_shapes, k, s, outs, accumulate, prec=0, gmaxs=None):
+def w_dgrad_g(dys, wts, x_shapes, k, s, outs, accumulate, prec=0, **kw):
     calls[("dgrad", tuple(tuple(xs) for xs in x_shapes), tuple(d.shape[3] for d in dys), k, s, prec)] += 1
-    return orig["conv_dgrad_group"](dys, wts, x_shapes, k, s, outs, accumulate, prec=prec, gmaxs=gmaxs)
+    return orig["conv_dgrad_group"](dys, wts, x_shapes, k, s, outs, accumulate, prec=prec, **kw)
 
 
-def w_wgrad_g(xs, dys, dws, k, s, prec=0, gmaxs=None):
-    if len(xs) > 1 or not (prec and k == 3 and s == 1):
-        calls[("wgrad", tuple(sig(x) for x in xs), tuple(d.shape[3] for d in dys), k, s, prec)] += 1
-    return orig["conv_wgrad_group"](xs, dys, dws, k, s, prec=prec, gmaxs=gmaxs)
+def w_wgrad_g(xs, dys, dws, k, s, prec=0, **kw):
+    calls[("wgrad", tuple(tuple(x.shape) for x in xs), tuple(d.shape[3] for d in dys), k, s, prec)] += 1
+    return orig["conv_wgrad_group"](xs, dys, dws, k, s, prec=prec, **kw)
 
 
-ops.conv_fwd, ops.conv_dgrad, ops.conv_wgrad = w_fwd, w_dgrad, w_wgrad
 ops.conv_fwd_group, ops.conv_dgrad_group, ops.conv_wgrad_group = w_fwd_g, w_dgrad_g, w_wgrad_g
-import hrseg_amd.engine as E
 T.train_step(model, opt, x, t, loss_fns, ns, tree, [])
 torch.cuda.synchronize()
 for n, f in orig.items():
@@ -97,18 +78,16 @@ for (kind, xshapes, couts, k, s, prec), cnt in calls.items():
     dys = [torch.randn_like(y) for y in ys]
     gms = [d.abs().max().reshape(1).repeat(64) for d in dys]
     if kind == "fwd":
-        fn = (lambda: ops.conv_fwd(xs[0], ws[0], None, k, s, prec=prec)) if n == 1 else (lambda: ops.conv_fwd_group(xs, ws, [None] * n, k, s, list(couts), prec=prec))
+        fn = lambda: ops.conv_fwd_group(xs, ws, [None] * n, k, s, list(couts), prec=prec)
     elif kind == "dgrad":
         wts = [ops.weight_transpose(w_, co, k * k, sh[3]) for w_, co, sh in zip(ws, couts, xshapes)]
-        fn = (lambda: ops.conv_dgrad(dys[0], wts[0], xshapes[0], k, s, prec=prec, gmax=gms[0])) if n == 1 else (
-            lambda: ops.conv_dgrad_group(dys, wts, list(xshapes), k, s, [None] * n, [False] * n, prec=prec, gmaxs=gms))
+        fn = lambda: ops.conv_dgrad_group(dys, wts, list(xshapes), k, s, [None] * n, [False] * n, prec=prec, gmaxs=gms)
     else:
         dws = [torch.zeros_like(w_) for w_ in ws]
-        fn = (lambda: ops.conv_wgrad(xs[0], dys[0], dws[0], k, s, prec=prec, gmax=gms[0])) if n == 1 else (
-            lambda: ops.conv_wgrad_group(xs, dys, dws, k, s, prec=prec, gmaxs=gms))
+        fn = lambda: ops.conv_wgrad_group(xs, dys, dws, k, s, prec=prec, gmaxs=gms)
     try:
         t_us = timeit(fn)
-    except Exception as e:          # a shape the single-call path does not take
+    except Exception:               # a shape the library refuses in isolation
         t_us = float("nan")
     rows.append((cnt * t_us, kind, cnt, t_us, fl, xshapes, couts, k, s))
     del xs, ws, ys, dys

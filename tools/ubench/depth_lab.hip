@@ -176,8 +176,8 @@ static void shape(int B, int H, int C) {
   hipMalloc(&x, nx * 4 + 4096); hipMalloc(&w, nw * 4 + 4096); hipMalloc(&y, nx * 4); hipMalloc(&y2, nx * 4);
   hipMemcpy(x, hx.data(), nx * 4, hipMemcpyHostToDevice); hipMemcpy(w, hw.data(), nw * 4, hipMemcpyHostToDevice);
   const double flop = 2.0 * B * H * H * C * 9.0 * C;
-  for (int rep = 0; rep < 3; ++rep) hrseg_conv_fwd(x, w, nullptr, y, &s, nullptr);
-  hipEventRecord(e0); for (int rep = 0; rep < 20; ++rep) hrseg_conv_fwd(x, w, nullptr, y, &s, nullptr); hipEventRecord(e1); hipEventSynchronize(e1);
+  for (int rep = 0; rep < 3; ++rep) hrseg_conv_fwd_group(1, &x, &w, nullptr, &y, &s, nullptr);
+  hipEventRecord(e0); for (int rep = 0; rep < 20; ++rep) hrseg_conv_fwd_group(1, &x, &w, nullptr, &y, &s, nullptr); hipEventRecord(e1); hipEventSynchronize(e1);
   float ms; hipEventElapsedTime(&ms, e0, e1);
   printf("shape B=%d %dx%d C=%d: production %.1f us %.1f TF\n", B, H, H, C, ms * 50, flop / (ms * 50e-6) * 1e-12);
   std::vector<float> ref(nx); hipMemcpy(ref.data(), y, nx * 4, hipMemcpyDeviceToHost);

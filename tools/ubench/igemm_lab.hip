@@ -120,8 +120,8 @@ int main() {
   const int nblk = ceil_div(a.M, 128);
   hipMalloc(&prof, (size_t)nblk * 4 * 8 * 8);
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-  for (int rep = 0; rep < 3; ++rep) hrseg_conv_fwd(x, w, nullptr, y, &s, nullptr);
-  hipEventRecord(e0); for (int rep = 0; rep < 10; ++rep) hrseg_conv_fwd(x, w, nullptr, y, &s, nullptr); hipEventRecord(e1); hipEventSynchronize(e1);
+  for (int rep = 0; rep < 3; ++rep) hrseg_conv_fwd_group(1, &x, &w, nullptr, &y, &s, nullptr);
+  hipEventRecord(e0); for (int rep = 0; rep < 10; ++rep) hrseg_conv_fwd_group(1, &x, &w, nullptr, &y, &s, nullptr); hipEventRecord(e1); hipEventSynchronize(e1);
   float ms; hipEventElapsedTime(&ms, e0, e1); printf("production kernel: %.1f us\n", ms * 100);
   for (int rep = 0; rep < 3; ++rep) hipLaunchKernelGGL((igemm_stamped<2, 3>), dim3(nblk), dim3(256), 0, 0, a, prof);
   hipEventRecord(e0); for (int rep = 0; rep < 10; ++rep) hipLaunchKernelGGL((igemm_stamped<2, 3>), dim3(nblk), dim3(256), 0, 0, a, prof); hipEventRecord(e1); hipEventSynchronize(e1);
