@@ -29,6 +29,28 @@
  *   - all launches go to `stream` (a hipStream_t); no call synchronises.
  *   - return 0 on success, a negative hrseg_status otherwise;
  *     hrseg_last_error_string() describes the last failure on this thread.
+ *   - non-finite values on the activation path stay loud.  Every output element
+ *     of a pointwise or reducing kernel has the class (finite, +Inf, -Inf, NaN)
+ *     that the same operation gives in torch: ReLU -- on its own, behind a
+ *     BatchNorm, a residual add, a resize, a fuse sum or in a convolution
+ *     epilogue -- keeps NaN and +Inf and maps -Inf to 0; a 2x2 max-pool window
+ *     that holds a NaN gives NaN; the clamp of the grouped KL keeps NaN; softmax
+ *     and log-sum-exp give NaN for a NaN or +Inf logit.  One NaN in a training
+ *     BatchNorm's input makes the whole channel and its running statistics NaN.
+ *     A resize gives a non-finite output wherever the poisoned input has a
+ *     non-zero interpolation weight (a zero-weight tap may or may not).  The
+ *     max|dy| recorders (hrseg_absmax, hrseg_bn_bwd_t.dy_absmax, hrseg_head_bn_t.
+ *     dy_absmax, hrseg_bilinear_bwd_multi) report NaN as +Inf.  No forward kernel
+ *     turns a non-finite value into a finite one except where torch does
+ *     (relu(-Inf) = 0).  One departure from torch, in the backward: the ReLU
+ *     mask is [z > 0], so the incoming gradient of an element whose activation
+ *     is NaN is zeroed (hrseg_relu_bwd, hrseg_bn_bwd_group, the relu_mask byte,
+ *     the fused head backward), where torch's threshold_backward passes it.  The
+ *     activation itself is NaN and loud, and a NaN in a training BatchNorm's
+ *     channel makes that channel's backward sums and dy NaN regardless.  So a
+ *     poisoned activation reaches the loss and the flat gradient, where
+ *     FusedAdamW(skip_nonfinite) voids the step.
+ *     (tests/nonfinite_ref.py states this per operation.)
  */
 #ifndef HRSEG_H
 #define HRSEG_H

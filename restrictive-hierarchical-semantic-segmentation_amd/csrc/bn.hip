@@ -243,8 +243,7 @@ __global__ __launch_bounds__(256) void bn_apply_group_kernel(BnFwdG g) {
       // one byte per (pixel, channel quad): bit j = "channel 4q+j passed the ReLU".  With a residual the backward cannot
       // recompute the mask from y alone; reading this byte instead of z saves it 4 B per element, twice
       if (p.relu_mask) p.relu_mask[pix * L.Q + L.cq] = (unsigned char)((v[0] > 0.f) | ((v[1] > 0.f) << 1) | ((v[2] > 0.f) << 2) | ((v[3] > 0.f) << 3));
-#pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
+      v = relu_nan(v);       // (a NaN element's mask bit is 0: its gradient is masked, the value itself stays loud)
     }
     // z_split: the tensor's only readers are fp16x2 convolutions that take their pixel operand pre-split (hrseg_conv_shape_t.
     // x_split): the granule goes out as {hi01, hi23, lo01, lo23} -- the same 16 bytes per 4 channels, the split done once here
@@ -333,7 +332,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_group_kernel(BnBwdG g, int e
     const f32x4 dyv = scale * (gg - mg - xh * mgx);
     st4(p.dy + pix * p.lddy + 4 * L.cq, dyv);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) amax = fmaxf(amax, fabsf(dyv[j]));
+    for (int j = 0; j < 4; ++j) amax = fmaxf(amax, abs_nan_inf(dyv[j]));
     if (p.dres) {
       float* d = p.dres + pix * p.lddres + 4 * L.cq;
       st4(d, p.dres_accumulate ? ld4(d) + gg : gg);
@@ -446,9 +445,7 @@ __global__ __launch_bounds__(256) void head_bn_bwd_reduce_kernel(hrseg_head_bn_t
           }
         }
         const f32x4 zc = bn_affine(yv[u], sc, sh);
-        f32x4 fv;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) fv[j] = fmaxf(zc[j], 0.f);
+        const f32x4 fv = relu_nan(zc);
         // head_bwd_kernel's `one`, with f recomputed
         const f32x4 fm = fv * gam + bet;
         f32x4 uu = {0.f, 0.f, 0.f, 0.f};
@@ -660,9 +657,7 @@ __global__ __launch_bounds__(512) void head_bn_bwd_reduce_ring_kernel(hrseg_head
         for (int c = 4; c < CO; ++c) g[c] = g1[c - 4];
       }
       const f32x4 zc = bn_affine(yv, sc, sh);
-      f32x4 fv;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) fv[j] = fmaxf(zc[j], 0.f);
+      const f32x4 fv = relu_nan(zc);
       const f32x4 fm = fv * gam + bet;
       f32x4 uu = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -789,7 +784,7 @@ __global__ __launch_bounds__(256) void head_bn_bwd_apply_kernel(hrseg_head_bn_t 
           const f32x4 dyv = scale * (gg - mg - xh * mgx);
           st4(a.dy + pix * a.lddy + 4 * L.cq, dyv);
 #pragma unroll
-          for (int j = 0; j < 4; ++j) amax = fmaxf(amax, fabsf(dyv[j]));
+          for (int j = 0; j < 4; ++j) amax = fmaxf(amax, abs_nan_inf(dyv[j]));
         }
       }
     }

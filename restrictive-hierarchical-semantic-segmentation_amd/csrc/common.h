@@ -56,6 +56,20 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   return v;
 }
 
+// The library's ReLU.  fmaxf(v, 0.f) returns the operand that is not NaN, so it turns NaN into 0 and a poisoned activation
+// goes quiet (hrseg.h, 'non-finite values on the activation path').  This spelling keeps NaN (the comparison is false) and
+// gives fmaxf's bits for every other input: +0.0 for -0.0 and for all negatives, -Inf included; +Inf stays +Inf.
+__device__ __forceinline__ float relu_nan(float v) { return v <= 0.f ? 0.f : v; }
+__device__ __forceinline__ f32x4 relu_nan(f32x4 v) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) v[j] = relu_nan(v[j]);
+  return v;
+}
+// max that returns NaN when either operand is NaN (fmaxf drops it); for non-NaN operands fmaxf's value
+__device__ __forceinline__ float max_nan(float a, float b) { return (a != a || b != b) ? a + b : fmaxf(a, b); }
+// |v| for a running maximum that a fp16x2 guard reads: NaN counts as +Inf (as absmax_kernel), since fmaxf would drop it
+__device__ __forceinline__ float abs_nan_inf(float v) { return (v != v) ? __builtin_inff() : fabsf(v); }
+
 // BatchNorm's y*scale + shift with ONE rounding per element: the forward pass, the backward pass's recomputed ReLU mask and
 // the level heads that read the un-normalised tensor (hrseg_head_bn_*) must evaluate the identical expression
 __device__ __forceinline__ f32x4 bn_affine(f32x4 y, f32x4 sc, f32x4 sh) {

@@ -287,7 +287,8 @@ __global__ __launch_bounds__(256) void group_kl_kernel(const float* __restrict__
         const float lg = logf((float)gs);
         float kl = 0.f;
         for (int c = 0; c < gs; ++c) {
-          const float q = fmaxf(v[c] / den, 1e-8f);
+          const float qq = v[c] / den;
+          const float q = qq < 1e-8f ? 1e-8f : qq;       // clamp_min that keeps NaN, as torch's (fmaxf would answer 1e-8)
           kl += q * (logf(q) + lg);
         }
         acc[gi] += kl;

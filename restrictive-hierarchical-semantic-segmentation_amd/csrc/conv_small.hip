@@ -48,7 +48,7 @@ __global__ __launch_bounds__(256) void conv_small_cin_fwd_kernel(const float* __
     if (co < Cout) {
       float v = acc[j] + (bias ? bias[co] : 0.f);
       if (res) v += res[(size_t)m * ldr + co];
-      yp[j] = relu ? fmaxf(v, 0.f) : v;
+      yp[j] = relu ? relu_nan(v) : v;
     }
   }
 }
@@ -94,10 +94,7 @@ __global__ __launch_bounds__(256) void conv_cin3_k3_fwd_kernel(const float* __re
     }
     f32x4 v = acc + bv;
     if (res) v += *reinterpret_cast<const f32x4*>(res + (size_t)m * ldr + co);
-    if (relu) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
-    }
+    if (relu) v = relu_nan(v);
     *reinterpret_cast<f32x4*>(y + (size_t)m * ldy + co) = v;
   }
 }

@@ -290,10 +290,7 @@ __device__ __forceinline__ void igemm_spw_body(const IgemmArgs& p, unsigned char
       } else {
         if (p.accumulate) v += *reinterpret_cast<const f32x4*>(yrow + ch);
         if (p.res) v += *reinterpret_cast<const f32x4*>(p.res + pix * p.ldr + ch);
-        if (p.relu) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-        }
+        if (p.relu) v = relu_nan(v);
         *reinterpret_cast<f32x4*>(yrow + ch) = v;
       }
     }

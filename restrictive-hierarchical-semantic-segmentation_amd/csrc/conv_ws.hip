@@ -393,10 +393,7 @@ __device__ __forceinline__ void igemm_patch_ws_body(const IgemmArgs& p, unsigned
 #pragma unroll
         for (int n = 0; n < WTN; ++n) {
           f32x4 v = PLAIN ? acc[n][m] * oscale : acc[n][m] * oscale + add[m][n];
-          if (!PLAIN && e_relu) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-          }
+          if (!PLAIN && e_relu) v = relu_nan(v);
           buf_store4(ry, off[m], 64 * n, v);
         }
         // A 16-byte store reads its data registers over several cycles after it issues, and the compiler lets a packed

@@ -18,7 +18,7 @@ __global__ __launch_bounds__(256) void maxpool2_fwd_kernel(const float* __restri
     f32x4 m = ld4(p);
     const f32x4 v1 = ld4(p + ldx), v2 = ld4(p + (size_t)Wi * ldx), v3 = ld4(p + (size_t)Wi * ldx + ldx);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) m[j] = fmaxf(fmaxf(m[j], v1[j]), fmaxf(v2[j], v3[j]));
+    for (int j = 0; j < 4; ++j) m[j] = max_nan(max_nan(m[j], v1[j]), max_nan(v2[j], v3[j]));   // NaN in the window -> NaN, as torch
     st4(y + pix * ldy + 4 * L.cq, m);
   }
 }
@@ -113,10 +113,7 @@ __global__ __launch_bounds__(256) void bilinear_fwd_kernel(const float* __restri
     }
     float* o = out + pix * ldout + 4 * L.cq;
     if (acc) v += ld4(o);
-    if (relu) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
-    }
+    if (relu) v = relu_nan(v);
     st4(o, v);
   }
 }
@@ -159,10 +156,7 @@ __global__ __launch_bounds__(256) void fuse_sum_kernel(FuseSumArgs a) {
           v += ly0 * (lx0 * v00 + lx1 * v01) + ly1 * (lx0 * v10 + lx1 * v11);
         }
     }
-    if (a.relu) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
-    }
+    if (a.relu) v = relu_nan(v);
     st4(a.out + pix * a.ldo + 4 * L.cq, v);
   }
 }
@@ -454,7 +448,7 @@ __global__ __launch_bounds__(1024) void bilinear_bwd_multi_kernel(BilinearBwdMul
   if (valid && rsi == 0) {
     st4(a.din[t] + (((size_t)b * Hi + iy) * Wi + ix) * a.lddin[t] + 4 * cq, s);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) amax = fmaxf(amax, (s[j] != s[j]) ? __builtin_inff() : fabsf(s[j]));
+    for (int j = 0; j < 4; ++j) amax = fmaxf(amax, abs_nan_inf(s[j]));
   }
   if (a.absmax) {
 #pragma unroll
@@ -493,10 +487,7 @@ __global__ __launch_bounds__(256) void add_kernel(const float* __restrict__ a, i
   if (!L.active) return;
   FOR_PIXELS(pix, L, npix) {
     f32x4 v = ld4(a + pix * lda + 4 * L.cq) + ld4(b + pix * ldb + 4 * L.cq);
-    if (relu) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
-    }
+    if (relu) v = relu_nan(v);
     st4(out + pix * ldo + 4 * L.cq, v);
   }
 }
@@ -534,7 +525,7 @@ __global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ x
     FOR_PIXELS(pix, L, npix) {
       const f32x4 v = ld4(x + pix * ldx + 4 * L.cq);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) amax = fmaxf(amax, (v[j] != v[j]) ? __builtin_inff() : fabsf(v[j]));
+      for (int j = 0; j < 4; ++j) amax = fmaxf(amax, abs_nan_inf(v[j]));
     }
   }
   __shared__ float wmax[4];

@@ -175,9 +175,7 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__
       if (BN) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-          v[j] = bn_affine(v[j], bsc[j], bsh[j]);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[j][e] = fmaxf(v[j][e], 0.f);
+          v[j] = relu_nan(bn_affine(v[j], bsc[j], bsh[j]));
         }
       }
       float acc[CO];
@@ -208,9 +206,7 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__
     for (int q = sub; q < Q; q += LP) {
       f32x4 v = *reinterpret_cast<const f32x4*>(row + 4 * q);
       if (BN) {
-        v = bn_affine(v, *reinterpret_cast<const f32x4*>(coef + 2 * F + 4 * q), *reinterpret_cast<const f32x4*>(coef + 3 * F + 4 * q));
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+        v = relu_nan(bn_affine(v, *reinterpret_cast<const f32x4*>(coef + 2 * F + 4 * q), *reinterpret_cast<const f32x4*>(coef + 3 * F + 4 * q)));
       }
 #pragma unroll
       for (int c = 0; c < CO; ++c) {

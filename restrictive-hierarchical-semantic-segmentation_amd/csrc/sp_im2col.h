@@ -242,10 +242,7 @@ __device__ __forceinline__ void igemm_sp_body(const IgemmArgs& p, unsigned char*
 #pragma unroll
         for (int e = 0; e < 4; ++e) atomicAdd(yrow + ch + e, v[e]);
       } else {
-        if (p.relu) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-        }
+        if (p.relu) v = relu_nan(v);
         *reinterpret_cast<f32x4*>(yrow + ch) = v;
       }
     }

@@ -236,10 +236,7 @@ __device__ __forceinline__ void igemm_patch_sp_body(const IgemmArgs& p, unsigned
         f32x4 v = acc[n][m];
         if (NS == 4) v *= oscale;
         v += add[m][n];
-        if (p.relu) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-        }
+        if (p.relu) v = relu_nan(v);
         *reinterpret_cast<f32x4*>(yrow + q.n0 + 16 * n + 4 * g) = v;
       }
     }

@@ -244,7 +244,10 @@ def test_bn_z_split_out_of_range_values_follow_the_model(relu):
     fin = torch.isfinite(z)
     assert bool(((z.abs() > 65504) & (z.abs() < 1.3e5) & fin).float().mean() > 0.05)
     assert bool((z[fin].abs() > 1.4e5).any()) and bool(torch.isinf(z).any())
-    assert bool(torch.isnan(z).any()) != relu            # (fmaxf(NaN, 0) = 0: ReLU removes the NaN channel, and -Inf)
+    # the ReLU keeps NaN (include/hrseg.h, non-finite values stay loud): the NaN channel stays NaN with it and without it; of the
+    # infinite channel it removes -Inf only, as torch's does
+    assert bool(torch.isnan(z[..., 5]).all()) and bool((z[..., 3] == float("inf")).any())
+    assert bool((z[..., 3] == float("-inf")).any()) != relu and bool((z[..., 3] == 0).any()) == relu
 
 
 @pytest.mark.parametrize("C", [48, 64])
