@@ -340,7 +340,9 @@ int hrseg_head_mix(float* y, int ldy, const float* bias, int n_low, const float*
                    int nchunks, hrseg_stream_t stream);
 /* its backward: the transpose of the bilinear resize of dout (B x Hout x Wout x C) onto n (1..3) targets din[j]
  * (B x Hi[j] x Wi[j] x C, overwritten) in one launch; each target equals hrseg_bilinear_bwd of the same dout up to the
- * order of the additions.  No atomics: the same bits every run.  absmax (may be NULL): [n][64] floats zeroed by the
+ * order of the additions and of the two weight products (large gradients stream dout through LDS and add
+ * wy * (sum wx * g), csrc/elem.hip).  No float atomics: the same bits every run, and for every setting of hrseg_tune
+ * bwd_multi_slab / bwd_multi_bands that keeps the shape on one body.  absmax (may be NULL): [n][64] floats zeroed by the
  * caller, row j receives max|din[j]| as hrseg_absmax leaves it (the FP16X2 gradient scale of the convolutions that
  * follow).  HOST arrays. */
 int hrseg_bilinear_bwd_multi(const float* dout, int lddout, int B, int Hout, int Wout, int C, int n,

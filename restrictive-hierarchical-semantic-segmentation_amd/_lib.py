@@ -240,6 +240,15 @@ def deterministic() -> bool:
     return _deterministic
 
 
+_fuse_bwd_multi = True
+
+
+def fuse_bwd_multi() -> bool:
+    """the hrseg_tune knob of that name (default on): Engine.fuse_sum's backward transposes the gradient onto all its
+    first-reader low-resolution terms in one hrseg_bilinear_bwd_multi launch"""
+    return _fuse_bwd_multi
+
+
 _tune_generation = 0
 
 
@@ -251,13 +260,15 @@ def tune_generation() -> int:
 
 def tune(**kv):
     """tile-plan overrides of the library (hrseg_tune; 0 = automatic), e.g. tune(igemm_wtm=2, igemm_kc=1)"""
-    global _deterministic, _tune_generation
+    global _deterministic, _fuse_bwd_multi, _tune_generation
     _tune_generation += 1
     for k, v in kv.items():
         if _lib.hrseg_tune(k.encode(), int(v)) != 0:
             raise RuntimeError(f"hrseg_tune({k}) failed: {last_error()}")
         if k == "deterministic":
             _deterministic = bool(v)
+        if k == "fuse_bwd_multi":
+            _fuse_bwd_multi = bool(v)
 
 
 def set_conv_tune(wtm=0, kc=0, db=0, ksplit=0):

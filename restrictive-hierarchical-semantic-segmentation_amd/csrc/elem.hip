@@ -337,16 +337,29 @@ __global__ __launch_bounds__(256) void bilinear_bwd_kernel(const float* __restri
   }
 }
 
-// The same transpose onto up to three targets in ONE launch (hrseg_bilinear_bwd_multi: the backward of head_mix_kernel, all
-// C channels of dout onto every target).  Gather form, bilinear_bwd_kernel's weights, (wy * wx) * g products and row order.
-// Threads = `qs` channel quads (one of C / 4 / qs channel slabs) x `lanes`; a block works on one target: rs[t] lanes split
-// the footprint rows of a pixel and are added in lane order through LDS, lanes / rs[t] pixels per block.  Every element of
-// dout is read four times per target; what that costs is decided by where the re-reads are served from.  The work list is
-// ordered by (channel slab, image, band of output rows) -- the blocks of all targets whose pixels centre on a band follow each
-// other -- and dealt to the XCDs in contiguous pieces (xcd_remap): the rows of dout an XCD's blocks work on at one time are a
-// few MB of one slab and dout comes from HBM about once (measured: the re-reads still miss L2 and are served by the Infinity
-// Cache at about 8 TB/s, profiles/README.md "Shared head at branch resolution").  absmax (optional, [n][64], zeroed by the
-// caller): max|din| per target as hrseg_absmax leaves it (an integer maximum: order-independent).
+// The same transpose onto up to three targets in ONE launch (hrseg_bilinear_bwd_multi: the backward of head_mix_kernel and of
+// the HRNet fuse layers, all C channels of dout onto every target).  Two bodies; hrseg_bilinear_bwd_multi holds the rule.
+// absmax (optional, [n][64], zeroed by the caller): max|din| per target as hrseg_absmax leaves it (an integer maximum:
+// order-independent).
+//
+// GATHER body (bilinear_bwd_multi_kernel): bilinear_bwd_kernel's weights, (wy * wx) * g products and row order.  Threads =
+// `qs` channel quads (one of C / 4 / qs channel slabs) x `lanes`; a block works on one target: rs[t] lanes split the footprint
+// rows of a pixel and are added in lane order through LDS, lanes / rs[t] pixels per block.  Every element of dout is loaded
+// four times per target, and no block order makes the re-reads hit L2 (profiles/README.md "Shared head at branch resolution":
+// they are served by the Infinity Cache at about 8 TB/s).  Kept for the shapes the streaming body refuses.
+//
+// STREAMING body (bilinear_bwd_stream_kernel, below it): dout comes from global memory about once and the reuse happens on
+// chip.  A block owns (channel slab, image, band); a band is the same range of target rows per target as in the gather body.
+// The block streams the rows of dout that carry weight for its target rows, in ascending oy, through a two-slot ring in LDS
+// (row oy + 1 is in flight in registers while row oy is consumed); neighbouring bands re-read the halo rows.  A thread owns up
+// to BWD_STREAM_ITEMS fixed items (target, ix, channel quad) and keeps two live target rows of each in registers:
+//   column pass  c = sum_k wx[k] * g[xa + k], ascending k, from the LDS row (xa, count and wx[] tabulated once per block,
+//                zero weights at the edges trimmed, as in the gather body);
+//   row pass     acc[y0] += w0 * c, acc[y0 + 1] += w1 * c (y0, w0, w1 tabulated per (target, oy) once per block; a weight
+//                of exactly 0 is never multiplied: a NaN of dout stays inside its 2 x 2 support);
+//   a target row is stored (and folded into absmax) once oy has passed its last contributing row.
+// The sum of a target element is wy * (sum wx * g) over ascending oy whatever the band count, the slab width and the grid:
+// the output bits do not depend on either knob.  No float atomics.
 struct BilinearBwdMultiArgs {
   const float* dout; int lddout;
   int B, Hout, Wout, C, n, align, lanes, nbands, qs;
@@ -455,6 +468,209 @@ __global__ __launch_bounds__(1024) void bilinear_bwd_multi_kernel(BilinearBwdMul
     for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
     if ((threadIdx.x & 63) == 0 && amax > 0.f)
       atomicMax(reinterpret_cast<unsigned*>(a.absmax) + t * 64 + (bid & 63), __float_as_uint(amax));
+  }
+}
+
+#define BWD_STREAM_ITEMS 4       // (target, ix, channel quad) items and 16-byte row loads per thread, at most
+struct BilinearBwdStreamArgs {
+  const float* dout; int lddout;
+  int B, H, W, C, n, align, nbands, SQ;      // SQ: channel quads of a slab (the last slab may hold fewer)
+  float* din[3]; int lddin[3]; int Hi[3], Wi[3];
+  float sh[3], sw[3];
+  int nx[3];             // most columns of a footprint (row length of the target's wx table)
+  int col0[4];           // running sum of Wi: first entry of the target in the column tables
+  int wx0[3];            // first float of the target's wx table
+  float* absmax;
+};
+// dynamic LDS: ring [2][W * SQ] f32x4 | row table y0 [n * H] int, w0 [n * H], w1 [n * H] | column table (xa, count) [col0[n]]
+// | wx tables
+__global__ __launch_bounds__(1024) void bilinear_bwd_stream_kernel(BilinearBwdStreamArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  __shared__ int range[2];                 // first and last row of dout with weight on the band
+  __shared__ unsigned bmax[3];
+  __shared__ int band_r0[3], band_r1[3];
+  constexpr int NI = BWD_STREAM_ITEMS;
+  const int T = blockDim.x, tid = threadIdx.x;
+  const int H = a.H, W = a.W, n = a.n, ncol = a.col0[n];
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);
+  // the slabs of one (image, band) follow each other on one XCD (xcd_remap) and stream the same rows at about the same time:
+  // a slab's pieces of a pixel (192 bytes at a 2880-byte stride) share their first and last 128-byte line with the
+  // neighbouring slabs, and whichever block comes second finds the line in L2 instead of fetching it again
+  const int nslab = ((a.C >> 2) + a.SQ - 1) / a.SQ;
+  const int slab = bid % nslab, ib = bid / nslab;
+  const int band = ib % a.nbands, b = ib / a.nbands;
+  const int q0 = slab * a.SQ, sq = min(a.SQ, (a.C >> 2) - q0);
+  const int rq = W * a.SQ;                 // quads of a ring slot
+  f32x4* const ring = reinterpret_cast<f32x4*>(smem);
+  int* const rowy = reinterpret_cast<int*>(smem + (size_t)8 * rq);
+  float* const roww0 = reinterpret_cast<float*>(rowy + n * H);
+  float* const roww1 = roww0 + n * H;
+  int* const colm = reinterpret_cast<int*>(roww1 + n * H);
+  float* const wxtab = reinterpret_cast<float*>(colm + 2 * ncol);
+  if (tid == 0) { range[0] = H; range[1] = -1; }
+  if (tid < 3) {
+    bmax[tid] = 0u;
+    if (tid < n) {         // target rows of this band: [ceil(band * Hi / nbands), ceil((band + 1) * Hi / nbands))
+      band_r0[tid] = (int)(((long)band * a.Hi[tid] + a.nbands - 1) / a.nbands);
+      band_r1[tid] = (int)(((long)(band + 1) * a.Hi[tid] + a.nbands - 1) / a.nbands);
+    }
+  }
+  __syncthreads();
+  // row table: dout row oy feeds target rows y0 (weight w0) and y0 + 1 (w1); both taps on one row add up as in the gather
+  // bodies, and a weight onto a row of another band is entered as 0: the row pass skips it
+  for (int e = tid; e < n * H; e += T) {
+    const int t = e / H, oy = e - t * H;
+    int y0, y1;
+    float ly0, ly1;
+    src_index(oy, a.sh[t], a.Hi[t], a.align, y0, y1, ly0, ly1);
+    float w0 = (y1 == y0) ? ly0 + ly1 : ly0, w1 = (y1 == y0) ? 0.f : ly1;
+    if (y0 < band_r0[t] || y0 >= band_r1[t]) w0 = 0.f;
+    if (y0 + 1 < band_r0[t] || y0 + 1 >= band_r1[t]) w1 = 0.f;
+    rowy[e] = y0; roww0[e] = w0; roww1[e] = w1;
+    if (w0 != 0.f || w1 != 0.f) {
+      atomicMin(&range[0], oy);
+      atomicMax(&range[1], oy);
+    }
+  }
+  // column table: first live column, live columns and wx[] of every (target, ix), the zero weights at the edges trimmed
+  for (int e = tid; e < ncol; e += T) {
+    int t = 0;
+    while (t + 1 < n && e >= a.col0[t + 1]) ++t;
+    const int ix = e - a.col0[t], Wi = a.Wi[t], align = a.align;
+    const float sw = a.sw[t], isw = sw > 0.f ? 1.f / sw : 0.f;
+    int ox_lo = 0, ox_hi = W - 1;
+    if (sw > 0.f) {
+      ox_lo = max(0, (int)floorf(((float)ix - 1.f + (align ? 0.f : 0.5f)) * isw - (align ? 0.f : 0.5f)) - 1);
+      ox_hi = min(W - 1, (int)ceilf(((float)ix + 1.f + (align ? 0.f : 0.5f)) * isw - (align ? 0.f : 0.5f)) + 1);
+    }
+    float* wxt = wxtab + a.wx0[t] + ix * a.nx[t];
+    int xa = -1, nx = 0;
+    for (int ox = ox_lo; ox <= ox_hi; ++ox) {
+      int x0, x1;
+      float lx0, lx1;
+      src_index(ox, sw, Wi, align, x0, x1, lx0, lx1);
+      const float wx = (x0 == ix ? lx0 : 0.f) + (x1 == ix ? lx1 : 0.f);
+      if (xa < 0 && wx != 0.f) xa = ox;
+      if (xa >= 0 && ox - xa < a.nx[t]) {
+        wxt[ox - xa] = wx;
+        if (wx != 0.f) nx = ox - xa + 1;
+      }
+    }
+    colm[2 * e] = xa < 0 ? 0 : xa;
+    colm[2 * e + 1] = nx;
+  }
+  __syncthreads();
+  // this thread's items (item e = tid + i * T over (column entry, quad of the slab)) and row loads (quad j = tid + l * T of a row)
+  int it_t[NI], it_nx[NI], it_g[NI], it_w[NI], it_out[NI];       // it_out: the item's element of target row 0, from din[t]
+  f32x4 acc0[NI], acc1[NI];
+  int ld_off[NI];
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    const int e = tid + i * T;
+    const bool valid = e < ncol * sq;
+    const int col = valid ? e / sq : 0, q = valid ? e - col * sq : 0;
+    int t = 0;
+    while (t + 1 < n && col >= a.col0[t + 1]) ++t;
+    const int ix = col - a.col0[t];
+    it_t[i] = valid ? t : -1;
+    it_nx[i] = valid ? colm[2 * col + 1] : 0;
+    it_g[i] = colm[2 * col] * sq + q;
+    it_w[i] = a.wx0[t] + ix * a.nx[t];
+    it_out[i] = (b * a.Hi[t] * a.Wi[t] + ix) * a.lddin[t] + 4 * (q0 + q);
+    acc0[i] = acc1[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int j = min(tid + i * T, W * sq - 1);        // (past the row: the last quad again, no branch around the load)
+    const int x = j / sq;
+    ld_off[i] = x * a.lddout + 4 * (q0 + j - x * sq);
+  }
+  // The live target rows are the same in every thread: acc0 holds row cur[t] of the item's target, acc1 row cur[t] + 1.
+  // rotate(t): row cur[t] is complete -- store it if it is the band's -- and the next row moves up.
+  int cur[3];
+#pragma unroll
+  for (int t = 0; t < 3; ++t) cur[t] = t < n ? __builtin_amdgcn_readfirstlane(band_r0[t]) - 1 : 0;
+  auto rotate = [&](int t) {
+    const bool mine = cur[t] >= band_r0[t] && cur[t] < band_r1[t];
+    float* const row = a.din[t] + (long)cur[t] * a.Wi[t] * a.lddin[t];
+    float m = 0.f;
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+      if (it_t[i] != t) continue;
+      if (mine) {
+        st4(row + it_out[i], acc0[i]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) m = fmaxf(m, abs_nan_inf(acc0[i][j]));
+      }
+      acc0[i] = acc1[i];
+      acc1[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    if (a.absmax && m > 0.f) atomicMax(&bmax[t], __float_as_uint(m));
+    ++cur[t];
+  };
+  const int oy_lo = range[0], oy_hi = range[1];
+  const float* const img = a.dout + (size_t)b * H * W * a.lddout;
+  f32x4 v[NI];
+  auto load = [&](int oy) {
+    const float* row = img + (size_t)oy * W * a.lddout;
+#pragma unroll
+    for (int l = 0; l < NI; ++l)
+      if (l * T < W * sq) v[l] = ld4(row + ld_off[l]);          // (uniform)
+  };
+  auto write = [&](f32x4* slot) {
+#pragma unroll
+    for (int l = 0; l < NI; ++l)
+      if (tid + l * T < W * sq) slot[tid + l * T] = v[l];
+  };
+  if (oy_lo <= oy_hi) {
+    load(oy_lo);
+    write(ring);
+    __syncthreads();
+    for (int oy = oy_lo; oy <= oy_hi; ++oy) {
+      // row oy + 1 is in flight while row oy is consumed; it goes into the slot that row oy - 1 was read from (every thread
+      // has passed the barrier that ended that trip)
+      const bool more = oy < oy_hi;
+      if (more) load(oy + 1);
+      const f32x4* g = ring + ((oy - oy_lo) & 1) * rq;
+#pragma unroll
+      for (int t = 0; t < 3; ++t) {
+        if (t >= n) continue;
+        const float w0 = roww0[t * H + oy], w1 = roww1[t * H + oy];      // (the same in every thread: the branches are uniform)
+        if (w0 == 0.f && w1 == 0.f) continue;
+        const int y0 = __builtin_amdgcn_readfirstlane(rowy[t * H + oy]);
+        while (cur[t] < y0) rotate(t);
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+          if (it_t[i] != t) continue;
+          const f32x4* gi = g + it_g[i];
+          const float* wx = wxtab + it_w[i];
+          f32x4 c = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 2
+          for (int k = 0; k < it_nx[i]; ++k) {
+            const f32x4 gv = gi[k * sq];
+            const float w = wx[k];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) c[j] = __builtin_fmaf(w, gv[j], c[j]);
+          }
+          if (w0 != 0.f) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc0[i][j] = __builtin_fmaf(w0, c[j], acc0[i][j]);
+          }
+          if (w1 != 0.f) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc1[i][j] = __builtin_fmaf(w1, c[j], acc1[i][j]);
+          }
+        }
+      }
+      if (more) write(ring + ((oy + 1 - oy_lo) & 1) * rq);
+      __syncthreads();
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < 3; ++t) {
+    if (t >= n) continue;
+    while (cur[t] < band_r1[t]) rotate(t);
+  }
+  if (a.absmax) {
+    __syncthreads();
+    if (tid < n && bmax[tid] > 0u) atomicMax(reinterpret_cast<unsigned*>(a.absmax) + tid * 64 + (bid & 63), bmax[tid]);
   }
 }
 
@@ -669,6 +885,82 @@ extern "C" int hrseg_head_mix(float* y, int ldy, const float* bias, int n_low, c
   return 0;
 }
 
+// The streaming body's plan.  -> 1 launched, 0 the shape is not its own (the caller runs the gather body), < 0 an error.
+//  * slab: the widest one whose row of dout (W x slab quads) and whose items (sum of Wi x slab quads) are at most
+//    BWD_STREAM_ITEMS per thread of a 512-thread block and whose ring is at most 64 KiB (two blocks per CU beside the tables):
+//    12 quads = 192 contiguous bytes per pixel at 155 columns, 15 slabs of the head's 720 channels.  A divisor of C / 4 where
+//    one lies in the upper half of that range, else a ragged last slab.  hrseg_tune bwd_multi_slab (channels) overrides it; a
+//    forced slab may take 1024 threads and one block per CU.
+//  * bands: as many as keep every block resident at once (BWD_STREAM_BLOCKS = two per CU; a fifth band at the head's shape
+//    starts a second round of blocks: 270 us with four, 352 with five), at most the rows of the coarsest target.
+//    hrseg_tune bwd_multi_bands overrides, clamped likewise.
+//  * the rule between the bodies, measured in isolation on MI355X (profiles/README.md "Streaming bilinear transpose"): a block
+//    streams its rows one after the other, so the body needs (slab, image) pairs -- at least a block per CU with
+//    BWD_STREAM_BANDS bands.  Head, 720 ch x 155 x 155 x 8 images, 120 pairs: streaming 270 us, gather 448 us.  Fuse layers,
+//    one slab x 8 images: streaming 69 / 28 / 11.5 us at its best band count (48 ch x 155 onto three targets / 96 x 78 onto
+//    two / 192 x 39 onto one), gather 36 / 16 / 10.3 us -- their gradients (12-49 MB) stay in the Infinity Cache and the
+//    re-reads cost little: they keep the gather body.  A knob that is set sends the shape to the streaming body regardless.
+#define BWD_STREAM_BLOCKS 512
+#define BWD_STREAM_BANDS 4
+static int bilinear_bwd_stream(BilinearBwdStreamArgs& a, hipStream_t stream) {
+  const int Q = a.C / 4, W = a.W, n = a.n;
+  int cols = 0, wx = 0, hmin = a.Hi[0];
+  for (int j = 0; j < n; ++j) {
+    a.col0[j] = cols; a.wx0[j] = wx;
+    cols += a.Wi[j];
+    wx += a.Wi[j] * a.nx[j];
+    if (a.Hi[j] < hmin) hmin = a.Hi[j];
+    if ((long)a.B * a.Hi[j] * a.Wi[j] * a.lddin[j] >= 2147483647L) return 0;      // (the kernel's element offsets are ints)
+    // a target larger than dout (no model issues one) has footprints of one or two terms: against hrseg_bilinear_bwd the
+    // separable products' extra rounding is not covered by 2 * n * 2^-24 * A at n = 1
+    if (a.Hi[j] > a.H || a.Wi[j] > W) return 0;
+  }
+  a.col0[n] = cols;
+  const int wide = cols > W ? cols : W;                          // quads of work per slab quad: loads or items, the larger
+  if ((long)W * a.lddout >= 2147483647L) return 0;
+  const size_t tables = ((size_t)3 * n * a.H + 2 * cols + wx) * sizeof(float);
+  auto ring_bytes = [&](int sq) { return (size_t)2 * W * sq * 16; };
+  int sq = hrseg_g_bwd_multi_slab / 4;
+  if (sq > 0) {                                                  // forced: clamped to what one block can hold
+    if (sq > Q) sq = Q;
+    while (sq > 1 && ((long)wide * sq > BWD_STREAM_ITEMS * 1024 || ring_bytes(sq) + tables > 150 * 1024)) --sq;
+  } else {
+    int most = Q;
+    while (most > 1 && ((long)wide * most > BWD_STREAM_ITEMS * 512 || ring_bytes(most) > 64 * 1024)) --most;
+    sq = most;
+    for (int d = most; 2 * d > most; --d)
+      if (Q % d == 0) { sq = d; break; }
+  }
+  if ((long)wide * sq > BWD_STREAM_ITEMS * 1024 || ring_bytes(sq) + tables > 150 * 1024) return 0;
+  const int threads = (long)wide * sq <= BWD_STREAM_ITEMS * 256 ? 256 : (long)wide * sq <= BWD_STREAM_ITEMS * 512 ? 512 : 1024;
+  const int nslab = ceil_div(Q, sq);
+  const bool forced = hrseg_g_bwd_multi_bands > 0 || hrseg_g_bwd_multi_slab > 0;
+  if (!forced && (long)nslab * a.B * BWD_STREAM_BANDS < BWD_STREAM_BLOCKS / 2) return 0;
+  int nbands = hrseg_g_bwd_multi_bands > 0 ? hrseg_g_bwd_multi_bands : (int)(BWD_STREAM_BLOCKS / ((long)nslab * a.B));
+  if (nbands > hmin) nbands = hmin;
+  if (nbands < 1) nbands = 1;
+  a.SQ = sq; a.nbands = nbands;
+  const long blocks = (long)nslab * a.B * nbands;
+  HRSEG_CHECK_ARG(blocks < 2147483647L, "hrseg_bilinear_bwd_multi: %ld blocks exceed the grid", blocks);
+  const size_t lds = ring_bytes(sq) + tables;
+  static bool big_lds = false;
+  if (lds > 48 * 1024 && !big_lds) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&bilinear_bwd_stream_kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    if (e != hipSuccess) {
+      hrseg_set_error("hrseg_bilinear_bwd_multi: %d bytes of LDS refused: %s", 150 * 1024, hipGetErrorString(e));
+      return HRSEG_ERR_LAUNCH;
+    }
+    big_lds = true;
+  }
+  hipLaunchKernelGGL(bilinear_bwd_stream_kernel, dim3((unsigned)blocks), dim3(threads), lds, stream, a);
+  HRSEG_LAUNCH_CHECK("bilinear_bwd_multi");
+  return 1;
+}
+
+// Routing (the rule and its numbers: bilinear_bwd_stream above): the streaming body where there are enough (slab, image)
+// pairs to fill the chip and the plan fits one block; the gather body otherwise -- small gradients, targets larger than
+// dout, rows or tables too large for LDS -- and on request (hrseg_tune bwd_multi_slab < 0: tools/bwd_multi_bench.py).
 extern "C" int hrseg_bilinear_bwd_multi(const float* dout, int lddout, int B, int Hout, int Wout, int C, int n,
                                         float* const* din, const int* lddin, const int* Hi, const int* Wi, int align_corners,
                                         float* absmax, hrseg_stream_t stream) {
@@ -676,6 +968,20 @@ extern "C" int hrseg_bilinear_bwd_multi(const float* dout, int lddout, int B, in
   HRSEG_CHECK_ARG(dout && lddout >= C && lddout % 4 == 0 && B > 0 && Hout > 0 && Wout > 0 && n >= 1 && n <= 3 && din && lddin &&
                       Hi && Wi,
                   "hrseg_bilinear_bwd_multi: bad arguments (1..3 targets, lddout=%d C=%d)", lddout, C);
+  for (int j = 0; j < n; ++j)
+    HRSEG_CHECK_ARG(din[j] && lddin[j] >= C && lddin[j] % 4 == 0 && Hi[j] > 0 && Wi[j] > 0, "hrseg_bilinear_bwd_multi: bad target %d", j);
+  if (hrseg_g_bwd_multi_slab >= 0) {
+    BilinearBwdStreamArgs s{};
+    s.dout = dout; s.lddout = lddout; s.B = B; s.H = Hout; s.W = Wout; s.C = C; s.n = n; s.align = align_corners;
+    s.absmax = absmax;
+    for (int j = 0; j < n; ++j) {
+      s.din[j] = din[j]; s.lddin[j] = lddin[j]; s.Hi[j] = Hi[j]; s.Wi[j] = Wi[j];
+      s.sh[j] = resize_scale(Hi[j], Hout, align_corners);
+      s.sw[j] = resize_scale(Wi[j], Wout, align_corners);
+      s.nx[j] = s.sw[j] > 0.f ? min(Wout, (int)(2.0 / s.sw[j]) + 6) : Wout;       // (as for the gather body, below)
+    }
+    if (int r = bilinear_bwd_stream(s, (hipStream_t)stream)) return r < 0 ? r : 0;
+  }
   BilinearBwdMultiArgs a{};
   a.dout = dout; a.lddout = lddout; a.B = B; a.Hout = Hout; a.Wout = Wout; a.C = C; a.n = n; a.align = align_corners;
   a.absmax = absmax;
@@ -689,10 +995,8 @@ extern "C" int hrseg_bilinear_bwd_multi(const float* dout, int lddout, int B, in
   while (lanes < 16 && Q * lanes * 2 <= 768) lanes *= 2;
   a.lanes = lanes;
   int nbands = Hi[0];
-  for (int j = 0; j < n; ++j) {
-    HRSEG_CHECK_ARG(din[j] && lddin[j] >= C && lddin[j] % 4 == 0 && Hi[j] > 0 && Wi[j] > 0, "hrseg_bilinear_bwd_multi: bad target %d", j);
+  for (int j = 0; j < n; ++j)
     if (Hi[j] < nbands) nbands = Hi[j];
-  }
   a.nbands = nbands;
   int end = 0, tab = 0;
   for (int j = 0; j < n; ++j) {

@@ -91,7 +91,10 @@ static inline void hrseg_count(int id, long n = 1) { hrseg_g_cnt[id] += n; }
   X(sp_patch_min_tiles, 192, 1, "routing threshold: least tile count of the halo-patch body")                                        \
   X(auto_min_pixels, 8192, 1, "routing threshold: HRSEG_CONV_AUTO runs fp16x2 from this many output pixels on")                      \
   X(sp_ws_min_tiles, 96, 1, "routing threshold: least tile count of the wave-specialised body")                                      \
-  X(deterministic, 0, 0, "1 = every float reduction with a run-dependent order takes its single-adder form (common.h)")
+  X(deterministic, 0, 0, "1 = every float reduction with a run-dependent order takes its single-adder form (common.h)")             \
+  X(bwd_multi_slab, 0, 0, "multi-target bilinear transpose: channels of a slab of the streaming body (0 = automatic, < 0 = the gather body)") \
+  X(bwd_multi_bands, 0, 0, "  ... its bands of target rows per image (0 = automatic; clamped to the coarsest target's rows)")        \
+  X(fuse_bwd_multi, 1, 0, "0 = the fuse layers' backward transposes each low-resolution term in a launch of its own (engine.py)")
 #define HRSEG_X(key, def, restore, meaning) extern int hrseg_g_##key;
 HRSEG_KNOBS(HRSEG_X)
 #undef HRSEG_X

@@ -528,7 +528,20 @@ class Recorder:
             def bwd():
                 g = ops.relu_bwd(y.grad, y.data, out=y.grad)
                 y.grad = None
-                for a in lows:
+                # the terms this layer is the first reader of (in HRNet: all of them) take their gradients from ONE launch
+                # that streams g once (hrseg_bilinear_bwd_multi, at most three targets; hrseg_tune fuse_bwd_multi = 0: off)
+                first = {}
+                if _lib.fuse_bwd_multi():
+                    for i, a in enumerate(lows):
+                        if a.grad is None and len(first) < 3 and all(a is not lows[j] for j in first):
+                            first[i] = a
+                if first:
+                    dts, _ = ops.bilinear_bwd_multi(g, [tuple(a.data.shape[1:3]) for a in first.values()], align_corners)
+                    for a, dt in zip(first.values(), dts):
+                        a.grad = dt
+                for i, a in enumerate(lows):
+                    if i in first:
+                        continue
                     if a.grad is None:
                         a.grad = ops.bilinear_bwd(g, a.data.shape, H, W, 0, 0, align_corners)
                     else:
