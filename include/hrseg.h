@@ -482,6 +482,22 @@ int hrseg_loss_finalize(const double* partial, const float* w, int B, int C, flo
 /* dz (=|+=) g_ce*dCE/dz + g_dice*dDice/dz ; g = device pointer to {g_ce,g_dice} */
 int hrseg_loss_bwd(const float* z, const float* t, const float* coef, const float* g, float* dz,
                    int accumulate, int B, int C, long hw, hrseg_stream_t stream);
+/* The same three with the loss options, by value (the entry points above are these at gamma = 0, smooth = 0, alpha = beta =
+ * 0.5, bit for bit).  Valid pixels t != -1, w the class weights, I = sum_c w_c sum p t, P = sum_c w_c sum p, T = sum_c w_c sum t:
+ *   gamma  focal exponent of the CE: the per-pixel term is -t (1-p)^gamma log p, with 1 - p_c taken as the other channels'
+ *          share of the softmax sum (never as a subtraction, which is 0 in fp32 at saturated pixels); 0 in the limit 1-p -> 0.
+ *          partials and bwd must be given the same gamma.
+ *   smooth, alpha, beta  Dice item = 1 - (2I + smooth) / (2(1-alpha-beta) I + 2 alpha P + 2 beta T + smooth): Tversky weights
+ *          alpha on the false positives P - I and beta on the false negatives T - I; an item is valid (counted in out[2], part
+ *          of the mean) iff its denominator is not 0, so smooth > 0 keeps every item.
+ * Each option must be finite and >= 0: anything else is refused (-1, the message starts with the entry point's name) before a
+ * launch.  A NaN logit gives a NaN CE and a NaN dz at its pixel under every option. */
+int hrseg_loss_partials_opt(const float* z, const float* t, double* partial, int B, int C, long hw,
+                            float gamma, hrseg_stream_t stream);
+int hrseg_loss_finalize_opt(const double* partial, const float* w, int B, int C, float smooth, float alpha,
+                            float beta, float* out, float* coef, hrseg_stream_t stream);
+int hrseg_loss_bwd_opt(const float* z, const float* t, const float* coef, const float* g, float* dz,
+                       int accumulate, int B, int C, long hw, float gamma, hrseg_stream_t stream);
 /* per-class metric vectors of nlevels (1..8) levels from their confusion counts in ONE launch: cm[L] (DEVICE, int64
  * [K_L][K_L], (target, predicted) as hrseg_predict_metrics counts them), child[L] != 0: label 0 is the synthetic background
  * of a child level (its row is dropped, its class not reported).  out (DEVICE) receives [5][sum_L (K_L - child_L)] floats:

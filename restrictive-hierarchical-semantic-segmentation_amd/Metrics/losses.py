@@ -10,9 +10,15 @@ masked per-(b,c) sums both losses need; the reference walks B*C boolean-mask
 gathers per loss (losses.py:52-59, :100-114), each a device->host sync.  The
 gradient is one more pass (hrseg_loss_bwd).  Semantics kept: mask = target != -1,
 CE item -> constant 1.0 when any class mask of the item is empty (:116), Dice
-items with 0/0 dropped (:64), Dice -> None when no item survives (:66).
+items with 0/0 dropped (:64), Dice -> None when no item survives (:66), Dice's
+``smooth`` in numerator and denominator (:40).  Beyond the reference: a focal
+exponent on the CE and Tversky weights in the Dice denominator (LossOptions); the
+defaults are the reference's losses, bit for bit what they were without options.
 """
 from __future__ import annotations
+
+import math
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -34,28 +40,61 @@ def _weights(class_weight, device):
     return w
 
 
+def _option(name, value):
+    """a loss option as a float: finite and >= 0, or ValueError"""
+    v = float(value)
+    if not (math.isfinite(v) and v >= 0.0):
+        raise ValueError(f"{name} must be finite and >= 0, got {value!r}")
+    return v
+
+
+class LossOptions(NamedTuple):
+    """What the fused loss kernels take by value besides the class weights (hrseg_loss_*_opt): the focal exponent of the CE
+    term, -t (1-p)^gamma log p, and the Dice term's smoothing and Tversky weights,
+    1 - (2I + smooth) / (2(1-alpha-beta) I + 2 alpha P + 2 beta T + smooth).  The defaults are the reference's losses."""
+    gamma: float = 0.0
+    smooth: float = 0.0
+    alpha: float = 0.5
+    beta: float = 0.5
+
+    @classmethod
+    def from_pair(cls, ce_fn=None, dice_fn=None):
+        """the options of a (CrossEntropyLoss, SoftDiceLoss) pair; None = that loss at its defaults"""
+        gamma = 0.0 if ce_fn is None else _option("focal_gamma", ce_fn.focal_gamma)
+        if dice_fn is None:
+            return cls(gamma=gamma)
+        return cls(gamma, _option("smooth", dice_fn.smooth), _option("alpha", dice_fn.alpha), _option("beta", dice_fn.beta))
+
+    def or_none(self):
+        """None at the defaults -- ops.loss_fwd / loss_bwd then make the calls without options -- else the tuple"""
+        return None if self == LossOptions() else self
+
+
 class _FusedLoss(torch.autograd.Function):
-    """(logits, targets, w) -> [ce, dice, n_valid_dice_items]"""
+    """(logits, targets, w, options) -> [ce, dice, n_valid_dice_items]"""
 
     @staticmethod
-    def forward(ctx, z, t, w):
+    def forward(ctx, z, t, w, options):
         z = z.contiguous()
         t = t.contiguous()
-        out, coef = ops.loss_fwd(z, t, w)
+        out, coef = ops.loss_fwd(z, t, w, options)
         ctx.save_for_backward(z, t, coef)
+        ctx.options = options
         return out
 
     @staticmethod
     def backward(ctx, g):
         z, t, coef = ctx.saved_tensors
-        return ops.loss_bwd(z, t, coef, g.contiguous()), None, None
+        return ops.loss_bwd(z, t, coef, g.contiguous(), options=ctx.options), None, None, None
 
 
-def fused_ce_dice(logits, targets, class_weight):
-    """-> tensor [3] = (CE, Dice, number of valid Dice items); differentiable w.r.t. logits."""
+def fused_ce_dice(logits, targets, class_weight, options=None):
+    """-> tensor [3] = (CE, Dice, number of valid Dice items); differentiable w.r.t. logits.  `options`: a LossOptions
+    (None = the defaults)."""
     if logits.shape[1] != len(class_weight):
         raise ValueError(f"class_weight has {len(class_weight)} entries, logits have {logits.shape[1]} channels")
-    return _FusedLoss.apply(logits, targets, _weights(class_weight, logits.device))
+    options = None if options is None else LossOptions(*options).or_none()
+    return _FusedLoss.apply(logits, targets, _weights(class_weight, logits.device), options)
 
 
 def global_batch_dice(res, group=None):
@@ -89,21 +128,31 @@ def _as_logits(outs, logits_input, log_domain):
 
 
 class CrossEntropyLoss(nn.Module):
-    def __init__(self, smooth=0.0):
+    """Masked class-weighted CE; ``focal_gamma`` > 0 multiplies each pixel's term by (1 - p)^gamma (focal loss), 0 is the
+    reference's CE.  ``smooth`` is stored and never used, as in the reference (its CE has no smoothing term either)."""
+
+    def __init__(self, smooth=0.0, focal_gamma=0.0):
         super().__init__()
         self.smooth = smooth
+        self.focal_gamma = _option("focal_gamma", focal_gamma)
 
     def forward(self, outs, targets, logits_input=False, class_weight=None):
-        return fused_ce_dice(_as_logits(outs, logits_input, True), targets, class_weight)[0]
+        return fused_ce_dice(_as_logits(outs, logits_input, True), targets, class_weight, LossOptions.from_pair(self, None))[0]
 
 
 class SoftDiceLoss(nn.Module):
-    def __init__(self, smooth=0, num_classes=3):
+    """Masked class-weighted soft Dice per item, (2I + smooth) / (U + smooth) as the reference computes it (losses.py:40):
+    with smooth > 0 no item is 0/0, so every item counts.  ``alpha`` / ``beta`` weigh the false positives / false negatives
+    in the denominator (Tversky); 0.5 / 0.5 is Dice."""
+
+    def __init__(self, smooth=0, num_classes=3, alpha=0.5, beta=0.5):
         super().__init__()
-        self.smooth = smooth
+        self.smooth = _option("smooth", smooth)
+        self.alpha = _option("alpha", alpha)
+        self.beta = _option("beta", beta)
 
     def forward(self, outs, targets, logits_input=False, class_weight=None):
-        res = fused_ce_dice(_as_logits(outs, logits_input, False), targets, class_weight)
+        res = fused_ce_dice(_as_logits(outs, logits_input, False), targets, class_weight, LossOptions.from_pair(None, self))
         if float(res[2]) == 0.0:          # every item was 0/0: the reference returns None
             return None
         return res[1]

@@ -111,6 +111,9 @@ PROTOTYPES = {
     "hrseg_loss_partials": [_p, _p, _p, _i, _i, _l, _p],
     "hrseg_loss_finalize": [_p, _p, _i, _i, _p, _p, _p],
     "hrseg_loss_bwd": [_p, _p, _p, _p, _p, _i, _i, _i, _l, _p],
+    "hrseg_loss_partials_opt": [_p, _p, _p, _i, _i, _l, _f, _p],
+    "hrseg_loss_finalize_opt": [_p, _p, _i, _i, _f, _f, _f, _p, _p, _p],
+    "hrseg_loss_bwd_opt": [_p, _p, _p, _p, _p, _i, _i, _i, _l, _f, _p],
     "hrseg_consistency": [_p, _p, _p, _i, _i, _i, _l, _i, _p, _p, _p],
     "hrseg_consistency_bwd": [_p, _p, _p, _f, _p, _p, _i, _i, _i, _l, _i, _p, _p, _p],
     "hrseg_group_kl": [_p, _p, _p, _i, _i, _i, _l, _i, _p, _p, _p],

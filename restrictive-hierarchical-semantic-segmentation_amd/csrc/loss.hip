@@ -4,6 +4,8 @@
 //
 // Logits / targets here are NCHW fp32 planes ([B,C,hw]) as the reference returns them; a thread owns one pixel and holds
 // its CT channels in registers.
+#include <cfloat>
+
 #include "common.h"
 #include "level_common.h"
 
@@ -15,16 +17,42 @@
     else hipLaunchKernelGGL((KERNEL<16>), grid, dim3(256), 0, st, __VA_ARGS__);              \
   } while (0)
 
+// the same ladder for kernels with a second template argument: KERNEL<CT, FLAG>
+#define LAUNCH_CT_FLAG(KERNEL, FLAG, C, grid, st, ...)                                             \
+  do {                                                                                             \
+    if ((C) <= 4) hipLaunchKernelGGL((KERNEL<4, FLAG>), grid, dim3(256), 0, st, __VA_ARGS__);      \
+    else if ((C) <= 8) hipLaunchKernelGGL((KERNEL<8, FLAG>), grid, dim3(256), 0, st, __VA_ARGS__); \
+    else hipLaunchKernelGGL((KERNEL<16, FLAG>), grid, dim3(256), 0, st, __VA_ARGS__);              \
+  } while (0)
+
 // --------------------------------------------------------------------------- loss
+// Focal CE (the FOCAL instances, gamma > 0): the per-pixel term is -t (1-p)^gamma log p.  om = 1 - p_c arrives as the sum of
+// the OTHER channels' exponentials over the softmax denominator, never as 1 - p: the subtraction is 0 in fp32 once a logit
+// gap passes 17, and for gamma < 1 the gradient factor (1-p)^(gamma-1) then makes 0 * inf.  `rest` = the exponentials after
+// channel c summed from the top (filled by focal_suffix), `pre` = those before it.
+template <int CT>
+__device__ __forceinline__ void focal_suffix(const float (&e)[CT], float (&rest)[CT]) {
+  float r = 0.f;
+#pragma unroll
+  for (int c = CT - 1; c >= 0; --c) {
+    rest[c] = r;
+    r += e[c];
+  }
+}
+// (1-p)^gamma; the limit at om -> 0 is 0 (all other exponentials underflowed, or C = 1); a NaN om stays NaN
+__device__ __forceinline__ float focal_pow(float om, float gamma) { return om == 0.f ? 0.f : expf(gamma * logf(om)); }
+// log p = log(1 - om): where p is near 1, z - m - log(sum) has already rounded to 0
+__device__ __forceinline__ float focal_logp(float om, float logp) { return om < 0.5f ? log1pf(-om) : logp; }
+
 __global__ void zero_f64_kernel(double* p, int n) {
   for (int i = threadIdx.x; i < n; i += blockDim.x) p[i] = 0.0;
 }
 
-// per (b,c): {n, sum t logp, sum p t, sum p, sum t} over pixels with t != -1
-template <int CT>
+// per (b,c): {n, sum t logp, sum p t, sum p, sum t} over pixels with t != -1; FOCAL: sum t (1-p)^gamma logp in slot 1
+template <int CT, bool FOCAL>
 __global__ __launch_bounds__(256) void loss_partials_kernel(const float* __restrict__ z, const float* __restrict__ t,
                                                             double* __restrict__ partial, int C, long hw,
-                                                            long pix_per_block) {
+                                                            long pix_per_block, float gamma) {
   __shared__ float red[4][CT * 5];
   const int b = blockIdx.y;
   const long lo = (long)blockIdx.x * pix_per_block;
@@ -52,16 +80,32 @@ __global__ __launch_bounds__(256) void loss_partials_kernel(const float* __restr
       s += (c < C) ? expf(zz[c]) : 0.f;
     }
     const float ls = logf(s), inv = 1.f / s;
+    float e[CT], rest[CT], pre = 0.f;
+    if constexpr (FOCAL) {
+#pragma unroll
+      for (int c = 0; c < CT; ++c) e[c] = (c < C) ? expf(zz[c]) : 0.f;
+      focal_suffix<CT>(e, rest);
+    }
 #pragma unroll
     for (int c = 0; c < CT; ++c) {
       if (c < C && tt[c] != -1.f) {
         const float logp = zz[c] - ls, p = expf(zz[c]) * inv;
         acc[c][0] += 1.f;
-        acc[c][1] += tt[c] * logp;
+        if constexpr (FOCAL) {
+          if (tt[c] != 0.f) {
+            const float om = (pre + rest[c]) * inv;
+            acc[c][1] += tt[c] * focal_pow(om, gamma) * focal_logp(om, logp);
+          } else {
+            acc[c][1] += tt[c] * logp;      // 0, or the NaN of a poisoned pixel
+          }
+        } else {
+          acc[c][1] += tt[c] * logp;
+        }
         acc[c][2] += p * tt[c];
         acc[c][3] += p;
         acc[c][4] += tt[c];
       }
+      if constexpr (FOCAL) pre += e[c];
     }
   }
 #pragma unroll
@@ -79,35 +123,58 @@ __global__ __launch_bounds__(256) void loss_partials_kernel(const float* __restr
 }
 
 // out[0]=CE out[1]=Dice out[2]=#valid dice items ; coef[b][c] = {ce, dice_a, dice_b, 0}
+// Dice item = 1 - N/D with N = 2I + smooth, D = 2(1-alpha-beta) I + 2 alpha P + 2 beta T + smooth (Tversky weights on the false
+// positives P - I and the false negatives T - I); an item counts iff D != 0.  d(item)/dp at a pixel of class c is
+// w_c (t (-2/D + 2N(1-alpha-beta)/D^2) + 2 alpha N / D^2): the two coefficient slots the backward multiplies t and 1 with.
+// smooth = 0, alpha = beta = 0.5 (`plain`) is 1 - 2I/U with U = P + T, evaluated by the expressions it always was.
 __global__ void loss_finalize_kernel(const double* __restrict__ partial, const float* __restrict__ w, int B, int C,
-                                     float* __restrict__ out, float* __restrict__ coef) {
+                                     float smooth, float alpha, float beta, float* __restrict__ out,
+                                     float* __restrict__ coef) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const bool plain = (smooth == 0.f && alpha == 0.5f && beta == 0.5f);
+  const double sm = smooth, al = alpha, be = beta, mix = 1.0 - al - be;
   double ce = 0.0, dice = 0.0;
   int nvalid = 0;
   for (int b = 0; b < B; ++b) {
-    double U = 0.0;
-    for (int c = 0; c < C; ++c) U += (double)w[c] * (partial[(b * C + c) * 5 + 3] + partial[(b * C + c) * 5 + 4]);
-    if (U != 0.0) ++nvalid;
+    double I = 0.0, P = 0.0, T = 0.0, U = 0.0;
+    for (int c = 0; c < C; ++c) {
+      const double* q = partial + (b * C + c) * 5;
+      U += (double)w[c] * (q[3] + q[4]);
+      I += (double)w[c] * q[2];
+      P += (double)w[c] * q[3];
+      T += (double)w[c] * q[4];
+    }
+    const double D = plain ? U : 2.0 * mix * I + 2.0 * al * P + 2.0 * be * T + sm;
+    if (D != 0.0) ++nvalid;
   }
   for (int b = 0; b < B; ++b) {
     bool ok = true;
-    double item = 0.0, I = 0.0, U = 0.0;
+    double item = 0.0, I = 0.0, U = 0.0, P = 0.0, T = 0.0;
     for (int c = 0; c < C; ++c) {
       const double* q = partial + (b * C + c) * 5;
       if (q[0] <= 0.0) ok = false;
       else item += -(double)w[c] * q[1] / q[0];
       I += (double)w[c] * q[2];
       U += (double)w[c] * (q[3] + q[4]);
+      P += (double)w[c] * q[3];
+      T += (double)w[c] * q[4];
     }
     ce += ok ? item / C : 1.0;
-    const bool dv = (U != 0.0);
-    if (dv) dice += 1.0 - 2.0 * I / U;
+    const double N = 2.0 * I + sm;
+    const double D = plain ? U : 2.0 * mix * I + 2.0 * al * P + 2.0 * be * T + sm;
+    const bool dv = (D != 0.0);
+    if (dv) dice += plain ? 1.0 - 2.0 * I / U : 1.0 - N / D;
     for (int c = 0; c < C; ++c) {
       const double* q = partial + (b * C + c) * 5;
       float* k = coef + (b * C + c) * 4;
       k[0] = ok ? (float)(-(double)w[c] / (q[0] * C * B)) : 0.f;
-      k[1] = dv ? (float)(-2.0 * w[c] / (U * nvalid)) : 0.f;
-      k[2] = dv ? (float)(2.0 * I * w[c] / (U * U * nvalid)) : 0.f;
+      if (plain) {
+        k[1] = dv ? (float)(-2.0 * w[c] / (U * nvalid)) : 0.f;
+        k[2] = dv ? (float)(2.0 * I * w[c] / (U * U * nvalid)) : 0.f;
+      } else {
+        k[1] = dv ? (float)((double)w[c] * (-2.0 / D + 2.0 * N * mix / (D * D)) / nvalid) : 0.f;
+        k[2] = dv ? (float)((double)w[c] * 2.0 * al * N / (D * D * nvalid)) : 0.f;
+      }
       k[3] = 0.f;
     }
   }
@@ -116,10 +183,12 @@ __global__ void loss_finalize_kernel(const double* __restrict__ partial, const f
   out[2] = (float)nvalid;
 }
 
-template <int CT>
+// FOCAL: d(-t (1-p)^gamma log p) / d log p = -t [(1-p)^gamma - gamma p (1-p)^(gamma-1) log p] replaces the CE's -t; the
+// softmax Jacobian behind it is the same.  The bracket is (1-p)^gamma (1 - gamma p log p / (1-p)), 0 in the limit 1-p -> 0.
+template <int CT, bool FOCAL>
 __global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__ z, const float* __restrict__ t,
                                                        const float* __restrict__ coef, const float* __restrict__ g,
-                                                       float* __restrict__ dz, int acc, int C, long hw) {
+                                                       float* __restrict__ dz, int acc, int C, long hw, float gamma) {
   const int b = blockIdx.y;
   const long pix = (long)blockIdx.x * 256 + threadIdx.x;
   if (pix >= hw) return;
@@ -142,16 +211,30 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__
   }
   const float inv = 1.f / s;
   float dlogp[CT], dpr[CT], sum_dlogp = 0.f, dot = 0.f;
+  float rest[CT], pre = 0.f, ls = 0.f;
+  if constexpr (FOCAL) {
+    focal_suffix<CT>(p, rest);          // p still holds the exponentials
+    ls = logf(s);
+  }
 #pragma unroll
   for (int c = 0; c < CT; ++c) {
+    const float e = p[c];
     p[c] *= inv;
     dlogp[c] = 0.f;
     dpr[c] = 0.f;
     if (c < C && tt[c] != -1.f) {
       const float* k = coef + ((size_t)b * C + c) * 4;
       dlogp[c] = gce * k[0] * tt[c];
+      if constexpr (FOCAL) {
+        if (tt[c] != 0.f) {
+          const float om = (pre + rest[c]) * inv;
+          const float logp = focal_logp(om, zz[c] - m - ls);
+          dlogp[c] *= (om == 0.f) ? 0.f : focal_pow(om, gamma) * (1.f - gamma * p[c] * logp / om);
+        }
+      }
       dpr[c] = gdice * (k[1] * tt[c] + k[2]);
     }
+    if constexpr (FOCAL) pre += e;
     sum_dlogp += dlogp[c];
     dot += p[c] * dpr[c];
   }
@@ -164,9 +247,14 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__
     }
 }
 
-extern "C" int hrseg_loss_partials(const float* z, const float* t, double* partial, int B, int C, long hw,
-                                   hrseg_stream_t stream) {
-  HRSEG_CHECK_ARG(z && t && partial && B > 0 && C > 0 && C <= MAXC && hw > 0, "hrseg_loss_partials: bad arguments (C=%d)", C);
+// The entry points without options are the _opt ones at gamma = 0, smooth = 0, alpha = beta = 0.5; `name` is the one that was
+// called (a refusal names it).  An option must be finite and >= 0.
+static bool loss_option_ok(float v) { return v >= 0.f && v <= FLT_MAX; }
+
+static int loss_partials(const char* name, const float* z, const float* t, double* partial, int B, int C, long hw,
+                         float gamma, hrseg_stream_t stream) {
+  HRSEG_CHECK_ARG(z && t && partial && B > 0 && C > 0 && C <= MAXC && hw > 0, "%s: bad arguments (C=%d)", name, C);
+  HRSEG_CHECK_ARG(loss_option_ok(gamma), "%s: gamma must be finite and >= 0 (got %g)", name, (double)gamma);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(zero_f64_kernel, dim3(1), dim3(256), 0, st, partial, B * C * 5);   // kernel node, not memset
   long chunks = hrseg_g_deterministic ? 1 : 1024 / B;      // deterministic: one block (one adder) per image
@@ -174,27 +262,59 @@ extern "C" int hrseg_loss_partials(const float* z, const float* t, double* parti
   long ppb = (hw + chunks - 1) / chunks;
   if (ppb < 256) ppb = 256;
   dim3 grid(ceil_div(hw, ppb), B);
-  LAUNCH_CT(loss_partials_kernel, C, grid, st, z, t, partial, C, hw, ppb);
+  if (gamma > 0.f) LAUNCH_CT_FLAG(loss_partials_kernel, true, C, grid, st, z, t, partial, C, hw, ppb, gamma);
+  else LAUNCH_CT_FLAG(loss_partials_kernel, false, C, grid, st, z, t, partial, C, hw, ppb, gamma);
   HRSEG_LAUNCH_CHECK("loss_partials");
   return 0;
 }
 
-extern "C" int hrseg_loss_finalize(const double* partial, const float* w, int B, int C, float* out, float* coef,
-                                   hrseg_stream_t stream) {
-  HRSEG_CHECK_ARG(partial && w && out && coef && B > 0 && C > 0, "hrseg_loss_finalize: bad arguments");
-  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, partial, w, B, C, out, coef);
+static int loss_finalize(const char* name, const double* partial, const float* w, int B, int C, float smooth, float alpha,
+                         float beta, float* out, float* coef, hrseg_stream_t stream) {
+  HRSEG_CHECK_ARG(partial && w && out && coef && B > 0 && C > 0, "%s: bad arguments", name);
+  HRSEG_CHECK_ARG(loss_option_ok(smooth) && loss_option_ok(alpha) && loss_option_ok(beta),
+                  "%s: smooth, alpha and beta must be finite and >= 0 (got %g, %g, %g)", name, (double)smooth, (double)alpha,
+                  (double)beta);
+  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, partial, w, B, C, smooth, alpha, beta,
+                     out, coef);
   HRSEG_LAUNCH_CHECK("loss_finalize");
   return 0;
 }
 
-extern "C" int hrseg_loss_bwd(const float* z, const float* t, const float* coef, const float* g, float* dz,
-                              int accumulate, int B, int C, long hw, hrseg_stream_t stream) {
-  HRSEG_CHECK_ARG(z && t && coef && g && dz && B > 0 && C > 0 && C <= MAXC && hw > 0, "hrseg_loss_bwd: bad arguments");
+static int loss_bwd(const char* name, const float* z, const float* t, const float* coef, const float* g, float* dz,
+                    int accumulate, int B, int C, long hw, float gamma, hrseg_stream_t stream) {
+  HRSEG_CHECK_ARG(z && t && coef && g && dz && B > 0 && C > 0 && C <= MAXC && hw > 0, "%s: bad arguments", name);
+  HRSEG_CHECK_ARG(loss_option_ok(gamma), "%s: gamma must be finite and >= 0 (got %g)", name, (double)gamma);
   hipStream_t st = (hipStream_t)stream;
   dim3 grid(ceil_div(hw, 256), B);
-  LAUNCH_CT(loss_bwd_kernel, C, grid, st, z, t, coef, g, dz, accumulate, C, hw);
+  if (gamma > 0.f) LAUNCH_CT_FLAG(loss_bwd_kernel, true, C, grid, st, z, t, coef, g, dz, accumulate, C, hw, gamma);
+  else LAUNCH_CT_FLAG(loss_bwd_kernel, false, C, grid, st, z, t, coef, g, dz, accumulate, C, hw, gamma);
   HRSEG_LAUNCH_CHECK("loss_bwd");
   return 0;
+}
+
+extern "C" int hrseg_loss_partials(const float* z, const float* t, double* partial, int B, int C, long hw,
+                                   hrseg_stream_t stream) {
+  return loss_partials("hrseg_loss_partials", z, t, partial, B, C, hw, 0.f, stream);
+}
+extern "C" int hrseg_loss_partials_opt(const float* z, const float* t, double* partial, int B, int C, long hw, float gamma,
+                                       hrseg_stream_t stream) {
+  return loss_partials("hrseg_loss_partials_opt", z, t, partial, B, C, hw, gamma, stream);
+}
+extern "C" int hrseg_loss_finalize(const double* partial, const float* w, int B, int C, float* out, float* coef,
+                                   hrseg_stream_t stream) {
+  return loss_finalize("hrseg_loss_finalize", partial, w, B, C, 0.f, 0.5f, 0.5f, out, coef, stream);
+}
+extern "C" int hrseg_loss_finalize_opt(const double* partial, const float* w, int B, int C, float smooth, float alpha,
+                                       float beta, float* out, float* coef, hrseg_stream_t stream) {
+  return loss_finalize("hrseg_loss_finalize_opt", partial, w, B, C, smooth, alpha, beta, out, coef, stream);
+}
+extern "C" int hrseg_loss_bwd(const float* z, const float* t, const float* coef, const float* g, float* dz,
+                              int accumulate, int B, int C, long hw, hrseg_stream_t stream) {
+  return loss_bwd("hrseg_loss_bwd", z, t, coef, g, dz, accumulate, B, C, hw, 0.f, stream);
+}
+extern "C" int hrseg_loss_bwd_opt(const float* z, const float* t, const float* coef, const float* g, float* dz,
+                                  int accumulate, int B, int C, long hw, float gamma, hrseg_stream_t stream) {
+  return loss_bwd("hrseg_loss_bwd_opt", z, t, coef, g, dz, accumulate, B, C, hw, gamma, stream);
 }
 
 // --------------------------------------------------------------------------- predictions / confusion counts

@@ -1151,24 +1151,34 @@ def _c(t):
     return t if t.is_contiguous() else t.contiguous()
 
 
-def loss_fwd(z, t, w):
-    """-> (out[3] = ce, dice, n_valid_dice ; coef for the backward)"""
+def loss_fwd(z, t, w, options=None):
+    """-> (out[3] = ce, dice, n_valid_dice ; coef for the backward).  options = (focal gamma, Dice smooth, Tversky alpha,
+    beta) selects the hrseg_loss_*_opt entry points; None = the calls without options (gamma 0, smooth 0, alpha = beta = 0.5)"""
     z, t = _c(z), _c(t)
     B, Cn, H, W = z.shape
     part = torch.empty(B * Cn * 5, dtype=torch.float64, device=z.device)
     out = torch.empty(3, dtype=torch.float32, device=z.device)
     coef = torch.empty(B * Cn * 4, dtype=torch.float32, device=z.device)
-    call("hrseg_loss_partials", ptr(z), ptr(t), ptr(part), B, Cn, H * W)
-    call("hrseg_loss_finalize", ptr(part), ptr(w), B, Cn, ptr(out), ptr(coef))
+    if options is None:
+        call("hrseg_loss_partials", ptr(z), ptr(t), ptr(part), B, Cn, H * W)
+        call("hrseg_loss_finalize", ptr(part), ptr(w), B, Cn, ptr(out), ptr(coef))
+    else:
+        gamma, smooth, alpha, beta = (float(v) for v in options)
+        call("hrseg_loss_partials_opt", ptr(z), ptr(t), ptr(part), B, Cn, H * W, gamma)
+        call("hrseg_loss_finalize_opt", ptr(part), ptr(w), B, Cn, smooth, alpha, beta, ptr(out), ptr(coef))
     return out, coef
 
 
-def loss_bwd(z, t, coef, g, dz=None, accumulate=False):
+def loss_bwd(z, t, coef, g, dz=None, accumulate=False, options=None):
+    """`options`: the ones loss_fwd produced `coef` with (the backward itself reads the focal gamma only)"""
     z, t = _c(z), _c(t)
     B, Cn, H, W = z.shape
     if dz is None:
         dz, accumulate = torch.empty_like(z), False
-    call("hrseg_loss_bwd", ptr(z), ptr(t), ptr(coef), ptr(g), ptr(dz), int(accumulate), B, Cn, H * W)
+    if options is None:
+        call("hrseg_loss_bwd", ptr(z), ptr(t), ptr(coef), ptr(g), ptr(dz), int(accumulate), B, Cn, H * W)
+    else:
+        call("hrseg_loss_bwd_opt", ptr(z), ptr(t), ptr(coef), ptr(g), ptr(dz), int(accumulate), B, Cn, H * W, float(options[0]))
     return dz
 
 

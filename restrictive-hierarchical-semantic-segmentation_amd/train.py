@@ -442,7 +442,7 @@ def get_loss(output_logits, targets, lossFuncts, levelLoss, level_weights=None, 
         level_weight = None if level_weights is None else level_weights[L]
         ce_fn, dice_fn = lossFuncts[L][0], lossFuncts[L][1]
         if isinstance(ce_fn, losses.CrossEntropyLoss) and isinstance(dice_fn, losses.SoftDiceLoss):
-            res = losses.fused_ce_dice(output_logits[L], targets[L], level_weight)
+            res = losses.fused_ce_dice(output_logits[L], targets[L], level_weight, losses.LossOptions.from_pair(ce_fn, dice_fn))
             # Dice is 0 with zero gradient when no item is valid == the reference skipping None; under data
             # parallelism its divisor is the global count of valid items (losses.global_batch_dice)
             sync = (torch.is_grad_enabled() and res.requires_grad) if sync_dice is None else bool(sync_dice)
@@ -598,6 +598,8 @@ class TapedTrainStep:
         self.t_levels = [torch.empty_like(v) for v in split_targets(self.t, args)] if self.hier else [self.t]
         weights = args.level_weights
         self.w = [losses._weights(weights[L] if self.hier else weights[0], dev) for L in range(self.n_levels)]
+        # the level's loss options go into the recorded calls by value: fixed for the life of the recording
+        self.opts = [losses.LossOptions.from_pair(*lossFuncts[L][:2]).or_none() for L in range(self.n_levels)]
         # d loss / d (ce, dice, n_valid) per level; the Dice entry carries the data-parallel divisor correction
         self.seed = [torch.tensor([1.0, 1.0, 0.0], dtype=torch.float32, device=dev) for _ in range(self.n_levels)]
         self._n_all = torch.zeros(self.n_levels, dtype=torch.float32, device=dev)
@@ -657,7 +659,7 @@ class TapedTrainStep:
                 outs.append(None)
                 coefs.append(None)
                 continue
-            o, c = ops.loss_fwd(z, t, self.w[L])
+            o, c = ops.loss_fwd(z, t, self.w[L], self.opts[L])
             outs.append(o)
             coefs.append(c)
         cons = []
@@ -671,7 +673,7 @@ class TapedTrainStep:
             if len(live) != self.n_levels:
                 raise NotImplementedError("TapedTrainStep: level0_pretrain_epochs together with data parallelism")
             _lib.host_call(lambda: self._dice_sync(live))
-        dz = [ops.loss_bwd(z, t, coefs[L], self.seed[L]) if outs[L] is not None else None
+        dz = [ops.loss_bwd(z, t, coefs[L], self.seed[L], options=self.opts[L]) if outs[L] is not None else None
               for L, (z, t) in enumerate(zip(logits, self.t_levels))]
         n_probs = len(run.probs)
         run.backward([None] * n_probs, dz)
@@ -788,7 +790,8 @@ def taped_step_for(model, optimizer, lossFuncts, args, class_tree, data, target,
            dist.is_available() and dist.is_initialized() and dist.get_world_size(), m.training,
            tuple(tuple(float(v) for v in w) for w in args.level_weights),
            bool(getattr(optimizer, "clip_path", False)),       # the path, not the threshold: that lives on the device
-           bool(getattr(optimizer, "ema_path", False)))        # likewise: the decay is read from device memory
+           bool(getattr(optimizer, "ema_path", False)),        # likewise: the decay is read from device memory
+           tuple(losses.LossOptions.from_pair(c, d) for c, d in lossFuncts))   # by value in the recorded loss calls
     cache = m.__dict__.setdefault("_hr_tapes", {})
     step = cache.get(key)
     if step is not None:
