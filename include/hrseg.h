@@ -174,8 +174,9 @@ int hrseg_conv_wgrad_group_ws(int n, const float* const* x, const float* const* 
  * "augment_image" / "augment_targets" (the input pipeline) and "decode_labels" (the output pipeline, 1 launch per
  * hrseg_decode_labels call) and "score_labels" (the scoring pipeline, 1 launch per hrseg_score_labels call), "decode_views"
  * and "flip_views" (test-time augmentation, 1 launch per hrseg_decode_views / hrseg_flip_views call), "window_crops" and
- * "decode_windows" (sliding-window inference, 1 launch per hrseg_window_crops / hrseg_decode_windows call) are families of their
- * own, outside the NULL total and the convolution counts. */
+ * "decode_windows" (sliding-window inference, 1 launch per hrseg_window_crops / hrseg_decode_windows call) and "ohem" (online hard
+ * example mining: 1 launch per hrseg_ohem_scores, 7 per hrseg_ohem_select, 1 per hrseg_loss_partials_ohem / hrseg_loss_bwd_ohem call)
+ * are families of their own, outside the NULL total and the convolution counts. */
 long hrseg_launch_count(const char* family, int reset);
 /* tile-plan overrides and A/B switches for the sweep tools under tools/ (value 0 = automatic plan).  Keys: igemm_wtm,
  * igemm_kc, igemm_db, igemm_ksplit, group_wtm, wgrad_pix, wgrad_db, wgrad_blocks, wgrad_group_mult,
@@ -498,6 +499,33 @@ int hrseg_loss_finalize_opt(const double* partial, const float* w, int B, int C,
                             float beta, float* out, float* coef, hrseg_stream_t stream);
 int hrseg_loss_bwd_opt(const float* z, const float* t, const float* coef, const float* g, float* dz,
                        int accumulate, int B, int C, long hw, float gamma, hrseg_stream_t stream);
+/* Online hard example mining for the CE term (csrc/loss_ohem.hip), per level, over the level's whole batch.
+ * With p = softmax(z) over all C channels, a pixel is a CANDIDATE iff some channel has t != -1; its score is
+ * q = sum over those channels of t_c p_c (non-candidates: -1).  N = number of candidates; lam_k = the min(min_kept, N)-th
+ * smallest candidate score when min_kept >= 1 and N >= 1, else -1 (NaN scores sort last).  A candidate is KEPT iff
+ * q is NaN, q < thresh, or q <= lam_k: ties at lam_k are all kept, so n_kept >= min(min_kept, N), and a NaN logit stays loud.
+ *   hrseg_ohem_scores   one pass over (z, t) writes q[B*hw].
+ *   hrseg_ohem_select   q[n] -> record (DEVICE, 16 bytes: {float lam_k; int n_candidates; int n_kept; int reserved}), exactly: a
+ *                       radix select over the scores' bit patterns with integer counts, no sort, no host read; the same
+ *                       input gives the same record whatever the block order.  `workspace` (DEVICE, 4-byte aligned,
+ *                       hrseg_ohem_workspace_bytes() bytes) is zeroed by the call's own first launch.  7 launches.
+ *   hrseg_loss_partials_ohem / hrseg_loss_bwd_ohem   hrseg_loss_partials_opt / hrseg_loss_bwd_opt with the CE slots of
+ *                       partial (n and sum t (1-p)^gamma log p) and the CE part of dz restricted to kept pixels; both take
+ *                       the decision from the stored q and the record, never from a recomputed score.  The Dice slots and
+ *                       the Dice part of dz are those of the plain calls.  hrseg_loss_finalize[_opt] runs between them
+ *                       unchanged: an item with a class mask that is empty AFTER the selection is the constant 1.0.
+ * The selection is a constant of the step: no gradient flows through q or lam_k.  Refused (-1, the message starts with the
+ * entry point's name) before any launch: null pointers, thresh outside [0, 1] or not finite, min_kept < 0, n <= 0 or beyond
+ * 2^31 - 1, C outside 1..16.  Every launch of these four is counted under the family "ohem" (outside the NULL total). */
+size_t hrseg_ohem_workspace_bytes(void);
+int hrseg_ohem_scores(const float* z, const float* t, float* q, int B, int C, long hw, hrseg_stream_t stream);
+int hrseg_ohem_select(const float* q, long n, float thresh, long min_kept, void* workspace, void* record,
+                      hrseg_stream_t stream);
+int hrseg_loss_partials_ohem(const float* z, const float* t, const float* q, const void* record, float thresh,
+                             double* partial, int B, int C, long hw, float gamma, hrseg_stream_t stream);
+int hrseg_loss_bwd_ohem(const float* z, const float* t, const float* q, const void* record, float thresh,
+                        const float* coef, const float* g, float* dz, int accumulate, int B, int C, long hw,
+                        float gamma, hrseg_stream_t stream);
 /* per-class metric vectors of nlevels (1..8) levels from their confusion counts in ONE launch: cm[L] (DEVICE, int64
  * [K_L][K_L], (target, predicted) as hrseg_predict_metrics counts them), child[L] != 0: label 0 is the synthetic background
  * of a child level (its row is dropped, its class not reported).  out (DEVICE) receives [5][sum_L (K_L - child_L)] floats:

@@ -14,6 +14,10 @@ items with 0/0 dropped (:64), Dice -> None when no item survives (:66), Dice's
 ``smooth`` in numerator and denominator (:40).  Beyond the reference: a focal
 exponent on the CE and Tversky weights in the Dice denominator (LossOptions); the
 defaults are the reference's losses, bit for bit what they were without options.
+Online hard example mining on the CE term (OhemOptions):
+``CrossEntropyLoss(ohem_thresh=0.7, ohem_min_kept=100000)`` averages the CE over the
+pixels of the level's batch whose true-class probability is below the threshold, and
+over at least the ``ohem_min_kept`` hardest ones; the Dice term is untouched.
 """
 from __future__ import annotations
 
@@ -70,31 +74,72 @@ class LossOptions(NamedTuple):
         return None if self == LossOptions() else self
 
 
+def _ohem_thresh(value):
+    """ohem_thresh as a float: finite and in [0, 1], or ValueError"""
+    v = float(value)
+    if not (math.isfinite(v) and 0.0 <= v <= 1.0):
+        raise ValueError(f"ohem_thresh must be a finite number in [0, 1], got {value!r}")
+    return v
+
+
+def _ohem_min_kept(value):
+    """ohem_min_kept as an int >= 0, or ValueError (a float is accepted only when it is a whole number)"""
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or (isinstance(value, float) and not math.isfinite(value)) \
+            or int(value) != value or value < 0:
+        raise ValueError(f"ohem_min_kept must be an integer >= 0, got {value!r}")
+    return int(value)
+
+
+class OhemOptions(NamedTuple):
+    """Online hard example mining on the CE term of one level, by value into the recorded calls (hrseg_ohem_select,
+    hrseg_loss_*_ohem): with q = the softmax probability of the true class among the valid channels of a pixel, the CE runs over
+    the pixels with q < thresh, and over the min_kept hardest (smallest q) of the level's whole batch at least; ties at the
+    min_kept-th score and NaN scores are kept.  Travels beside LossOptions, which stays the four-field tuple it is."""
+    thresh: float
+    min_kept: int = 0
+
+    @classmethod
+    def from_ce(cls, ce_fn=None):
+        """the OHEM options of a CrossEntropyLoss; None = off (no loss object, or ohem_thresh=None)"""
+        if ce_fn is None or getattr(ce_fn, "ohem_thresh", None) is None:
+            return None
+        return cls(_ohem_thresh(ce_fn.ohem_thresh), _ohem_min_kept(ce_fn.ohem_min_kept))
+
+
 class _FusedLoss(torch.autograd.Function):
-    """(logits, targets, w, options) -> [ce, dice, n_valid_dice_items]"""
+    """(logits, targets, w, options, ohem, record_to) -> [ce, dice, n_valid_dice_items]"""
 
     @staticmethod
-    def forward(ctx, z, t, w, options):
+    def forward(ctx, z, t, w, options, ohem, record_to):
         z = z.contiguous()
         t = t.contiguous()
-        out, coef = ops.loss_fwd(z, t, w, options)
-        ctx.save_for_backward(z, t, coef)
         ctx.options = options
+        ctx.ohem = None
+        if ohem is None:
+            out, coef = ops.loss_fwd(z, t, w, options)
+        else:
+            out, coef, ctx.ohem = ops.loss_fwd(z, t, w, options, ohem=ohem)
+            if record_to is not None:
+                record_to.last_ohem = ctx.ohem.record
+        ctx.save_for_backward(z, t, coef)
         return out
 
     @staticmethod
     def backward(ctx, g):
         z, t, coef = ctx.saved_tensors
-        return ops.loss_bwd(z, t, coef, g.contiguous(), options=ctx.options), None, None, None
+        return ops.loss_bwd(z, t, coef, g.contiguous(), options=ctx.options, ohem=ctx.ohem), None, None, None, None, None
 
 
-def fused_ce_dice(logits, targets, class_weight, options=None):
+def fused_ce_dice(logits, targets, class_weight, options=None, ohem=None, record_to=None):
     """-> tensor [3] = (CE, Dice, number of valid Dice items); differentiable w.r.t. logits.  `options`: a LossOptions
-    (None = the defaults)."""
+    (None = the defaults).  `ohem`: an OhemOptions / (thresh, min_kept) pair, None = off; the selection's device record
+    (int32[4]: lam_k as fp32 bits, n_candidates, n_kept, reserved) is left in `record_to.last_ohem` when an object is given."""
     if logits.shape[1] != len(class_weight):
         raise ValueError(f"class_weight has {len(class_weight)} entries, logits have {logits.shape[1]} channels")
     options = None if options is None else LossOptions(*options).or_none()
-    return _FusedLoss.apply(logits, targets, _weights(class_weight, logits.device), options)
+    if ohem is not None:
+        ohem = OhemOptions(_ohem_thresh(ohem[0]), _ohem_min_kept(ohem[1]))
+    return _FusedLoss.apply(logits, targets, _weights(class_weight, logits.device), options, ohem, record_to)
 
 
 def global_batch_dice(res, group=None):
@@ -129,15 +174,30 @@ def _as_logits(outs, logits_input, log_domain):
 
 class CrossEntropyLoss(nn.Module):
     """Masked class-weighted CE; ``focal_gamma`` > 0 multiplies each pixel's term by (1 - p)^gamma (focal loss), 0 is the
-    reference's CE.  ``smooth`` is stored and never used, as in the reference (its CE has no smoothing term either)."""
+    reference's CE.  ``smooth`` is stored and never used, as in the reference (its CE has no smoothing term either).
+    ``ohem_thresh`` (None = off) switches online hard example mining on: the CE then runs over the pixels of the level's batch
+    whose true-class probability is below it, and over the ``ohem_min_kept`` hardest at least (OhemOptions).  ``last_ohem`` is
+    the device record of the latest selection (int32[4]: lam_k as fp32 bits, n_candidates, n_kept, reserved; None before the
+    first), written without a sync: ``kept_fraction()`` reads it."""
 
-    def __init__(self, smooth=0.0, focal_gamma=0.0):
+    def __init__(self, smooth=0.0, focal_gamma=0.0, ohem_thresh=None, ohem_min_kept=0):
         super().__init__()
         self.smooth = smooth
         self.focal_gamma = _option("focal_gamma", focal_gamma)
+        self.ohem_thresh = None if ohem_thresh is None else _ohem_thresh(ohem_thresh)
+        self.ohem_min_kept = _ohem_min_kept(ohem_min_kept)
+        self.last_ohem = None
+
+    def kept_fraction(self):
+        """n_kept / n_candidates of the latest selection (a host read: for logging), None when there is none"""
+        if self.last_ohem is None:
+            return None
+        _, n, kept, _ = self.last_ohem.tolist()
+        return kept / n if n else 0.0
 
     def forward(self, outs, targets, logits_input=False, class_weight=None):
-        return fused_ce_dice(_as_logits(outs, logits_input, True), targets, class_weight, LossOptions.from_pair(self, None))[0]
+        return fused_ce_dice(_as_logits(outs, logits_input, True), targets, class_weight, LossOptions.from_pair(self, None),
+                             ohem=OhemOptions.from_ce(self), record_to=self)[0]
 
 
 class SoftDiceLoss(nn.Module):

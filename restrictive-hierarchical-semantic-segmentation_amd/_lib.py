@@ -114,6 +114,10 @@ PROTOTYPES = {
     "hrseg_loss_partials_opt": [_p, _p, _p, _i, _i, _l, _f, _p],
     "hrseg_loss_finalize_opt": [_p, _p, _i, _i, _f, _f, _f, _p, _p, _p],
     "hrseg_loss_bwd_opt": [_p, _p, _p, _p, _p, _i, _i, _i, _l, _f, _p],
+    "hrseg_ohem_scores": [_p, _p, _p, _i, _i, _l, _p],
+    "hrseg_ohem_select": [_p, _l, _f, _l, _p, _p, _p],
+    "hrseg_loss_partials_ohem": [_p, _p, _p, _p, _f, _p, _i, _i, _l, _f, _p],
+    "hrseg_loss_bwd_ohem": [_p, _p, _p, _p, _f, _p, _p, _p, _i, _i, _i, _l, _f, _p],
     "hrseg_consistency": [_p, _p, _p, _i, _i, _i, _l, _i, _p, _p, _p],
     "hrseg_consistency_bwd": [_p, _p, _p, _f, _p, _p, _i, _i, _i, _l, _i, _p, _p, _p],
     "hrseg_group_kl": [_p, _p, _p, _i, _i, _i, _l, _i, _p, _p, _p],
@@ -156,6 +160,7 @@ RAW_PROTOTYPES = {
     "hrseg_grad_sumsq_chunk_len": [],
     "hrseg_grad_sumsq_max_blocks": [],
     "hrseg_grad_sumsq_chunks": [_l],
+    "hrseg_ohem_workspace_bytes": [],
 }
 
 _lib.hrseg_last_error_string.restype = C.c_char_p
@@ -340,6 +345,11 @@ def grad_sumsq_chunks(n) -> int:
     if k < 0:
         raise RuntimeError(f"hrseg_grad_sumsq_chunks failed ({k}): {last_error()}")
     return k
+
+
+def ohem_workspace_bytes() -> int:
+    """bytes of the workspace hrseg_ohem_select needs (a constant of the library)"""
+    return int(raw["hrseg_ohem_workspace_bytes"]())
 
 
 def ptr(t):

@@ -8,6 +8,7 @@
 
 #include "common.h"
 #include "level_common.h"
+#include "ohem.h"
 
 // launches KERNEL<CT> (256-thread blocks, no dynamic LDS) with the smallest CT of 4 / 8 / 16 that holds C channels
 #define LAUNCH_CT(KERNEL, C, grid, st, ...)                                                  \
@@ -17,12 +18,12 @@
     else hipLaunchKernelGGL((KERNEL<16>), grid, dim3(256), 0, st, __VA_ARGS__);              \
   } while (0)
 
-// the same ladder for kernels with a second template argument: KERNEL<CT, FLAG>
-#define LAUNCH_CT_FLAG(KERNEL, FLAG, C, grid, st, ...)                                             \
-  do {                                                                                             \
-    if ((C) <= 4) hipLaunchKernelGGL((KERNEL<4, FLAG>), grid, dim3(256), 0, st, __VA_ARGS__);      \
-    else if ((C) <= 8) hipLaunchKernelGGL((KERNEL<8, FLAG>), grid, dim3(256), 0, st, __VA_ARGS__); \
-    else hipLaunchKernelGGL((KERNEL<16, FLAG>), grid, dim3(256), 0, st, __VA_ARGS__);              \
+// the same ladder for kernels with two more template arguments: KERNEL<CT, FLAG, FLAG2>
+#define LAUNCH_CT_FLAGS(KERNEL, FLAG, FLAG2, C, grid, st, ...)                                            \
+  do {                                                                                                    \
+    if ((C) <= 4) hipLaunchKernelGGL((KERNEL<4, FLAG, FLAG2>), grid, dim3(256), 0, st, __VA_ARGS__);      \
+    else if ((C) <= 8) hipLaunchKernelGGL((KERNEL<8, FLAG, FLAG2>), grid, dim3(256), 0, st, __VA_ARGS__); \
+    else hipLaunchKernelGGL((KERNEL<16, FLAG, FLAG2>), grid, dim3(256), 0, st, __VA_ARGS__);              \
   } while (0)
 
 // --------------------------------------------------------------------------- loss
@@ -49,10 +50,14 @@ __global__ void zero_f64_kernel(double* p, int n) {
 }
 
 // per (b,c): {n, sum t logp, sum p t, sum p, sum t} over pixels with t != -1; FOCAL: sum t (1-p)^gamma logp in slot 1
-template <int CT, bool FOCAL>
+// OHEM (online hard example mining, ohem.h): slots 0 and 1 -- the CE's -- run over the pixels the selection kept, read from
+// the stored scores q[B*hw] and the record; the Dice slots 2..4 still run over every valid pixel.  The three arguments behind
+// gamma are read by the OHEM instances only.
+template <int CT, bool FOCAL, bool OHEM>
 __global__ __launch_bounds__(256) void loss_partials_kernel(const float* __restrict__ z, const float* __restrict__ t,
                                                             double* __restrict__ partial, int C, long hw,
-                                                            long pix_per_block, float gamma) {
+                                                            long pix_per_block, float gamma, const float* __restrict__ q,
+                                                            const OhemRecord* __restrict__ rec, float thresh) {
   __shared__ float red[4][CT * 5];
   const int b = blockIdx.y;
   const long lo = (long)blockIdx.x * pix_per_block;
@@ -64,7 +69,11 @@ __global__ __launch_bounds__(256) void loss_partials_kernel(const float* __restr
     for (int k = 0; k < 5; ++k) acc[c][k] = 0.f;
   const float* zb = z + (size_t)b * C * hw;
   const float* tb = t + (size_t)b * C * hw;
+  float lam_k = 0.f;
+  if constexpr (OHEM) lam_k = rec->lam_k;
   for (long pix = lo + threadIdx.x; pix < hi; pix += 256) {
+    bool kept = true;
+    if constexpr (OHEM) kept = ohem_kept(q[(size_t)b * hw + pix], thresh, lam_k);
     float zz[CT], tt[CT];
     float m = -INFINITY;
 #pragma unroll
@@ -90,16 +99,18 @@ __global__ __launch_bounds__(256) void loss_partials_kernel(const float* __restr
     for (int c = 0; c < CT; ++c) {
       if (c < C && tt[c] != -1.f) {
         const float logp = zz[c] - ls, p = expf(zz[c]) * inv;
-        acc[c][0] += 1.f;
-        if constexpr (FOCAL) {
-          if (tt[c] != 0.f) {
-            const float om = (pre + rest[c]) * inv;
-            acc[c][1] += tt[c] * focal_pow(om, gamma) * focal_logp(om, logp);
+        if (!OHEM || kept) {
+          acc[c][0] += 1.f;
+          if constexpr (FOCAL) {
+            if (tt[c] != 0.f) {
+              const float om = (pre + rest[c]) * inv;
+              acc[c][1] += tt[c] * focal_pow(om, gamma) * focal_logp(om, logp);
+            } else {
+              acc[c][1] += tt[c] * logp;      // 0, or the NaN of a poisoned pixel
+            }
           } else {
-            acc[c][1] += tt[c] * logp;      // 0, or the NaN of a poisoned pixel
+            acc[c][1] += tt[c] * logp;
           }
-        } else {
-          acc[c][1] += tt[c] * logp;
         }
         acc[c][2] += p * tt[c];
         acc[c][3] += p;
@@ -185,14 +196,20 @@ __global__ void loss_finalize_kernel(const double* __restrict__ partial, const f
 
 // FOCAL: d(-t (1-p)^gamma log p) / d log p = -t [(1-p)^gamma - gamma p (1-p)^(gamma-1) log p] replaces the CE's -t; the
 // softmax Jacobian behind it is the same.  The bracket is (1-p)^gamma (1 - gamma p log p / (1-p)), 0 in the limit 1-p -> 0.
-template <int CT, bool FOCAL>
+// OHEM: the selection is a constant, so the CE part of dz is simply 0 at the pixels it did not keep (the same stored scores
+// and record as the forward: the two cannot disagree); the Dice part is untouched.
+template <int CT, bool FOCAL, bool OHEM>
 __global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__ z, const float* __restrict__ t,
                                                        const float* __restrict__ coef, const float* __restrict__ g,
-                                                       float* __restrict__ dz, int acc, int C, long hw, float gamma) {
+                                                       float* __restrict__ dz, int acc, int C, long hw, float gamma,
+                                                       const float* __restrict__ q, const OhemRecord* __restrict__ rec,
+                                                       float thresh) {
   const int b = blockIdx.y;
   const long pix = (long)blockIdx.x * 256 + threadIdx.x;
   if (pix >= hw) return;
   const float gce = g[0], gdice = g[1];
+  bool kept = true;
+  if constexpr (OHEM) kept = ohem_kept(q[(size_t)b * hw + pix], thresh, rec->lam_k);
   const float* zb = z + (size_t)b * C * hw + pix;
   const float* tb = t + (size_t)b * C * hw + pix;
   float zz[CT], tt[CT], p[CT];
@@ -232,6 +249,8 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__
           dlogp[c] *= (om == 0.f) ? 0.f : focal_pow(om, gamma) * (1.f - gamma * p[c] * logp / om);
         }
       }
+      // (a select behind the arithmetic, not a branch around it: the branch cost the CT = 16 focal instance 408 bytes of scratch)
+      if (OHEM && !kept) dlogp[c] = 0.f;
       dpr[c] = gdice * (k[1] * tt[c] + k[2]);
     }
     if constexpr (FOCAL) pre += e;
@@ -251,10 +270,19 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__
 // called (a refusal names it).  An option must be finite and >= 0.
 static bool loss_option_ok(float v) { return v >= 0.f && v <= FLT_MAX; }
 
+// The _ohem entry points are the _opt ones with the stored scores, the selection's record and the threshold (`ohem` set): the
+// masked instances of the same kernels.
+struct OhemArgs { const float* q; const OhemRecord* rec; float thresh; };
+static const OhemArgs* const NO_OHEM = nullptr;
+
 static int loss_partials(const char* name, const float* z, const float* t, double* partial, int B, int C, long hw,
-                         float gamma, hrseg_stream_t stream) {
+                         float gamma, const OhemArgs* ohem, hrseg_stream_t stream) {
   HRSEG_CHECK_ARG(z && t && partial && B > 0 && C > 0 && C <= MAXC && hw > 0, "%s: bad arguments (C=%d)", name, C);
   HRSEG_CHECK_ARG(loss_option_ok(gamma), "%s: gamma must be finite and >= 0 (got %g)", name, (double)gamma);
+  if (ohem) {
+    HRSEG_CHECK_ARG(ohem->q && ohem->rec, "%s: null pointer (q, record)", name);
+    HRSEG_CHECK_ARG(ohem_thresh_ok(ohem->thresh), "%s: thresh must be a finite number in [0, 1] (got %g)", name, (double)ohem->thresh);
+  }
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(zero_f64_kernel, dim3(1), dim3(256), 0, st, partial, B * C * 5);   // kernel node, not memset
   long chunks = hrseg_g_deterministic ? 1 : 1024 / B;      // deterministic: one block (one adder) per image
@@ -262,8 +290,17 @@ static int loss_partials(const char* name, const float* z, const float* t, doubl
   long ppb = (hw + chunks - 1) / chunks;
   if (ppb < 256) ppb = 256;
   dim3 grid(ceil_div(hw, ppb), B);
-  if (gamma > 0.f) LAUNCH_CT_FLAG(loss_partials_kernel, true, C, grid, st, z, t, partial, C, hw, ppb, gamma);
-  else LAUNCH_CT_FLAG(loss_partials_kernel, false, C, grid, st, z, t, partial, C, hw, ppb, gamma);
+  const float* q = ohem ? ohem->q : nullptr;
+  const OhemRecord* rec = ohem ? ohem->rec : nullptr;
+  const float thresh = ohem ? ohem->thresh : 0.f;
+  if (ohem) {
+    if (gamma > 0.f) LAUNCH_CT_FLAGS(loss_partials_kernel, true, true, C, grid, st, z, t, partial, C, hw, ppb, gamma, q, rec, thresh);
+    else LAUNCH_CT_FLAGS(loss_partials_kernel, false, true, C, grid, st, z, t, partial, C, hw, ppb, gamma, q, rec, thresh);
+    hrseg_count(CNT_OHEM);
+  } else {
+    if (gamma > 0.f) LAUNCH_CT_FLAGS(loss_partials_kernel, true, false, C, grid, st, z, t, partial, C, hw, ppb, gamma, q, rec, thresh);
+    else LAUNCH_CT_FLAGS(loss_partials_kernel, false, false, C, grid, st, z, t, partial, C, hw, ppb, gamma, q, rec, thresh);
+  }
   HRSEG_LAUNCH_CHECK("loss_partials");
   return 0;
 }
@@ -281,24 +318,37 @@ static int loss_finalize(const char* name, const double* partial, const float* w
 }
 
 static int loss_bwd(const char* name, const float* z, const float* t, const float* coef, const float* g, float* dz,
-                    int accumulate, int B, int C, long hw, float gamma, hrseg_stream_t stream) {
+                    int accumulate, int B, int C, long hw, float gamma, const OhemArgs* ohem, hrseg_stream_t stream) {
   HRSEG_CHECK_ARG(z && t && coef && g && dz && B > 0 && C > 0 && C <= MAXC && hw > 0, "%s: bad arguments", name);
   HRSEG_CHECK_ARG(loss_option_ok(gamma), "%s: gamma must be finite and >= 0 (got %g)", name, (double)gamma);
+  if (ohem) {
+    HRSEG_CHECK_ARG(ohem->q && ohem->rec, "%s: null pointer (q, record)", name);
+    HRSEG_CHECK_ARG(ohem_thresh_ok(ohem->thresh), "%s: thresh must be a finite number in [0, 1] (got %g)", name, (double)ohem->thresh);
+  }
   hipStream_t st = (hipStream_t)stream;
   dim3 grid(ceil_div(hw, 256), B);
-  if (gamma > 0.f) LAUNCH_CT_FLAG(loss_bwd_kernel, true, C, grid, st, z, t, coef, g, dz, accumulate, C, hw, gamma);
-  else LAUNCH_CT_FLAG(loss_bwd_kernel, false, C, grid, st, z, t, coef, g, dz, accumulate, C, hw, gamma);
+  const float* q = ohem ? ohem->q : nullptr;
+  const OhemRecord* rec = ohem ? ohem->rec : nullptr;
+  const float thresh = ohem ? ohem->thresh : 0.f;
+  if (ohem) {
+    if (gamma > 0.f) LAUNCH_CT_FLAGS(loss_bwd_kernel, true, true, C, grid, st, z, t, coef, g, dz, accumulate, C, hw, gamma, q, rec, thresh);
+    else LAUNCH_CT_FLAGS(loss_bwd_kernel, false, true, C, grid, st, z, t, coef, g, dz, accumulate, C, hw, gamma, q, rec, thresh);
+    hrseg_count(CNT_OHEM);
+  } else {
+    if (gamma > 0.f) LAUNCH_CT_FLAGS(loss_bwd_kernel, true, false, C, grid, st, z, t, coef, g, dz, accumulate, C, hw, gamma, q, rec, thresh);
+    else LAUNCH_CT_FLAGS(loss_bwd_kernel, false, false, C, grid, st, z, t, coef, g, dz, accumulate, C, hw, gamma, q, rec, thresh);
+  }
   HRSEG_LAUNCH_CHECK("loss_bwd");
   return 0;
 }
 
 extern "C" int hrseg_loss_partials(const float* z, const float* t, double* partial, int B, int C, long hw,
                                    hrseg_stream_t stream) {
-  return loss_partials("hrseg_loss_partials", z, t, partial, B, C, hw, 0.f, stream);
+  return loss_partials("hrseg_loss_partials", z, t, partial, B, C, hw, 0.f, NO_OHEM, stream);
 }
 extern "C" int hrseg_loss_partials_opt(const float* z, const float* t, double* partial, int B, int C, long hw, float gamma,
                                        hrseg_stream_t stream) {
-  return loss_partials("hrseg_loss_partials_opt", z, t, partial, B, C, hw, gamma, stream);
+  return loss_partials("hrseg_loss_partials_opt", z, t, partial, B, C, hw, gamma, NO_OHEM, stream);
 }
 extern "C" int hrseg_loss_finalize(const double* partial, const float* w, int B, int C, float* out, float* coef,
                                    hrseg_stream_t stream) {
@@ -310,11 +360,22 @@ extern "C" int hrseg_loss_finalize_opt(const double* partial, const float* w, in
 }
 extern "C" int hrseg_loss_bwd(const float* z, const float* t, const float* coef, const float* g, float* dz,
                               int accumulate, int B, int C, long hw, hrseg_stream_t stream) {
-  return loss_bwd("hrseg_loss_bwd", z, t, coef, g, dz, accumulate, B, C, hw, 0.f, stream);
+  return loss_bwd("hrseg_loss_bwd", z, t, coef, g, dz, accumulate, B, C, hw, 0.f, NO_OHEM, stream);
 }
 extern "C" int hrseg_loss_bwd_opt(const float* z, const float* t, const float* coef, const float* g, float* dz,
                                   int accumulate, int B, int C, long hw, float gamma, hrseg_stream_t stream) {
-  return loss_bwd("hrseg_loss_bwd_opt", z, t, coef, g, dz, accumulate, B, C, hw, gamma, stream);
+  return loss_bwd("hrseg_loss_bwd_opt", z, t, coef, g, dz, accumulate, B, C, hw, gamma, NO_OHEM, stream);
+}
+extern "C" int hrseg_loss_partials_ohem(const float* z, const float* t, const float* q, const void* record, float thresh,
+                                        double* partial, int B, int C, long hw, float gamma, hrseg_stream_t stream) {
+  const OhemArgs ohem = {q, (const OhemRecord*)record, thresh};
+  return loss_partials("hrseg_loss_partials_ohem", z, t, partial, B, C, hw, gamma, &ohem, stream);
+}
+extern "C" int hrseg_loss_bwd_ohem(const float* z, const float* t, const float* q, const void* record, float thresh,
+                                   const float* coef, const float* g, float* dz, int accumulate, int B, int C, long hw,
+                                   float gamma, hrseg_stream_t stream) {
+  const OhemArgs ohem = {q, (const OhemRecord*)record, thresh};
+  return loss_bwd("hrseg_loss_bwd_ohem", z, t, coef, g, dz, accumulate, B, C, hw, gamma, &ohem, stream);
 }
 
 // --------------------------------------------------------------------------- predictions / confusion counts

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -1151,31 +1152,82 @@ def _c(t):
     return t if t.is_contiguous() else t.contiguous()
 
 
-def loss_fwd(z, t, w, options=None):
+class OhemState(NamedTuple):
+    """what loss_fwd leaves for loss_bwd when online hard example mining is on: the options it ran with, the stored scores
+    q[B*hw] and the selection's record (int32[4] on the device: lam_k as fp32 bits, n_candidates, n_kept, reserved)"""
+    thresh: float
+    min_kept: int
+    q: torch.Tensor
+    record: torch.Tensor
+
+    @property
+    def lam_k(self):
+        """0-dim device tensor (no sync)"""
+        return self.record[:1].view(torch.float32)[0]
+
+
+def ohem_scores(z, t, q=None):
+    """-> q[B*hw] fp32: per pixel the softmax probability mass on the valid channels' targets, sum_{t_c != -1} t_c p_c; -1 where
+    every channel is ignored (hrseg_ohem_scores)"""
+    z, t = _c(z), _c(t)
+    B, Cn, H, W = z.shape
+    if q is None:
+        q = torch.empty(B * H * W, dtype=torch.float32, device=z.device)
+    call("hrseg_ohem_scores", ptr(z), ptr(t), ptr(q), B, Cn, H * W)
+    return q
+
+
+def ohem_select(q, thresh, min_kept, record=None, workspace=None):
+    """-> record (int32[4], device): the exact min(min_kept, N)-th smallest candidate score of q and the counts that go with
+    it (hrseg_ohem_select; no sync, no sort).  `workspace`: _lib.ohem_workspace_bytes() bytes the call zeroes itself."""
+    if record is None:
+        record = torch.empty(4, dtype=torch.int32, device=q.device)
+    if workspace is None:
+        workspace = torch.empty(_lib.ohem_workspace_bytes() // 4, dtype=torch.int32, device=q.device)
+    call("hrseg_ohem_select", ptr(q), q.numel(), float(thresh), int(min_kept), ptr(workspace), ptr(record))
+    return record
+
+
+def loss_fwd(z, t, w, options=None, ohem=None):
     """-> (out[3] = ce, dice, n_valid_dice ; coef for the backward).  options = (focal gamma, Dice smooth, Tversky alpha,
-    beta) selects the hrseg_loss_*_opt entry points; None = the calls without options (gamma 0, smooth 0, alpha = beta = 0.5)"""
+    beta) selects the hrseg_loss_*_opt entry points; None = the calls without options (gamma 0, smooth 0, alpha = beta = 0.5).
+    ohem = (thresh, min_kept): online hard example mining on the CE term -- scores, selection, then the masked partials; the
+    return value gains a third entry, the OhemState loss_bwd needs.  None = exactly the calls above."""
     z, t = _c(z), _c(t)
     B, Cn, H, W = z.shape
     part = torch.empty(B * Cn * 5, dtype=torch.float64, device=z.device)
     out = torch.empty(3, dtype=torch.float32, device=z.device)
     coef = torch.empty(B * Cn * 4, dtype=torch.float32, device=z.device)
+    state = None
+    if ohem is not None:
+        thresh, min_kept = float(ohem[0]), int(ohem[1])
+        q = ohem_scores(z, t)
+        state = OhemState(thresh, min_kept, q, ohem_select(q, thresh, min_kept))
+        gamma = 0.0 if options is None else float(options[0])
+        call("hrseg_loss_partials_ohem", ptr(z), ptr(t), ptr(q), ptr(state.record), thresh, ptr(part), B, Cn, H * W, gamma)
     if options is None:
-        call("hrseg_loss_partials", ptr(z), ptr(t), ptr(part), B, Cn, H * W)
+        if ohem is None:
+            call("hrseg_loss_partials", ptr(z), ptr(t), ptr(part), B, Cn, H * W)
         call("hrseg_loss_finalize", ptr(part), ptr(w), B, Cn, ptr(out), ptr(coef))
     else:
         gamma, smooth, alpha, beta = (float(v) for v in options)
-        call("hrseg_loss_partials_opt", ptr(z), ptr(t), ptr(part), B, Cn, H * W, gamma)
+        if ohem is None:
+            call("hrseg_loss_partials_opt", ptr(z), ptr(t), ptr(part), B, Cn, H * W, gamma)
         call("hrseg_loss_finalize_opt", ptr(part), ptr(w), B, Cn, smooth, alpha, beta, ptr(out), ptr(coef))
-    return out, coef
+    return (out, coef) if ohem is None else (out, coef, state)
 
 
-def loss_bwd(z, t, coef, g, dz=None, accumulate=False, options=None):
-    """`options`: the ones loss_fwd produced `coef` with (the backward itself reads the focal gamma only)"""
+def loss_bwd(z, t, coef, g, dz=None, accumulate=False, options=None, ohem=None):
+    """`options`: the ones loss_fwd produced `coef` with (the backward itself reads the focal gamma only); `ohem`: the
+    OhemState that loss_fwd returned (the keep decision is read from its stored scores and record, never recomputed)"""
     z, t = _c(z), _c(t)
     B, Cn, H, W = z.shape
     if dz is None:
         dz, accumulate = torch.empty_like(z), False
-    if options is None:
+    if ohem is not None:
+        call("hrseg_loss_bwd_ohem", ptr(z), ptr(t), ptr(ohem.q), ptr(ohem.record), float(ohem.thresh), ptr(coef), ptr(g), ptr(dz),
+             int(accumulate), B, Cn, H * W, 0.0 if options is None else float(options[0]))
+    elif options is None:
         call("hrseg_loss_bwd", ptr(z), ptr(t), ptr(coef), ptr(g), ptr(dz), int(accumulate), B, Cn, H * W)
     else:
         call("hrseg_loss_bwd_opt", ptr(z), ptr(t), ptr(coef), ptr(g), ptr(dz), int(accumulate), B, Cn, H * W, float(options[0]))

@@ -442,7 +442,8 @@ def get_loss(output_logits, targets, lossFuncts, levelLoss, level_weights=None, 
         level_weight = None if level_weights is None else level_weights[L]
         ce_fn, dice_fn = lossFuncts[L][0], lossFuncts[L][1]
         if isinstance(ce_fn, losses.CrossEntropyLoss) and isinstance(dice_fn, losses.SoftDiceLoss):
-            res = losses.fused_ce_dice(output_logits[L], targets[L], level_weight, losses.LossOptions.from_pair(ce_fn, dice_fn))
+            res = losses.fused_ce_dice(output_logits[L], targets[L], level_weight, losses.LossOptions.from_pair(ce_fn, dice_fn),
+                                       ohem=losses.OhemOptions.from_ce(ce_fn), record_to=ce_fn)
             # Dice is 0 with zero gradient when no item is valid == the reference skipping None; under data
             # parallelism its divisor is the global count of valid items (losses.global_batch_dice)
             sync = (torch.is_grad_enabled() and res.requires_grad) if sync_dice is None else bool(sync_dice)
@@ -521,6 +522,10 @@ class GraphedTrainStep:
     gradient hook (multi-GPU): collectives stay outside the graph, see `train_step`."""
 
     def __init__(self, model, optimizer, lossFuncts, args, class_tree, data, target, warmup=2, epoch_num=1):
+        if any(losses.OhemOptions.from_ce(fns[0]) is not None for fns in lossFuncts
+               if isinstance(fns[0], losses.CrossEntropyLoss)):
+            raise NotImplementedError("GraphedTrainStep: online hard example mining (CrossEntropyLoss(ohem_thresh=...)) has not been "
+                                      "run inside a captured hipGraph; use the taped or the eager step")
         self.model, self.optimizer = model, optimizer
         self.x, self.t = data.clone(), target.clone()
         level_loss = []
@@ -600,6 +605,12 @@ class TapedTrainStep:
         self.w = [losses._weights(weights[L] if self.hier else weights[0], dev) for L in range(self.n_levels)]
         # the level's loss options go into the recorded calls by value: fixed for the life of the recording
         self.opts = [losses.LossOptions.from_pair(*lossFuncts[L][:2]).or_none() for L in range(self.n_levels)]
+        # so do its online-hard-example-mining options (None = off: the calls without it); the scores, the record and the
+        # selection's workspace of a level are buffers of the step like any other, allocated inside the pool by the recording
+        # run.  self.ohem[L] = the level's device record (int32[4]: lam_k as fp32 bits, n_candidates, n_kept, reserved)
+        self.ohem_opts = [losses.OhemOptions.from_ce(lossFuncts[L][0]) for L in range(self.n_levels)]
+        self.ohem = [None] * self.n_levels
+        self._ce_fns = [lossFuncts[L][0] for L in range(self.n_levels)]
         # d loss / d (ce, dice, n_valid) per level; the Dice entry carries the data-parallel divisor correction
         self.seed = [torch.tensor([1.0, 1.0, 0.0], dtype=torch.float32, device=dev) for _ in range(self.n_levels)]
         self._n_all = torch.zeros(self.n_levels, dtype=torch.float32, device=dev)
@@ -649,7 +660,7 @@ class TapedTrainStep:
             p.grad = None
         run = m._run(self.x, True)
         logits = run.logits
-        onehots, cms, outs, coefs = [], [], [], []
+        onehots, cms, outs, coefs, ohem = [], [], [], [], [None] * self.n_levels
         for L, (z, t) in enumerate(zip(logits, self.t_levels)):
             oh, cm = ops.predict_metrics(z, t, child=(L > 0), mask_pred=True)
             onehots.append(oh)
@@ -659,7 +670,11 @@ class TapedTrainStep:
                 outs.append(None)
                 coefs.append(None)
                 continue
-            o, c = ops.loss_fwd(z, t, self.w[L], self.opts[L])
+            if self.ohem_opts[L] is None:
+                o, c = ops.loss_fwd(z, t, self.w[L], self.opts[L])
+            else:
+                o, c, ohem[L] = ops.loss_fwd(z, t, self.w[L], self.opts[L], ohem=self.ohem_opts[L])
+                self.ohem[L] = self._ce_fns[L].last_ohem = ohem[L].record
             outs.append(o)
             coefs.append(c)
         cons = []
@@ -673,7 +688,7 @@ class TapedTrainStep:
             if len(live) != self.n_levels:
                 raise NotImplementedError("TapedTrainStep: level0_pretrain_epochs together with data parallelism")
             _lib.host_call(lambda: self._dice_sync(live))
-        dz = [ops.loss_bwd(z, t, coefs[L], self.seed[L], options=self.opts[L]) if outs[L] is not None else None
+        dz = [ops.loss_bwd(z, t, coefs[L], self.seed[L], options=self.opts[L], ohem=ohem[L]) if outs[L] is not None else None
               for L, (z, t) in enumerate(zip(logits, self.t_levels))]
         n_probs = len(run.probs)
         run.backward([None] * n_probs, dz)
@@ -791,7 +806,8 @@ def taped_step_for(model, optimizer, lossFuncts, args, class_tree, data, target,
            tuple(tuple(float(v) for v in w) for w in args.level_weights),
            bool(getattr(optimizer, "clip_path", False)),       # the path, not the threshold: that lives on the device
            bool(getattr(optimizer, "ema_path", False)),        # likewise: the decay is read from device memory
-           tuple(losses.LossOptions.from_pair(c, d) for c, d in lossFuncts))   # by value in the recorded loss calls
+           tuple(losses.LossOptions.from_pair(c, d) for c, d in lossFuncts),   # by value in the recorded loss calls
+           tuple(losses.OhemOptions.from_ce(c) for c, _ in lossFuncts))        # likewise: thresh and min_kept of every level
     cache = m.__dict__.setdefault("_hr_tapes", {})
     step = cache.get(key)
     if step is not None:
