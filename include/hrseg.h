@@ -805,6 +805,66 @@ int hrseg_score_labels(const unsigned char* pred, const long* pdesc, const unsig
                        const unsigned long long* path_lut, int nlevels, const int* C, long long* counts,
                        long long* ignored, int B, int per_image, hrseg_stream_t stream);
 
+/* ------------------------------------------------------------------ device post-processing (Data/postprocess.py; csrc/components.hip)
+ * The fourth stage: connected-component clean-up of label maps (hrseg_decode_*), on the device.  A batch is a packed uint8
+ * buffer `labels` with a DEVICE table desc [B][4] int64 (byte offset, H, W, 1) exactly as hrseg_score_labels reads it:
+ * image b is the dense row-major span [offset_b, offset_b + H_b * W_b); offsets are arbitrary bytes, gaps are allowed.
+ * desc_host is the HOST copy of the same table: the entry points size their grids and check their limits on it, the
+ * kernels read `desc`.  group: DEVICE table [256] of bytes, pixel value -> group id.
+ *
+ * hrseg_label_components.  A COMPONENT is a maximal 4- or 8-connected (connectivity) set of pixels OF ONE IMAGE with
+ * equal group[label].  Images never connect, however they lie in the buffer.  The FIRST pixel of a component is the one
+ * with the smallest row-major index y * W + x within its image.  roots and area are int32 buffers with the labels buffer's
+ * own indexing (element i belongs to byte i):
+ *   roots[offset + y * W + x] = row-major index of the first pixel of the pixel's component;
+ *   area [offset + y * W + x] = the component's pixel count where (y, x) is that first pixel, 0 at every other pixel.
+ * Elements outside every image span are not written; label bytes outside the spans are not read (rows are read through
+ * aligned 16-byte loads that lie inside the span, single bytes elsewhere).
+ * Method: union-find with the parent array in `roots`; a union links the larger root below the smaller, so parent[i] <= i
+ * at all times, every walk descends, and the root is the smallest index whatever order the atomics land in: the result
+ * is the same bytes in every run.  A block labels a tile of HRSEG_COMPONENTS_TILE_W x HRSEG_COMPONENTS_TILE_H pixels in
+ * LDS (hrseg_components_tile returns the two numbers), a second launch unites across tile borders, a third flattens and
+ * counts.  HRSEG_LABEL_COMPONENTS_LAUNCHES launches, counted under the family "label_components" (outside the NULL
+ * total); no workspace, no device allocation, no host read, no synchronisation.
+ * Refused with a message before anything is launched: NULL pointers; B outside 1..65535; connectivity not 4 or 8; roots or
+ * area not 4-byte aligned; a descriptor row with a negative offset, H < 1, W < 1 or channels != 1; H * W >= 2^31.
+ *
+ * hrseg_filter_components.  roots / area: what hrseg_label_components wrote for the same labels, desc and group.
+ * rules: DEVICE table of 256 hrseg_component_rule_t, one per group id.  A component of group g != 255 is REMOVED when
+ *   area < rules[g].min_area, or
+ *   rules[g].keep_largest != 0 and it is not the largest component of group g in its image (equal areas: the one whose
+ *   first pixel has the smaller index is the largest).
+ * Every pixel of a removed component is written to out as the fill value: rules[g].fill in 0..255, or for fill < 0 the
+ * INPUT label of the west neighbour of the component's first pixel; of its north neighbour when the first pixel lies in
+ * column 0; and when the first pixel is the image's origin the component stays as it is and does not count as removed.
+ * (That neighbour is of another group: a west or north neighbour of the same group would belong to the component and
+ * come first.  It is read from `labels`, so a neighbour that is removed itself does not cascade.)  All other pixels are
+ * copied; group 255 has no rule and is always copied.  out has the layout of labels; bytes outside the spans are not
+ * written; out must not overlap labels (the spans' extent from the buffers' starts).
+ * stats: DEVICE int64 [B][256][3], += (the caller zeroes it): per image and group the components found, the components
+ * removed, the pixels of removed components.  workspace: hrseg_filter_components_workspace_bytes(B) bytes, 8-byte
+ * aligned; the call initialises it.  HRSEG_FILTER_COMPONENTS_LAUNCHES launches (clearing the workspace, the
+ * per-group maximum, the filter), family "filter_components", outside the NULL total; no host read, no synchronisation.
+ * Refused before anything is launched: NULL pointers; B outside 1..65535; roots, area or rules not 4-byte, stats or
+ * workspace not 8-byte aligned; the descriptor rules above; out overlapping labels. */
+#define HRSEG_COMPONENTS_TILE_W 64
+#define HRSEG_COMPONENTS_TILE_H 32
+#define HRSEG_LABEL_COMPONENTS_LAUNCHES 3
+#define HRSEG_FILTER_COMPONENTS_LAUNCHES 3
+typedef struct {
+  int min_area;      /* components with fewer pixels are removed */
+  int keep_largest;  /* != 0: all but the largest component of the group are removed */
+  int fill;          /* 0..255, or < 0: the neighbour rule */
+} hrseg_component_rule_t;
+int hrseg_components_tile(int* w, int* h);
+size_t hrseg_filter_components_workspace_bytes(int B);
+int hrseg_label_components(const unsigned char* labels, const long* desc, const long* desc_host, int B,
+                           const unsigned char* group, int connectivity, int* roots, int* area, hrseg_stream_t stream);
+int hrseg_filter_components(const unsigned char* labels, const long* desc, const long* desc_host, int B,
+                            const unsigned char* group, const hrseg_component_rule_t* rules, const int* roots,
+                            const int* area, unsigned char* out, long long* stats, void* workspace,
+                            hrseg_stream_t stream);
+
 /* ------------------------------------------------------------------ level synthesis for flat models (evaluation side; csrc/targets.hip)
  * predictEval.py:85-129 get_parent_masks (parent = union of its descendant leaves, "any > 0") and :134-185
  * combine_levels (per-level tensors stitched from leaf and parent channels).  out[b][o] is the COPY of the single

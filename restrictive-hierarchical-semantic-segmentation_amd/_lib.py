@@ -144,6 +144,8 @@ PROTOTYPES = {
     "hrseg_window_crops": [_p, _p, _p, _p, _p, _i, _i, _i, _p],
     "hrseg_decode_windows": [_i, _p, C.POINTER(C.c_int), C.POINTER(DecodeTree), _p, _p, _p, _p, _p, _p, _i, _i, _i, _p],
     "hrseg_score_labels": [_p, _p, _p, _p, _p, _i, C.POINTER(C.c_int), _p, _p, _i, _i, _p],
+    "hrseg_label_components": [_p, _p, _p, _i, _p, _i, _p, _p, _p],
+    "hrseg_filter_components": [_p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p],
     "hrseg_combine_levels": [_p, _i, _p, _i, _p, _p, _p, _i, _i, _l, _p],
     "hrseg_weight_images_refresh": [_p],
 }
@@ -161,6 +163,8 @@ RAW_PROTOTYPES = {
     "hrseg_grad_sumsq_max_blocks": [],
     "hrseg_grad_sumsq_chunks": [_l],
     "hrseg_ohem_workspace_bytes": [],
+    "hrseg_components_tile": [C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "hrseg_filter_components_workspace_bytes": [_i],
 }
 
 _lib.hrseg_last_error_string.restype = C.c_char_p
@@ -240,7 +244,7 @@ def launch_count(family=None, reset=False) -> int:
     """launches issued so far by kernel family (hrseg_launch_count; None = all convolution families; the input
     pipeline counts under "augment_image" / "augment_targets", the output pipeline under "decode_labels", the scoring
     pipeline under "score_labels", test-time augmentation under "decode_views" / "flip_views", sliding-window inference
-    under "window_crops" / "decode_windows")"""
+    under "window_crops" / "decode_windows", the post-processing under "label_components" / "filter_components")"""
     return int(_lib.hrseg_launch_count(None if family is None else family.encode(), int(reset)))
 
 
@@ -350,6 +354,21 @@ def grad_sumsq_chunks(n) -> int:
 def ohem_workspace_bytes() -> int:
     """bytes of the workspace hrseg_ohem_select needs (a constant of the library)"""
     return int(raw["hrseg_ohem_workspace_bytes"]())
+
+
+raw["hrseg_filter_components_workspace_bytes"].restype = C.c_size_t
+
+
+def components_tile():
+    """(width, height) of the tile a block of hrseg_label_components labels in LDS (a constant of the library)"""
+    w, h = C.c_int(0), C.c_int(0)
+    call_raw("hrseg_components_tile", C.byref(w), C.byref(h))
+    return int(w.value), int(h.value)
+
+
+def filter_components_workspace_bytes(B) -> int:
+    """bytes of the workspace hrseg_filter_components needs for B images"""
+    return int(raw["hrseg_filter_components_workspace_bytes"](int(B)))
 
 
 def ptr(t):

@@ -950,6 +950,72 @@ def score_labels(pred, pdesc, pdesc_host, gt, gdesc, gdesc_host, tables, out=Non
     return counts, ignored
 
 
+COMPONENTS_MAX_PIXELS = (1 << 31) - 1
+LABEL_COMPONENTS_LAUNCHES, FILTER_COMPONENTS_LAUNCHES = 3, 3
+
+
+def components_tile():
+    """(width, height) of the tile one block of label_components labels in LDS"""
+    return _lib.components_tile()
+
+
+def _check_components(who, labels, desc, desc_host, group, connectivity=8):
+    _check_ragged(labels, desc, desc_host, (1,))
+    if desc_host.is_cuda or desc_host.dtype != torch.int64 or not desc_host.is_contiguous() or desc_host.shape[0] < 1:
+        raise ValueError(f"{who}: desc_host must be a contiguous int64 host table with at least one row")
+    for b, (_, H, W, _) in enumerate(desc_host.tolist()):
+        if H * W > COMPONENTS_MAX_PIXELS:
+            raise ValueError(f"{who}: image {b}: {H}x{W} has 2^31 pixels or more")
+    if connectivity not in (4, 8):
+        raise ValueError(f"{who}: connectivity {connectivity}, supported 4 and 8")
+    if group.dtype != torch.uint8 or group.numel() != 256 or group.device != labels.device or not group.is_contiguous():
+        raise ValueError(f"{who}: group must be a contiguous uint8 table of 256 entries on the labels' device")
+
+
+def label_components(labels, desc, desc_host, group, connectivity=8, out=None):
+    """packed uint8 label maps + [B,4] int64 descriptors (device, and the host copy) + group [256] uint8 (device) ->
+    (roots, area), int32 tensors with the labels buffer's own indexing, as hrseg_label_components states them; elements
+    outside the image spans are left as they are (out = (roots, area)) or uninitialised.  3 launches, no synchronisation."""
+    _check_components("label_components", labels, desc, desc_host, group, connectivity)
+    if out is None:
+        roots = torch.empty(labels.numel(), dtype=torch.int32, device=labels.device)
+        area = torch.empty(labels.numel(), dtype=torch.int32, device=labels.device)
+    else:
+        roots, area = out
+        for t in (roots, area):
+            if t.dtype != torch.int32 or t.device != labels.device or t.numel() != labels.numel() or not t.is_contiguous():
+                raise ValueError("label_components: out must hold contiguous int32 device tensors of the labels' length")
+    call("hrseg_label_components", ptr(labels), ptr(desc), desc_host.data_ptr(), desc_host.shape[0], ptr(group), int(connectivity),
+         ptr(roots), ptr(area))
+    return roots, area
+
+
+def filter_components(labels, desc, desc_host, group, rules, roots, area, out=None, stats=None):
+    """the filter of hrseg_filter_components on what label_components returned for the same maps: rules [256,3] int32
+    (device; min_area, keep_largest, fill or -1) -> (out, stats): the cleaned maps in the layout of labels (bytes outside
+    the spans: as they were in `out`, else uninitialised) and int64 [B,256,3] (found, removed, pixels), added to when given.
+    3 launches (+ one fill launch when stats is allocated here), no synchronisation."""
+    _check_components("filter_components", labels, desc, desc_host, group)
+    B, dev = desc_host.shape[0], labels.device
+    if rules.dtype != torch.int32 or tuple(rules.shape) != (256, 3) or rules.device != dev or not rules.is_contiguous():
+        raise ValueError("filter_components: rules must be a contiguous int32 [256,3] table on the labels' device")
+    for t in (roots, area):
+        if t.dtype != torch.int32 or t.device != dev or t.numel() != labels.numel() or not t.is_contiguous():
+            raise ValueError("filter_components: roots and area must be contiguous int32 device tensors of the labels' length")
+    if out is None:
+        out = torch.empty(labels.numel(), dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or out.device != dev or out.numel() != labels.numel() or not out.is_contiguous():
+        raise ValueError("filter_components: out must be a contiguous uint8 device tensor of the labels' length")
+    if stats is None:
+        stats = zeros((B, 256, 3), torch.int64, dev)
+    elif stats.dtype != torch.int64 or stats.device != dev or tuple(stats.shape) != (B, 256, 3) or not stats.is_contiguous():
+        raise ValueError(f"filter_components: stats must be a contiguous int64 device tensor of shape {(B, 256, 3)}")
+    work = torch.empty(_lib.filter_components_workspace_bytes(B) // 8, dtype=torch.int64, device=dev)
+    call("hrseg_filter_components", ptr(labels), ptr(desc), desc_host.data_ptr(), B, ptr(group), ptr(rules), ptr(roots), ptr(area),
+         ptr(out), ptr(stats), ptr(work))
+    return out, stats
+
+
 def combine_levels(x0, x1, masks, is_union):
     """x0 [B,C0,H,W] (+ x1 [B,C1,H,W] or None), per output channel a bit mask over the C0+C1 input channels and a
     union flag -> [B,len(masks),H,W]: copy of the selected channel, or 1.0 where any selected channel is > 0"""

@@ -268,9 +268,14 @@ class Predictor:
     through eval-mode forwards of `window_batch` windows at a time (the last chunk shorter; eval-mode BatchNorm: windows do
     not interact) and their per-level logits, gathered into [N,C_L,S,S], are blended and decoded by ONE
     Data.DeviceDecode.decode_windows launch at the sizes asked for; keep_logits=True then keeps `last_window_logits` =
-    (logits, plan).  window=None: exactly the calls described above.  window together with tta is refused."""
+    (logits, plan).  window=None: exactly the calls described above.  window together with tta is refused.
+    postprocess=Data.DevicePostprocess(...): the connected-component clean-up (Data/postprocess.py) of the decoded maps,
+    behind whichever of the three decodes ran: the call returns the cleaned maps and `score` scores them.  Its min_area
+    counts pixels of the map being produced -- the source's size in a call, the ground truth's size in `score` -- not
+    pixels at network size.  postprocess=None: exactly the calls described above, no launch and no allocation more."""
 
-    def __init__(self, model, class_tree, class_map, args, want_confidence=False, keep_logits=False, tta=None, window=None):
+    def __init__(self, model, class_tree, class_map, args, want_confidence=False, keep_logits=False, tta=None, window=None,
+                 postprocess=None):
         from .Data.decode import DeviceDecode
         self.model, self.class_tree, self.class_map, self.args = model, class_tree, class_map, args
         self.scorer, self.last_labels = None, None
@@ -282,6 +287,7 @@ class Predictor:
         self.tta, self.last_view_logits = tta, None
         if tta is not None:
             tta.views(self.size)                    # refuses sizes the decode cannot take before any image is seen
+        self.postprocess = postprocess
         self.window, self.last_window_logits = window, None
         if window is not None:
             if tta is not None:
@@ -356,13 +362,15 @@ class Predictor:
         ldesc = label_desc([(H, W) for _, H, W, _ in desc_host.tolist()] if sizes is None else sizes)
         if self.window is not None:
             self.last_window_logits = (output_logits, plan) if self.keep_logits else None
-            return self.decoder.decode_windows(output_logits, plan, self.window_profile, ldesc, None, self.want_confidence)
-        if self.tta is not None:
+            maps = self.decoder.decode_windows(output_logits, plan, self.window_profile, ldesc, None, self.want_confidence)
+        elif self.tta is not None:
             self.last_view_logits = views if self.keep_logits else None
-            return self.decoder.decode_views(views, ldesc, None, self.want_confidence)
-        if self.keep_logits:
-            self.last_logits = output_logits
-        return self.decoder.decode(output_logits, ldesc, None, self.want_confidence)
+            maps = self.decoder.decode_views(views, ldesc, None, self.want_confidence)
+        else:
+            if self.keep_logits:
+                self.last_logits = output_logits
+            maps = self.decoder.decode(output_logits, ldesc, None, self.want_confidence)
+        return maps if self.postprocess is None else self.postprocess.apply(maps)
 
 
 def write_metrics_csv(path, accuracy, iou, dice, precision, recall, class_metrics):
@@ -379,7 +387,7 @@ def write_metrics_csv(path, accuracy, iou, dice, precision, recall, class_metric
 
 @torch.no_grad()
 def predict_loop(model, device, test_loader, args, class_tree, Accuracy, Iou, perf_measure, Precision, Recall,
-                 save_dir=None, target_paths=None, label_dir=None, class_map=None, score_sources=False):
+                 save_dir=None, target_paths=None, label_dir=None, class_map=None, score_sources=False, postprocess=None):
     """The per-fold body of the reference's predict() (predictEval.py:305-573) on a built model and loader: eval-mode
     forward, prediction_prep, get_metrics per batch, optional PNG dump of each batch's first image and metrics.csv.
     -> dict(accuracy, iou, dice, precision, recall, class_metrics, performance).
@@ -392,7 +400,9 @@ def predict_loop(model, device, test_loader, args, class_tree, Accuracy, Iou, pe
     agree).  The result gains the key "source": dict(names per tree node in breadth-first order, per_image {metric: one
     list over the nodes per image}, total {metric: list over the nodes, from the counts summed over the dataset}, ignored
     [unlabelled ground truth, predictions outside the class map] per image), and save_dir gets metrics_source.csv (the
-    dataset totals, one row per node).  Everything else is returned and written as without it."""
+    dataset totals, one row per node).  Everything else is returned and written as without it.
+    postprocess (a Data.DevicePostprocess; with label_dir or score_sources): every decoded source-size map goes through the
+    connected-component clean-up before it is written or scored, as in Predictor(postprocess=...)."""
     import os
     import numpy as np
     from . import train as T
@@ -435,6 +445,8 @@ def predict_loop(model, device, test_loader, args, class_tree, Accuracy, Iou, pe
             names = [os.path.basename(target_paths[n_images + j]) if target_paths is not None else f"{n_images + j:05d}.png"
                      for j in range(len(sizes))]
             decoded = decoder.decode(output_logits, label_desc(sizes))
+            if postprocess is not None:
+                decoded = postprocess.apply(decoded)
             save_label_maps(label_dir, names, decoded)
             n_images += len(sizes)
         if scorer is not None:
@@ -444,6 +456,8 @@ def predict_loop(model, device, test_loader, args, class_tree, Accuracy, Iou, pe
             gt_sizes = [(H, W) for _, H, W, _ in batch[2].ldesc_host.tolist()]
             if decoder is None or gt_sizes != sizes:
                 decoded = source_decoder.decode(output_logits, label_desc(gt_sizes))
+                if postprocess is not None:
+                    decoded = postprocess.apply(decoded)
             scored.append(scorer.score(decoded, batch[2]))
     if save_dir is not None:
         os.makedirs(save_dir, exist_ok=True)
