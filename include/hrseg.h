@@ -175,8 +175,9 @@ int hrseg_conv_wgrad_group_ws(int n, const float* const* x, const float* const* 
  * hrseg_decode_labels call) and "score_labels" (the scoring pipeline, 1 launch per hrseg_score_labels call), "decode_views"
  * and "flip_views" (test-time augmentation, 1 launch per hrseg_decode_views / hrseg_flip_views call), "window_crops" and
  * "decode_windows" (sliding-window inference, 1 launch per hrseg_window_crops / hrseg_decode_windows call) and "ohem" (online hard
- * example mining: 1 launch per hrseg_ohem_scores, 7 per hrseg_ohem_select, 1 per hrseg_loss_partials_ohem / hrseg_loss_bwd_ohem call)
- * are families of their own, outside the NULL total and the convolution counts. */
+ * example mining: 1 launch per hrseg_ohem_scores, 7 per hrseg_ohem_select, 1 per hrseg_loss_partials_ohem / hrseg_loss_bwd_ohem call),
+ * "label_components" / "filter_components" (post-processing) and "score_boundaries" (boundary scoring, HRSEG_SCORE_BOUNDARIES_LAUNCHES
+ * per hrseg_score_boundaries call) are families of their own, outside the NULL total and the convolution counts. */
 long hrseg_launch_count(const char* family, int reset);
 /* tile-plan overrides and A/B switches for the sweep tools under tools/ (value 0 = automatic plan).  Keys: igemm_wtm,
  * igemm_kc, igemm_db, igemm_ksplit, group_wtm, wgrad_pix, wgrad_db, wgrad_blocks, wgrad_group_mult,
@@ -864,6 +865,71 @@ int hrseg_filter_components(const unsigned char* labels, const long* desc, const
                             const unsigned char* group, const hrseg_component_rule_t* rules, const int* roots,
                             const int* area, unsigned char* out, long long* stats, void* workspace,
                             hrseg_stream_t stream);
+
+/* ------------------------------------------------------------------ device boundary scoring (Data/boundary.py; csrc/boundary.hip)
+ * The fifth, optional stage: how far the predicted outline of every tree node lies from the true one.  Label maps and
+ * ground-truth maps at the source's own size, both in the pixel values of class_map.csv, in the packed-buffer + [B][4]
+ * descriptor form of hrseg_score_labels and hrseg_label_components -> per image and tree node the integer records from which
+ * the Hausdorff distance, its percentile, the average symmetric surface distance and the surface Dice follow.  No map
+ * leaves the device; no host read, no synchronisation, no device allocation.
+ *
+ * Nodes: all nodes of the class tree in breadth-first order (the order of the metric vectors), node = sum_{l<L} C[l] + c for
+ * channel c of level L, N = sum C[L].  Limits as for hrseg_score_labels: nlevels <= 8, C[L] <= 16, N <= 64.  path_lut is the
+ * table of hrseg_score_labels (byte L of entry v = 1 + channel of the level-L node of the leaf with pixel value v, 0 below
+ * the leaf; an entry that breaks the rules stated there counts as 0).
+ * Validity: a pixel whose ground truth is no leaf's value belongs to no node IN EITHER MAP (hrseg_score_labels counts
+ * nothing there either); a predicted value outside the class map belongs to no predicted node.
+ * Masks: the mask of node n at level L in a map is the set of valid pixels whose path has n in byte L.  There is NO
+ * restrictive masking -- on purpose unlike hrseg_score_labels, where a prediction competes at level L only where it agreed
+ * with the truth above: an outline is a property of one map.
+ * Border pixels: a pixel of a mask is a border pixel when one of its FOUR neighbours is outside the mask; the outside of the
+ * image counts as outside the mask.  P_n: the border pixels of node n in the prediction, G_n: in the ground truth.
+ * Distance: for x in P_n, d2(x) = min over y in G_n of (dy^2 + dx^2), an exact integer; the other direction likewise.
+ * H, W <= HRSEG_BOUNDARY_MAX_SIDE = 32768 keeps d2 < 2^31 (and H*W < 2^31 as elsewhere); larger maps are refused, and a
+ * sample whose DEVICE descriptors break a rule, or whose two tables disagree on a size, is skipped by the kernels.
+ *
+ * records: DEVICE int64 [B][N][2][5], WRITTEN (not accumulated).  Direction 0: prediction -> truth (the pixels of P_n query
+ * G_n), direction 1: truth -> prediction.  Fields:
+ *   0 n        border pixels of the querying set;
+ *   1 sum_q16  sum over those pixels of floor(sqrt(d2 << 32)): the distance in 16.16 fixed point, floored (Python:
+ *              math.isqrt(d2 << 32)).  Integer, so the sum is exact whatever order the atomics land in; on the device a
+ *              floating-point root is only the first guess, corrected with integer multiplies;
+ *   2 max_d2   the largest d2;
+ *   3 within   pixels with d2 <= tau2; the caller computes tau2 = floor(tolerance^2);
+ *   4 pk_d2    the k-th smallest d2, k = ceil(percentile * n / 100) = (percentile * n + 99) / 100 in integers: the
+ *              NEAREST-RANK percentile, no interpolation, per direction.
+ * When n is 0 in EITHER direction (the node is absent from one map or from both) every field but the two n is 0.
+ * The usual figures follow (Data/boundary.py derives them, NaN where either n is 0):
+ *   hausdorff = sqrt(max(max_d2[0], max_d2[1])),  hd_percentile = sqrt(max(pk_d2[0], pk_d2[1])),
+ *   assd = (sum_q16[0] + sum_q16[1]) / 65536 / (n[0] + n[1]),  surface_dice = (within[0] + within[1]) / (n[0] + n[1]).
+ * DELIBERATE CONVENTION: hd_percentile is the larger of the two directions' nearest-rank percentiles.  Some libraries take
+ * numpy's linearly interpolated percentile of the two directions' distances concatenated instead; the two differ by up to
+ * the gap between neighbouring order statistics, and where the two sets have very different sizes.
+ *
+ * desc_host: HOST table [2][B][4]: the host copy of pdesc's B rows followed by that of gdesc's; the entry point sizes its
+ * grids and checks its limits on it, the kernels read pdesc / gdesc.  C is a HOST array.
+ * workspace: hrseg_boundary_workspace_bytes(desc_host, B, nlevels, C) bytes (it reads the first B rows; 0 with a message
+ * when an argument is refused), 8-byte aligned, DEVICE; the call's own first launch initialises what it needs of it, so a
+ * dirty workspace may be reused.  In bytes: 16 B + 4 * (B * 2 N * HRSEG_BOUNDARY_SEGMENT_WORDS + bitmaps + maps), bitmaps =
+ * sum_b 2 N H_b ceil(W_b / 32) rounded up to an even number, maps = sum_b 2 nlevels H_b W_b: one border bitmap per
+ * (node, map) with rows padded to 32-bit words (tail bits stay 0), one int32 d2 map per (level, direction), and 256 radix
+ * bins per (image, node, direction).
+ * Method (csrc/boundary.hip): mark the border bitmaps of all nodes in one pass over both maps; every border pixel searches
+ * the other map's bitmap of its own node -- the 7 rows around it first, which decides every d2 <= 16, else row by row outwards
+ * with a whole wave on the query until the vertical offset alone exceeds the best distance; the k-th smallest per (image, node, direction) by four 8-bit radix passes over the d2 maps.  Reads never
+ * leave [offset, offset + H*W) of either buffer.  HRSEG_SCORE_BOUNDARIES_LAUNCHES launches, family "score_boundaries",
+ * outside the NULL total.  All arithmetic is integer: the same bytes in every run, whatever the "deterministic" knob says.
+ * Refused with a message before anything is launched: NULL pointers; B outside 1..65535; records, workspace or path_lut
+ * not 8-byte aligned; percentile outside 1..100; tau2 < 0; nlevels / C outside the limits; a descriptor row (of either
+ * table) with a negative offset, H < 1, W < 1 or channels != 1, H * W >= 2^31 or a side above 32768; the two tables
+ * disagreeing on a size. */
+#define HRSEG_SCORE_BOUNDARIES_LAUNCHES 11
+#define HRSEG_BOUNDARY_MAX_SIDE 32768
+#define HRSEG_BOUNDARY_SEGMENT_WORDS 260
+size_t hrseg_boundary_workspace_bytes(const long* desc_host, int B, int nlevels, const int* C);
+int hrseg_score_boundaries(const unsigned char* pred, const long* pdesc, const unsigned char* gt, const long* gdesc,
+                           const long* desc_host, const unsigned long long* path_lut, int nlevels, const int* C, long tau2,
+                           int percentile, long long* records, void* workspace, int B, hrseg_stream_t stream);
 
 /* ------------------------------------------------------------------ level synthesis for flat models (evaluation side; csrc/targets.hip)
  * predictEval.py:85-129 get_parent_masks (parent = union of its descendant leaves, "any > 0") and :134-185

@@ -4,3 +4,4 @@ from .augment import DeviceAugment  # noqa: F401
 from .decode import DeviceDecode, RaggedLabels, WindowPlan, plan_windows, window_profile  # noqa: F401
 from .score import DeviceScore, SourceScores, build_score_tables  # noqa: F401
 from .postprocess import ComponentTables, DevicePostprocess, build_component_tables  # noqa: F401
+from .boundary import BoundaryScores, DeviceBoundaryScore  # noqa: F401

@@ -146,6 +146,7 @@ PROTOTYPES = {
     "hrseg_score_labels": [_p, _p, _p, _p, _p, _i, C.POINTER(C.c_int), _p, _p, _i, _i, _p],
     "hrseg_label_components": [_p, _p, _p, _i, _p, _i, _p, _p, _p],
     "hrseg_filter_components": [_p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p],
+    "hrseg_score_boundaries": [_p, _p, _p, _p, _p, _p, _i, C.POINTER(C.c_int), _l, _i, _p, _p, _i, _p],
     "hrseg_combine_levels": [_p, _i, _p, _i, _p, _p, _p, _i, _i, _l, _p],
     "hrseg_weight_images_refresh": [_p],
 }
@@ -165,6 +166,7 @@ RAW_PROTOTYPES = {
     "hrseg_ohem_workspace_bytes": [],
     "hrseg_components_tile": [C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "hrseg_filter_components_workspace_bytes": [_i],
+    "hrseg_boundary_workspace_bytes": [_p, _i, _i, C.POINTER(C.c_int)],
 }
 
 _lib.hrseg_last_error_string.restype = C.c_char_p
@@ -244,7 +246,8 @@ def launch_count(family=None, reset=False) -> int:
     """launches issued so far by kernel family (hrseg_launch_count; None = all convolution families; the input
     pipeline counts under "augment_image" / "augment_targets", the output pipeline under "decode_labels", the scoring
     pipeline under "score_labels", test-time augmentation under "decode_views" / "flip_views", sliding-window inference
-    under "window_crops" / "decode_windows", the post-processing under "label_components" / "filter_components")"""
+    under "window_crops" / "decode_windows", the post-processing under "label_components" / "filter_components", the
+    boundary scoring under "score_boundaries")"""
     return int(_lib.hrseg_launch_count(None if family is None else family.encode(), int(reset)))
 
 
@@ -369,6 +372,18 @@ def components_tile():
 def filter_components_workspace_bytes(B) -> int:
     """bytes of the workspace hrseg_filter_components needs for B images"""
     return int(raw["hrseg_filter_components_workspace_bytes"](int(B)))
+
+
+raw["hrseg_boundary_workspace_bytes"].restype = C.c_size_t
+
+
+def boundary_workspace_bytes(desc_host_ptr, B, Cs) -> int:
+    """bytes of the workspace hrseg_score_boundaries needs for the B images of a host descriptor table (its address)
+    and the channels per level `Cs`; RuntimeError when the library refuses an argument"""
+    n = int(raw["hrseg_boundary_workspace_bytes"](desc_host_ptr, int(B), len(Cs), int_array(list(Cs))))
+    if n == 0:
+        raise RuntimeError(f"hrseg_boundary_workspace_bytes failed: {last_error()}")
+    return n
 
 
 def ptr(t):

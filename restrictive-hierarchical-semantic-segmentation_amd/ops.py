@@ -1016,6 +1016,66 @@ def filter_components(labels, desc, desc_host, group, rules, roots, area, out=No
     return out, stats
 
 
+SCORE_BOUNDARIES_LAUNCHES = 11
+BOUNDARY_MAX_SIDE = 32768
+BOUNDARY_FIELDS = ("n", "sum_q16", "max_d2", "within", "pk_d2")
+
+
+def _boundary_host_table(who, pred, pdesc, pdesc_host, gt, gdesc, gdesc_host):
+    """the checks of score_labels on the two descriptor tables + the limits of hrseg_score_boundaries -> the [2B,4] host table"""
+    _check_ragged(pred, pdesc, pdesc_host, (1,))
+    _check_ragged(gt, gdesc, gdesc_host, (1,))
+    prow, grow = pdesc_host.tolist(), gdesc_host.tolist()
+    if len(prow) != len(grow) or not prow:
+        raise ValueError(f"{who}: {len(prow)} predicted maps against {len(grow)} ground-truth maps")
+    for b, ((_, H, W, _), (_, gH, gW, _)) in enumerate(zip(prow, grow)):
+        if (H, W) != (gH, gW):
+            raise ValueError(f"{who}: sample {b}: predicted map {H}x{W}, ground truth {gH}x{gW}")
+        if H > BOUNDARY_MAX_SIDE or W > BOUNDARY_MAX_SIDE:
+            raise ValueError(f"{who}: sample {b}: {H}x{W}, a side above {BOUNDARY_MAX_SIDE}")
+    if gt.device != pred.device:
+        raise ValueError(f"{who}: the two buffers live on different devices")
+    return torch.cat([pdesc_host.to(torch.int64), gdesc_host.to(torch.int64)]).contiguous()
+
+
+def boundary_workspace_bytes(desc_host, tables):
+    """bytes of the workspace score_boundaries needs for the images of a [B,4] int64 host descriptor table (needs no GPU)"""
+    check_score_tables(tables)
+    if desc_host.is_cuda or desc_host.dtype != torch.int64 or desc_host.dim() != 2 or desc_host.shape[1] != 4 or desc_host.shape[0] < 1:
+        raise ValueError("boundary_workspace_bytes: desc_host must be an int64 host table [B,4] with at least one row")
+    desc_host = desc_host.contiguous()
+    return _lib.boundary_workspace_bytes(desc_host.data_ptr(), desc_host.shape[0], list(tables.C))
+
+
+def score_boundaries(pred, pdesc, pdesc_host, gt, gdesc, gdesc_host, tables, tau2, percentile=95, out=None, workspace=None):
+    """boundary records of predicted against ground-truth label maps (arguments as score_labels) -> int64 [B, N, 2, 5]
+    device tensor as hrseg_score_boundaries states it: per image, tree node (breadth first) and direction (0: prediction ->
+    truth) the fields BOUNDARY_FIELDS.  tau2 = floor(tolerance^2), percentile in 1..100.  The records are written, not
+    added to (out: a tensor to write into); workspace: an int64 device tensor of at least boundary_workspace_bytes bytes
+    (dirty is fine), else allocated here.  SCORE_BOUNDARIES_LAUNCHES launches, no synchronisation."""
+    check_score_tables(tables)
+    host = _boundary_host_table("score_boundaries", pred, pdesc, pdesc_host, gt, gdesc, gdesc_host)
+    tau2, percentile = int(tau2), int(percentile)
+    if not 1 <= percentile <= 100:
+        raise ValueError(f"score_boundaries: percentile {percentile} not in 1..100")
+    if tau2 < 0:
+        raise ValueError(f"score_boundaries: tau2 {tau2} is negative")
+    B, N, dev = host.shape[0] // 2, sum(tables.C), pred.device
+    shape = (B, N, 2, len(BOUNDARY_FIELDS))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int64, device=dev)
+    elif out.dtype != torch.int64 or out.device != dev or tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError(f"score_boundaries: out must be a contiguous int64 device tensor of shape {shape}")
+    need = _lib.boundary_workspace_bytes(host.data_ptr(), B, list(tables.C))
+    if workspace is None:
+        workspace = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+    elif workspace.dtype != torch.int64 or workspace.device != dev or not workspace.is_contiguous() or workspace.numel() * 8 < need:
+        raise ValueError(f"score_boundaries: workspace must be a contiguous int64 device tensor of at least {need} bytes")
+    call("hrseg_score_boundaries", ptr(pred), ptr(pdesc), ptr(gt), ptr(gdesc), host.data_ptr(), ptr(tables.device_lut(dev)),
+         len(tables.C), _lib.int_array(list(tables.C)), tau2, percentile, ptr(out), ptr(workspace), B)
+    return out
+
+
 def combine_levels(x0, x1, masks, is_union):
     """x0 [B,C0,H,W] (+ x1 [B,C1,H,W] or None), per output channel a bit mask over the C0+C1 input channels and a
     union flag -> [B,len(masks),H,W]: copy of the selected channel, or 1.0 where any selected channel is > 0"""

@@ -272,13 +272,14 @@ class Predictor:
     postprocess=Data.DevicePostprocess(...): the connected-component clean-up (Data/postprocess.py) of the decoded maps,
     behind whichever of the three decodes ran: the call returns the cleaned maps and `score` scores them.  Its min_area
     counts pixels of the map being produced -- the source's size in a call, the ground truth's size in `score` -- not
-    pixels at network size.  postprocess=None: exactly the calls described above, no launch and no allocation more."""
+    pixels at network size.  postprocess=None: exactly the calls described above, no launch and no allocation more.
+    `predictor.score_boundaries(images, labels)` decodes as `score` does and scores the outlines (Data/boundary.py)."""
 
     def __init__(self, model, class_tree, class_map, args, want_confidence=False, keep_logits=False, tta=None, window=None,
                  postprocess=None):
         from .Data.decode import DeviceDecode
         self.model, self.class_tree, self.class_map, self.args = model, class_tree, class_map, args
-        self.scorer, self.last_labels = None, None
+        self.scorer, self.boundary_scorer, self.last_labels = None, None, None
         self.size = int(args.img_size)
         self.decoder = DeviceDecode(class_tree, class_map, args.model_type)
         self.want_confidence = bool(want_confidence)
@@ -302,24 +303,43 @@ class Predictor:
     def score(self, images, labels=None, out=None, per_image=True):
         """images as for the call; labels: a list of uint8 HxW ground-truth maps in class_map pixel values (None: the
         RaggedBatch's own label maps) -> SourceScores of the maps decoded at the labels' sizes"""
-        from .Data.decode import pack_images
-        from .Data.loader import RaggedBatch
         from .Data.score import DeviceScore
         if self.scorer is None:
             self.scorer = DeviceScore(self.class_tree, self.class_map)
+        gt = self._ground_truth("Predictor.score", images, labels)
+        self.last_labels = self._predict(images, [(H, W) for _, H, W, _ in gt[2].tolist()])
+        return self.scorer.score(self.last_labels, gt, out, per_image)
+
+    @torch.no_grad()
+    def score_boundaries(self, images, labels=None, tolerance=2.0, percentile=95):
+        """images and labels as for `score`: the maps are decoded at the labels' sizes through the same window / TTA /
+        postprocess path (they stay in `last_labels`), then their outlines are scored against the labels' on the device
+        (Data/boundary.py) -> BoundaryScores"""
+        from .Data.boundary import DeviceBoundaryScore
+        key = (float(tolerance), int(percentile))
+        if self.boundary_scorer is None or (self.boundary_scorer.tolerance, self.boundary_scorer.percentile) != key:
+            self.boundary_scorer = DeviceBoundaryScore(self.class_tree, self.class_map, tolerance, percentile)
+        gt = self._ground_truth("Predictor.score_boundaries", images, labels)
+        self.last_labels = self._predict(images, [(H, W) for _, H, W, _ in gt[2].tolist()])
+        return self.boundary_scorer.score(self.last_labels, gt)
+
+    @staticmethod
+    def _ground_truth(who, images, labels):
+        """the (buffer, desc, desc_host) triple of the ground-truth maps of `score` / `score_boundaries`"""
+        from .Data.decode import pack_images
+        from .Data.loader import RaggedBatch
         if labels is None:
             if not isinstance(images, RaggedBatch) or images.label is None:
-                raise ValueError("Predictor.score: no ground-truth label maps")
+                raise ValueError(f"{who}: no ground-truth label maps")
             gt = (images.label, images.ldesc, images.ldesc_host)
         else:
             buf, host = pack_images(labels)
             if any(ch != 1 for _, _, _, ch in host.tolist()):
-                raise ValueError("Predictor.score: ground-truth label maps are single-channel uint8 images")
+                raise ValueError(f"{who}: ground-truth label maps are single-channel uint8 images")
             gt = (buf, host, host)
         if gt[2].shape[0] != len(images):
-            raise ValueError(f"Predictor.score: {len(images)} images, {gt[2].shape[0]} label maps")
-        self.last_labels = self._predict(images, [(H, W) for _, H, W, _ in gt[2].tolist()])
-        return self.scorer.score(self.last_labels, gt, out, per_image)
+            raise ValueError(f"{who}: {len(images)} images, {gt[2].shape[0]} label maps")
+        return gt
 
     @torch.no_grad()
     def _predict(self, images, sizes):
@@ -387,7 +407,8 @@ def write_metrics_csv(path, accuracy, iou, dice, precision, recall, class_metric
 
 @torch.no_grad()
 def predict_loop(model, device, test_loader, args, class_tree, Accuracy, Iou, perf_measure, Precision, Recall,
-                 save_dir=None, target_paths=None, label_dir=None, class_map=None, score_sources=False, postprocess=None):
+                 save_dir=None, target_paths=None, label_dir=None, class_map=None, score_sources=False, postprocess=None,
+                 boundary=None):
     """The per-fold body of the reference's predict() (predictEval.py:305-573) on a built model and loader: eval-mode
     forward, prediction_prep, get_metrics per batch, optional PNG dump of each batch's first image and metrics.csv.
     -> dict(accuracy, iou, dice, precision, recall, class_metrics, performance).
@@ -402,7 +423,12 @@ def predict_loop(model, device, test_loader, args, class_tree, Accuracy, Iou, pe
     [unlabelled ground truth, predictions outside the class map] per image), and save_dir gets metrics_source.csv (the
     dataset totals, one row per node).  Everything else is returned and written as without it.
     postprocess (a Data.DevicePostprocess; with label_dir or score_sources): every decoded source-size map goes through the
-    connected-component clean-up before it is written or scored, as in Predictor(postprocess=...)."""
+    connected-component clean-up before it is written or scored, as in Predictor(postprocess=...).
+    boundary (a Data.DeviceBoundaryScore; needs score_sources): the maps that are scored also have their outlines scored
+    against the sources' label maps on the device (Data/boundary.py).  The result gains the key "boundary" -- the
+    BoundaryScores.summary() of the dataset, {node name: mean hausdorff / hd_percentile / assd / surface_dice, images,
+    missed, spurious} -- and save_dir gets metrics_boundary.csv, one row per node.  boundary=None: exactly the launches and
+    files described above."""
     import os
     import numpy as np
     from . import train as T
@@ -425,6 +451,9 @@ def predict_loop(model, device, test_loader, args, class_tree, Accuracy, Iou, pe
         scorer = DeviceScore(class_tree, class_map)
         if source_decoder is None:
             source_decoder = DeviceDecode(class_tree, class_map, args.model_type)
+    outlines = []
+    if boundary is not None and not score_sources:
+        raise ValueError("boundary needs score_sources=True (the sources' own label maps)")
     for i, batch in enumerate(test_loader):
         data, target = batch[0].to(device), batch[1].to(device)
         _, output_logits = T._model_call(model, data, args, class_tree)
@@ -459,6 +488,8 @@ def predict_loop(model, device, test_loader, args, class_tree, Accuracy, Iou, pe
                 if postprocess is not None:
                     decoded = postprocess.apply(decoded)
             scored.append(scorer.score(decoded, batch[2]))
+            if boundary is not None:
+                outlines.append(boundary.score(decoded, batch[2]))
     if save_dir is not None:
         os.makedirs(save_dir, exist_ok=True)
         write_metrics_csv(os.path.join(save_dir, "metrics.csv"), acc2, iou2, dice2, prec2, rec2, cls2)
@@ -471,7 +502,25 @@ def predict_loop(model, device, test_loader, args, class_tree, Accuracy, Iou, pe
             tot = result["source"]["total"]
             write_metrics_csv(os.path.join(save_dir, "metrics_source.csv"), *[tot[k] for k in METRIC_NAMES],
                               [{k: [tot[k][c]] for k in METRIC_NAMES} for c in range(len(tot["accuracy"]))])
+    if boundary is not None:
+        from .Data.boundary import BoundaryScores
+        result["boundary"] = BoundaryScores.cat(outlines).summary()
+        if save_dir is not None:
+            write_boundary_csv(os.path.join(save_dir, "metrics_boundary.csv"), result["boundary"])
     return result
+
+
+def write_boundary_csv(path, summary):
+    """metrics_boundary.csv: one row per tree node of a BoundaryScores.summary() (distances in pixels; empty cells where a
+    node was in both maps of no image)"""
+    import csv
+    from .Data.boundary import METRICS
+    with open(path, "w", newline="") as f:
+        wr = csv.writer(f)
+        wr.writerow(["Class", "Hausdorff", "HDPercentile", "ASSD", "SurfaceDice", "Images", "Missed", "Spurious"])
+        for name, row in summary.items():
+            wr.writerow([name] + ["" if math.isnan(row[k]) else row[k] for k in METRICS] +
+                        [row["images"], row["missed"], row["spurious"]])
 
 
 def _source_summary(scores):
