@@ -931,6 +931,90 @@ int hrseg_score_boundaries(const unsigned char* pred, const long* pdesc, const u
                            const long* desc_host, const unsigned long long* path_lut, int nlevels, const int* C, long tau2,
                            int percentile, long long* records, void* workspace, int B, hrseg_stream_t stream);
 
+/* ------------------------------------------------------------------ device instance scoring (Data/instances.py; csrc/instances.hip)
+ * The sixth, optional stage: the question per OBJECT -- how many teeth, restorations or lesions were found, missed or
+ * invented, and how well each found one overlaps its true one.  The connected components (hrseg_label_components) of the
+ * prediction and of the ground truth are matched one to one on the device -> per image and group of the cut the integer
+ * records from which detection precision / recall / F1, segmentation quality and panoptic quality (PQ = SQ x RQ) follow,
+ * and per-instance match maps.  No map leaves the device; no host read, no synchronisation, no device allocation.
+ *
+ * Inputs as for hrseg_score_labels / hrseg_score_boundaries: packed uint8 buffers pred and gt with their DEVICE [B][4] int64
+ * tables pdesc / gdesc (byte offset, H, W, 1) -- arbitrary offsets and gaps, the two buffers may be laid out differently, the
+ * two tables must agree on every H_b x W_b -- and desc_host, the HOST table [2][B][4]: the host copy of pdesc's B rows
+ * followed by that of gdesc's.  The entry points size their grids and check their limits on desc_host, the kernels read
+ * pdesc / gdesc; a sample whose DEVICE descriptors break a rule, disagree on the size or leave the extent of the host
+ * table is skipped by the kernels.
+ * group: the DEVICE [256] byte table of hrseg_label_components (pixel value -> group id of the cut, 255 = no leaf's value).
+ * things: DEVICE [256] bytes, non-zero for the group ids that are scored as instances; group 255 is never a thing.
+ *
+ * Validity.  A pixel whose ground-truth value has group 255 is VOID: it belongs to no component IN EITHER MAP (the convention
+ * of hrseg_score_boundaries).  A predicted value of group 255 belongs to no predicted component.
+ * hrseg_mask_void_labels realises this by a masked copy of the prediction: out[i] = pred[i] where the ground truth is valid,
+ * else void_value, a byte the caller picks with group[void_value] == 255; void_value = -1: no such byte exists, nothing can
+ * be void and out is a plain copy.  group is device memory, so THE CALLER checks group[void_value] == 255 (ops.mask_void_labels
+ * does, on the host table it builds the device table from); the entry point checks the range -1..255.  out has the layout
+ * of pred and must not overlap it; bytes outside the spans are neither read nor written.  One launch.
+ * Components are those of hrseg_label_components on the masked prediction pm and on gt, with one group table and one
+ * connectivity.  DELIBERATE CONVENTION: a predicted region cut in two by a void area is TWO components, one lying wholly in
+ * void does not exist.
+ *
+ * Match.  A predicted component P and a true component G of the same thing group in the same image, inter = |P n G|,
+ * match when 3 * inter > |P| + |G|: IoU = inter / (|P| + |G| - inter) > 1/2 in integers; IoU exactly 1/2 does not match.
+ * At most one partner exists on either side: |P| >= inter gives 2 * inter > |G|, so a partner holds more than half of G's
+ * pixels, and two disjoint components cannot both; likewise for P.
+ *
+ * hrseg_score_instances.  pm / proots / parea and gt / groots / garea: the masked prediction and the ground truth with the
+ * roots and areas hrseg_label_components wrote for them (same desc tables, group and connectivity).
+ * records: DEVICE int64 [per_image ? B : 1][256][HRSEG_INSTANCE_FIELDS], indexed by group id, ACCUMULATED (+=; the caller
+ * zeroes it, a dataset total accumulates in place as for hrseg_score_labels).  Rows of groups that are no things are not
+ * touched.  Fields:
+ *   0 n_gt, 1 n_pred    the thing components of the ground truth / of the masked prediction;
+ *   2 tp                the matched pairs;  fp = n_pred - tp, fn = n_gt - tp;
+ *   3 sum_iou_q30       sum over the matched pairs of floor((inter << 30) / union), union = |P| + |G| - inter, unsigned
+ *                       64-bit: an integer, so the sum is exact in any order;
+ *   4 sum_inter, 5 sum_union   over the matched pairs;
+ *   6..9 tp_at[k]       the matched pairs with inter * 1000 >= thresholds[k] * union.
+ * thresholds: HOST int[4], per mille; 0 = unused (the field stays as it was), else 501..1000.
+ * gmatch, ginter: int32, indexed like the gt buffer; pmatch: int32, indexed like the prediction buffer.  Inside the image
+ * spans every element is written: gmatch / pmatch hold at the FIRST pixel of a thing component the row-major index (within
+ * the image) of the partner's first pixel, or -1 when unmatched, and -2 everywhere else; ginter holds inter at the first
+ * pixel of a matched true component and 0 elsewhere.  Elements outside every span are not written, bytes outside the
+ * spans are not read.
+ * workspace: hrseg_instances_workspace_bytes(desc_host, B) bytes (it takes the same [2][B][4] table and reads the
+ * ground-truth rows; 0 with a message when refused), 8-byte aligned, DEVICE: with E = the extent of the ground-truth buffer
+ * (max_b offset_b + H_b W_b), 8 E bytes of vote slots + 4 E of overlaps, rounded up to 8 -- below 16 bytes per byte of the
+ * extent, computed on the host; nothing is sized by a component count.  The call's first launch initialises what it needs,
+ * so a dirty workspace may be reused.
+ * Method (csrc/instances.hip).  No pair table: the distinct (P, G) pairs are bounded by the pixel count only.  Every true
+ * thing component has one 64-bit slot (candidate root, count) at its first pixel's index; every pixel of G votes for the
+ * predicted component of G's group it lies in, or for "none", as runs of equal (g_root, p_root) merged into weighted votes;
+ * a Boyer-Moore majority vote is merged into the slot by a compare-and-swap loop (an empty slot takes the vote, an equal
+ * candidate adds, another subtracts, what passes zero takes over).  The loop serialises the votes in SOME order, a weighted
+ * vote equals its unit votes in sequence, and a strict majority is the final candidate in every order.  A second pass
+ * counts inter with the candidate, a third applies the exact test: where a partner exists it is the candidate, where none
+ * exists every candidate fails -- the same bytes in every run although the vote's intermediate state is not, and whatever
+ * the "deterministic" knob says.  HRSEG_SCORE_INSTANCES_CALL_LAUNCHES launches; with the masked copy's one the stage
+ * counts HRSEG_SCORE_INSTANCES_LAUNCHES under the family "score_instances", outside the NULL total (the two labellings
+ * count under "label_components").
+ * Refused with a message before anything is launched, under the entry point's own name: NULL pointers; B outside 1..65535;
+ * roots, areas, pmatch, gmatch or ginter not 4-byte, records or workspace not 8-byte aligned; a descriptor row of either
+ * table with a negative offset, H < 1, W < 1 or channels != 1; H * W >= 2^31; the two tables disagreeing on a size; a
+ * threshold outside {0, 501..1000}; void_value outside -1..255; out overlapping pred (the spans' extent from the buffers'
+ * starts). */
+#define HRSEG_INSTANCE_FIELDS 10
+#define HRSEG_MASK_VOID_LABELS_LAUNCHES 1
+#define HRSEG_SCORE_INSTANCES_CALL_LAUNCHES 4
+#define HRSEG_SCORE_INSTANCES_LAUNCHES (HRSEG_MASK_VOID_LABELS_LAUNCHES + HRSEG_SCORE_INSTANCES_CALL_LAUNCHES)
+size_t hrseg_instances_workspace_bytes(const long* desc_host, int B);
+int hrseg_mask_void_labels(const unsigned char* pred, const long* pdesc, const unsigned char* gt, const long* gdesc,
+                           const long* desc_host, const unsigned char* group, int void_value, unsigned char* out, int B,
+                           hrseg_stream_t stream);
+int hrseg_score_instances(const unsigned char* pm, const long* pdesc, const int* proots, const int* parea,
+                          const unsigned char* gt, const long* gdesc, const int* groots, const int* garea,
+                          const long* desc_host, const unsigned char* group, const unsigned char* things,
+                          const int* thresholds, long long* records, int* pmatch, int* gmatch, int* ginter, void* workspace,
+                          int B, int per_image, hrseg_stream_t stream);
+
 /* ------------------------------------------------------------------ level synthesis for flat models (evaluation side; csrc/targets.hip)
  * predictEval.py:85-129 get_parent_masks (parent = union of its descendant leaves, "any > 0") and :134-185
  * combine_levels (per-level tensors stitched from leaf and parent channels).  out[b][o] is the COPY of the single

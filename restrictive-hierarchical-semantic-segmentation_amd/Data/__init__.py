@@ -5,3 +5,4 @@ from .decode import DeviceDecode, RaggedLabels, WindowPlan, plan_windows, window
 from .score import DeviceScore, SourceScores, build_score_tables  # noqa: F401
 from .postprocess import ComponentTables, DevicePostprocess, build_component_tables  # noqa: F401
 from .boundary import BoundaryScores, DeviceBoundaryScore  # noqa: F401
+from .instances import DeviceInstanceScore, InstanceScores  # noqa: F401

@@ -147,6 +147,8 @@ PROTOTYPES = {
     "hrseg_label_components": [_p, _p, _p, _i, _p, _i, _p, _p, _p],
     "hrseg_filter_components": [_p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p],
     "hrseg_score_boundaries": [_p, _p, _p, _p, _p, _p, _i, C.POINTER(C.c_int), _l, _i, _p, _p, _i, _p],
+    "hrseg_mask_void_labels": [_p, _p, _p, _p, _p, _p, _i, _p, _i, _p],
+    "hrseg_score_instances": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, C.POINTER(C.c_int), _p, _p, _p, _p, _p, _i, _i, _p],
     "hrseg_combine_levels": [_p, _i, _p, _i, _p, _p, _p, _i, _i, _l, _p],
     "hrseg_weight_images_refresh": [_p],
 }
@@ -167,6 +169,7 @@ RAW_PROTOTYPES = {
     "hrseg_components_tile": [C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "hrseg_filter_components_workspace_bytes": [_i],
     "hrseg_boundary_workspace_bytes": [_p, _i, _i, C.POINTER(C.c_int)],
+    "hrseg_instances_workspace_bytes": [_p, _i],
 }
 
 _lib.hrseg_last_error_string.restype = C.c_char_p
@@ -247,7 +250,8 @@ def launch_count(family=None, reset=False) -> int:
     pipeline counts under "augment_image" / "augment_targets", the output pipeline under "decode_labels", the scoring
     pipeline under "score_labels", test-time augmentation under "decode_views" / "flip_views", sliding-window inference
     under "window_crops" / "decode_windows", the post-processing under "label_components" / "filter_components", the
-    boundary scoring under "score_boundaries")"""
+    boundary scoring under "score_boundaries", the instance scoring's masked copy and scoring launches under
+    "score_instances")"""
     return int(_lib.hrseg_launch_count(None if family is None else family.encode(), int(reset)))
 
 
@@ -383,6 +387,18 @@ def boundary_workspace_bytes(desc_host_ptr, B, Cs) -> int:
     n = int(raw["hrseg_boundary_workspace_bytes"](desc_host_ptr, int(B), len(Cs), int_array(list(Cs))))
     if n == 0:
         raise RuntimeError(f"hrseg_boundary_workspace_bytes failed: {last_error()}")
+    return n
+
+
+raw["hrseg_instances_workspace_bytes"].restype = C.c_size_t
+
+
+def instances_workspace_bytes(desc_host_ptr, B) -> int:
+    """bytes of the workspace hrseg_score_instances needs for the B images of a [2][B][4] host descriptor table (its
+    address; the ground-truth rows decide); RuntimeError when the library refuses an argument"""
+    n = int(raw["hrseg_instances_workspace_bytes"](desc_host_ptr, int(B)))
+    if n == 0:
+        raise RuntimeError(f"hrseg_instances_workspace_bytes failed: {last_error()}")
     return n
 
 

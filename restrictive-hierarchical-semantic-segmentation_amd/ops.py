@@ -1021,8 +1021,9 @@ BOUNDARY_MAX_SIDE = 32768
 BOUNDARY_FIELDS = ("n", "sum_q16", "max_d2", "within", "pk_d2")
 
 
-def _boundary_host_table(who, pred, pdesc, pdesc_host, gt, gdesc, gdesc_host):
-    """the checks of score_labels on the two descriptor tables + the limits of hrseg_score_boundaries -> the [2B,4] host table"""
+def _pair_host_table(who, pred, pdesc, pdesc_host, gt, gdesc, gdesc_host, max_side=BOUNDARY_MAX_SIDE):
+    """the checks of score_labels on the two descriptor tables + the limit of hrseg_score_boundaries on a side (max_side=None:
+    that of hrseg_label_components on the pixels) -> the [2B,4] host table"""
     _check_ragged(pred, pdesc, pdesc_host, (1,))
     _check_ragged(gt, gdesc, gdesc_host, (1,))
     prow, grow = pdesc_host.tolist(), gdesc_host.tolist()
@@ -1031,8 +1032,10 @@ def _boundary_host_table(who, pred, pdesc, pdesc_host, gt, gdesc, gdesc_host):
     for b, ((_, H, W, _), (_, gH, gW, _)) in enumerate(zip(prow, grow)):
         if (H, W) != (gH, gW):
             raise ValueError(f"{who}: sample {b}: predicted map {H}x{W}, ground truth {gH}x{gW}")
-        if H > BOUNDARY_MAX_SIDE or W > BOUNDARY_MAX_SIDE:
-            raise ValueError(f"{who}: sample {b}: {H}x{W}, a side above {BOUNDARY_MAX_SIDE}")
+        if max_side is not None and (H > max_side or W > max_side):
+            raise ValueError(f"{who}: sample {b}: {H}x{W}, a side above {max_side}")
+        if max_side is None and H * W > COMPONENTS_MAX_PIXELS:
+            raise ValueError(f"{who}: sample {b}: {H}x{W} has 2^31 pixels or more")
     if gt.device != pred.device:
         raise ValueError(f"{who}: the two buffers live on different devices")
     return torch.cat([pdesc_host.to(torch.int64), gdesc_host.to(torch.int64)]).contiguous()
@@ -1054,7 +1057,7 @@ def score_boundaries(pred, pdesc, pdesc_host, gt, gdesc, gdesc_host, tables, tau
     added to (out: a tensor to write into); workspace: an int64 device tensor of at least boundary_workspace_bytes bytes
     (dirty is fine), else allocated here.  SCORE_BOUNDARIES_LAUNCHES launches, no synchronisation."""
     check_score_tables(tables)
-    host = _boundary_host_table("score_boundaries", pred, pdesc, pdesc_host, gt, gdesc, gdesc_host)
+    host = _pair_host_table("score_boundaries", pred, pdesc, pdesc_host, gt, gdesc, gdesc_host)
     tau2, percentile = int(tau2), int(percentile)
     if not 1 <= percentile <= 100:
         raise ValueError(f"score_boundaries: percentile {percentile} not in 1..100")
@@ -1074,6 +1077,109 @@ def score_boundaries(pred, pdesc, pdesc_host, gt, gdesc, gdesc_host, tables, tau
     call("hrseg_score_boundaries", ptr(pred), ptr(pdesc), ptr(gt), ptr(gdesc), host.data_ptr(), ptr(tables.device_lut(dev)),
          len(tables.C), _lib.int_array(list(tables.C)), tau2, percentile, ptr(out), ptr(workspace), B)
     return out
+
+
+# launches counted under the family "score_instances": the masked copy's one and hrseg_score_instances' four.
+# SCORE_INSTANCES_LAUNCHES is what one DeviceInstanceScore.score adds to the family (the labellings count under their own)
+MASK_VOID_LABELS_LAUNCHES, SCORE_INSTANCES_CALL_LAUNCHES = 1, 4
+SCORE_INSTANCES_LAUNCHES = MASK_VOID_LABELS_LAUNCHES + SCORE_INSTANCES_CALL_LAUNCHES
+INSTANCE_FIELDS = ("n_gt", "n_pred", "tp", "sum_iou_q30", "sum_inter", "sum_union", "tp_at0", "tp_at1", "tp_at2", "tp_at3")
+INSTANCE_MAX_THRESHOLDS = 4
+
+
+def _check_byte_table(who, what, t, device):
+    if t.dtype != torch.uint8 or t.numel() != 256 or t.device != device or not t.is_contiguous():
+        raise ValueError(f"{who}: {what} must be a contiguous uint8 table of 256 entries on the maps' device")
+
+
+def void_value(group):
+    """the byte the masked copy writes at void pixels: the largest pixel value of group 255 in a host group table (256
+    ints), or -1 when every value has a group (then nothing can be void)"""
+    free = [v for v, g in enumerate(group) if int(g) == 255]
+    return free[-1] if free else -1
+
+
+def instances_workspace_bytes(pdesc_host, gdesc_host):
+    """bytes of the workspace score_instances needs for the images of two [B,4] int64 host descriptor tables: 12 bytes per
+    byte of the ground-truth buffer's extent, rounded up to 8 (needs no GPU)"""
+    for t in (pdesc_host, gdesc_host):
+        if t.is_cuda or t.dtype != torch.int64 or t.dim() != 2 or t.shape[1] != 4 or t.shape[0] < 1:
+            raise ValueError("instances_workspace_bytes: the descriptor tables must be int64 host tables [B,4] with at least one row")
+    if pdesc_host.shape != gdesc_host.shape:
+        raise ValueError(f"instances_workspace_bytes: {pdesc_host.shape[0]} predicted maps against {gdesc_host.shape[0]} ground-truth maps")
+    host = torch.cat([pdesc_host, gdesc_host]).contiguous()
+    return _lib.instances_workspace_bytes(host.data_ptr(), pdesc_host.shape[0])
+
+
+def mask_void_labels(pred, pdesc, pdesc_host, gt, gdesc, gdesc_host, group, group_host, void=None, out=None):
+    """the masked copy of hrseg_mask_void_labels: the predicted maps with the byte `void` wherever the ground truth's value
+    has group 255 (void=None: void_value(group_host); -1: a plain copy).  group: the [256] uint8 device table, group_host:
+    the 256 ints it was built from -- group[void] == 255 is checked HERE, on the host table, the library checks the range.
+    out: a uint8 device tensor of pred's length to write into (bytes outside the spans stay), else allocated here.
+    One launch, no synchronisation."""
+    who = "mask_void_labels"
+    if len(group_host) != 256:
+        raise ValueError(f"{who}: the host group table has {len(group_host)} entries, not 256")
+    v = void_value(group_host) if void is None else int(void)
+    if not -1 <= v <= 255 or (v >= 0 and int(group_host[v]) != 255):
+        raise ValueError(f"{who}: void value {v}: a byte whose group is 255, or -1 for none")
+    if v < 0 and any(int(g) == 255 for g in group_host):
+        raise ValueError(f"{who}: void value -1, but the group table has bytes of group 255")
+    host = _pair_host_table(who, pred, pdesc, pdesc_host, gt, gdesc, gdesc_host, None)
+    _check_byte_table(who, "group", group, pred.device)
+    if out is None:
+        out = torch.empty(pred.numel(), dtype=torch.uint8, device=pred.device)
+    elif out.dtype != torch.uint8 or out.device != pred.device or out.numel() != pred.numel() or not out.is_contiguous():
+        raise ValueError(f"{who}: out must be a contiguous uint8 device tensor of pred's length")
+    call("hrseg_mask_void_labels", ptr(pred), ptr(pdesc), ptr(gt), ptr(gdesc), host.data_ptr(), ptr(group), v, ptr(out),
+         host.shape[0] // 2)
+    return out
+
+
+def score_instances(pm, pdesc, pdesc_host, proots, parea, gt, gdesc, gdesc_host, groots, garea, group, things, thresholds=(),
+                    per_image=True, out=None, workspace=None):
+    """hrseg_score_instances on the masked prediction `pm` and the ground truth with what label_components returned for
+    each; group / things: [256] uint8 device tables; thresholds: up to 4 per-mille values, 0 or 501..1000.
+    -> (records, pmatch, gmatch, ginter): int64 [R, 256, 10] (R = B or 1; fields INSTANCE_FIELDS) and the int32 match maps
+    indexed like the prediction (pmatch) and the ground-truth buffer (gmatch, ginter).  out = that tuple of an earlier
+    call: records are added to, the maps written inside the spans and returned as given; else records are zeroed and the
+    maps uninitialised outside the spans.  workspace: an int64 device tensor of at least instances_workspace_bytes bytes
+    (dirty is fine), else allocated here.  SCORE_INSTANCES_CALL_LAUNCHES launches, no synchronisation."""
+    who = "score_instances"
+    host = _pair_host_table(who, pm, pdesc, pdesc_host, gt, gdesc, gdesc_host, None)
+    dev, B = pm.device, host.shape[0] // 2
+    _check_byte_table(who, "group", group, dev)
+    _check_byte_table(who, "things", things, dev)
+    thr = [int(t) for t in thresholds]
+    if len(thr) > INSTANCE_MAX_THRESHOLDS or any(t != 0 and not 501 <= t <= 1000 for t in thr):
+        raise ValueError(f"{who}: thresholds {thr}: at most {INSTANCE_MAX_THRESHOLDS} per-mille values, each 0 or in 501..1000")
+    thr += [0] * (INSTANCE_MAX_THRESHOLDS - len(thr))
+    for t, like in ((proots, pm), (parea, pm), (groots, gt), (garea, gt)):
+        if t.dtype != torch.int32 or t.device != dev or t.numel() != like.numel() or not t.is_contiguous():
+            raise ValueError(f"{who}: roots and areas must be contiguous int32 device tensors of their label buffer's length")
+    R = B if per_image else 1
+    shape = (R, 256, len(INSTANCE_FIELDS))
+    if out is None:
+        records = zeros(shape, torch.int64, dev)
+        pmatch = torch.empty(pm.numel(), dtype=torch.int32, device=dev)
+        gmatch = torch.empty(gt.numel(), dtype=torch.int32, device=dev)
+        ginter = torch.empty(gt.numel(), dtype=torch.int32, device=dev)
+    else:
+        records, pmatch, gmatch, ginter = out
+        if records.dtype != torch.int64 or records.device != dev or tuple(records.shape) != shape or not records.is_contiguous():
+            raise ValueError(f"{who}: out's records must be a contiguous int64 device tensor of shape {shape}")
+        for t, like in ((pmatch, pm), (gmatch, gt), (ginter, gt)):
+            if t.dtype != torch.int32 or t.device != dev or t.numel() != like.numel() or not t.is_contiguous():
+                raise ValueError(f"{who}: out's match maps must be contiguous int32 device tensors of their label buffer's length")
+    need = _lib.instances_workspace_bytes(host.data_ptr(), B)
+    if workspace is None:
+        workspace = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+    elif workspace.dtype != torch.int64 or workspace.device != dev or not workspace.is_contiguous() or workspace.numel() * 8 < need:
+        raise ValueError(f"{who}: workspace must be a contiguous int64 device tensor of at least {need} bytes")
+    call("hrseg_score_instances", ptr(pm), ptr(pdesc), ptr(proots), ptr(parea), ptr(gt), ptr(gdesc), ptr(groots), ptr(garea),
+         host.data_ptr(), ptr(group), ptr(things), _lib.int_array(thr), ptr(records), ptr(pmatch), ptr(gmatch), ptr(ginter),
+         ptr(workspace), B, int(bool(per_image)))
+    return records, pmatch, gmatch, ginter
 
 
 def combine_levels(x0, x1, masks, is_union):

@@ -273,13 +273,15 @@ class Predictor:
     behind whichever of the three decodes ran: the call returns the cleaned maps and `score` scores them.  Its min_area
     counts pixels of the map being produced -- the source's size in a call, the ground truth's size in `score` -- not
     pixels at network size.  postprocess=None: exactly the calls described above, no launch and no allocation more.
-    `predictor.score_boundaries(images, labels)` decodes as `score` does and scores the outlines (Data/boundary.py)."""
+    `predictor.score_boundaries(images, labels)` decodes as `score` does and scores the outlines (Data/boundary.py);
+    `predictor.score_instances(images, labels)` likewise matches the objects of the two maps (Data/instances.py)."""
 
     def __init__(self, model, class_tree, class_map, args, want_confidence=False, keep_logits=False, tta=None, window=None,
                  postprocess=None):
         from .Data.decode import DeviceDecode
         self.model, self.class_tree, self.class_map, self.args = model, class_tree, class_map, args
         self.scorer, self.boundary_scorer, self.last_labels = None, None, None
+        self.instance_scorer, self._instance_key = None, None
         self.size = int(args.img_size)
         self.decoder = DeviceDecode(class_tree, class_map, args.model_type)
         self.want_confidence = bool(want_confidence)
@@ -322,6 +324,21 @@ class Predictor:
         gt = self._ground_truth("Predictor.score_boundaries", images, labels)
         self.last_labels = self._predict(images, [(H, W) for _, H, W, _ in gt[2].tolist()])
         return self.boundary_scorer.score(self.last_labels, gt)
+
+    @torch.no_grad()
+    def score_instances(self, images, labels=None, level=0, things=None, connectivity=8, thresholds=(0.75, 0.9)):
+        """images and labels as for `score`: the maps are decoded at the labels' sizes through the same window / TTA /
+        postprocess path (they stay in `last_labels`), then their connected components are matched with the labels' on the
+        device (Data/instances.py; the options are DeviceInstanceScore's, the scorer is kept per option set)
+        -> InstanceScores"""
+        from .Data.instances import DeviceInstanceScore
+        key = (int(level), None if things is None else tuple(things), int(connectivity), tuple(float(t) for t in thresholds))
+        if self.instance_scorer is None or self._instance_key != key:
+            self.instance_scorer = DeviceInstanceScore(self.class_tree, self.class_map, level, things, connectivity, thresholds)
+            self._instance_key = key
+        gt = self._ground_truth("Predictor.score_instances", images, labels)
+        self.last_labels = self._predict(images, [(H, W) for _, H, W, _ in gt[2].tolist()])
+        return self.instance_scorer.score(self.last_labels, gt)
 
     @staticmethod
     def _ground_truth(who, images, labels):
@@ -408,7 +425,7 @@ def write_metrics_csv(path, accuracy, iou, dice, precision, recall, class_metric
 @torch.no_grad()
 def predict_loop(model, device, test_loader, args, class_tree, Accuracy, Iou, perf_measure, Precision, Recall,
                  save_dir=None, target_paths=None, label_dir=None, class_map=None, score_sources=False, postprocess=None,
-                 boundary=None):
+                 boundary=None, instances=None):
     """The per-fold body of the reference's predict() (predictEval.py:305-573) on a built model and loader: eval-mode
     forward, prediction_prep, get_metrics per batch, optional PNG dump of each batch's first image and metrics.csv.
     -> dict(accuracy, iou, dice, precision, recall, class_metrics, performance).
@@ -428,7 +445,11 @@ def predict_loop(model, device, test_loader, args, class_tree, Accuracy, Iou, pe
     against the sources' label maps on the device (Data/boundary.py).  The result gains the key "boundary" -- the
     BoundaryScores.summary() of the dataset, {node name: mean hausdorff / hd_percentile / assd / surface_dice, images,
     missed, spurious} -- and save_dir gets metrics_boundary.csv, one row per node.  boundary=None: exactly the launches and
-    files described above."""
+    files described above.
+    instances (a Data.DeviceInstanceScore; needs score_sources): the maps that are scored also have their connected
+    components matched with those of the sources' label maps on the device (Data/instances.py).  The result gains the key
+    "instances" -- the InstanceScores.summary() of the dataset -- and save_dir gets metrics_instances.csv, one row per thing
+    group plus "all".  instances=None: exactly the launches and files described above."""
     import os
     import numpy as np
     from . import train as T
@@ -454,6 +475,9 @@ def predict_loop(model, device, test_loader, args, class_tree, Accuracy, Iou, pe
     outlines = []
     if boundary is not None and not score_sources:
         raise ValueError("boundary needs score_sources=True (the sources' own label maps)")
+    matched = []
+    if instances is not None and not score_sources:
+        raise ValueError("instances needs score_sources=True (the sources' own label maps)")
     for i, batch in enumerate(test_loader):
         data, target = batch[0].to(device), batch[1].to(device)
         _, output_logits = T._model_call(model, data, args, class_tree)
@@ -490,6 +514,8 @@ def predict_loop(model, device, test_loader, args, class_tree, Accuracy, Iou, pe
             scored.append(scorer.score(decoded, batch[2]))
             if boundary is not None:
                 outlines.append(boundary.score(decoded, batch[2]))
+            if instances is not None:
+                matched.append(instances.score(decoded, batch[2]))
     if save_dir is not None:
         os.makedirs(save_dir, exist_ok=True)
         write_metrics_csv(os.path.join(save_dir, "metrics.csv"), acc2, iou2, dice2, prec2, rec2, cls2)
@@ -507,7 +533,28 @@ def predict_loop(model, device, test_loader, args, class_tree, Accuracy, Iou, pe
         result["boundary"] = BoundaryScores.cat(outlines).summary()
         if save_dir is not None:
             write_boundary_csv(os.path.join(save_dir, "metrics_boundary.csv"), result["boundary"])
+    if instances is not None:
+        from .Data.instances import InstanceScores
+        result["instances"] = InstanceScores.cat(matched).summary()
+        if save_dir is not None:
+            write_instances_csv(os.path.join(save_dir, "metrics_instances.csv"), result["instances"])
     return result
+
+
+def write_instances_csv(path, summary):
+    """metrics_instances.csv: one row per thing group of an InstanceScores.summary() and one for "all" (empty cells where a
+    denominator was 0; one TPAt column per threshold)"""
+    import csv
+    rows = {k: v for k, v in summary.items() if isinstance(v, dict)}
+    at = list(rows["all"]["tp_at"])
+    keys = ("n_gt", "n_pred", "tp", "fp", "fn", "precision", "recall", "rq", "sq", "pq", "mean_iou")
+    with open(path, "w", newline="") as f:
+        wr = csv.writer(f)
+        wr.writerow(["Group", "GT", "Predicted", "TP", "FP", "FN", "Precision", "Recall", "RQ", "SQ", "PQ", "MeanIoU"] +
+                    [f"TPAt{t:g}" for t in at])
+        for name, row in rows.items():
+            wr.writerow([name] + ["" if isinstance(row[k], float) and math.isnan(row[k]) else row[k] for k in keys] +
+                        [row["tp_at"][t] for t in at])
 
 
 def write_boundary_csv(path, summary):
