@@ -177,7 +177,8 @@ int hrseg_conv_wgrad_group_ws(int n, const float* const* x, const float* const* 
  * "decode_windows" (sliding-window inference, 1 launch per hrseg_window_crops / hrseg_decode_windows call) and "ohem" (online hard
  * example mining: 1 launch per hrseg_ohem_scores, 7 per hrseg_ohem_select, 1 per hrseg_loss_partials_ohem / hrseg_loss_bwd_ohem call),
  * "label_components" / "filter_components" (post-processing) and "score_boundaries" (boundary scoring, HRSEG_SCORE_BOUNDARIES_LAUNCHES
- * per hrseg_score_boundaries call) are families of their own, outside the NULL total and the convolution counts. */
+ * per hrseg_score_boundaries call), "score_instances" (instance scoring) and "score_calibration" (calibration scoring, 1 launch
+ * per hrseg_score_calibration call) are families of their own, outside the NULL total and the convolution counts. */
 long hrseg_launch_count(const char* family, int reset);
 /* tile-plan overrides and A/B switches for the sweep tools under tools/ (value 0 = automatic plan).  Keys: igemm_wtm,
  * igemm_kc, igemm_db, igemm_ksplit, group_wtm, wgrad_pix, wgrad_db, wgrad_blocks, wgrad_group_mult,
@@ -1014,6 +1015,52 @@ int hrseg_score_instances(const unsigned char* pm, const long* pdesc, const int*
                           const long* desc_host, const unsigned char* group, const unsigned char* things,
                           const int* thresholds, long long* records, int* pmatch, int* gmatch, int* ginter, void* workspace,
                           int B, int per_image, hrseg_stream_t stream);
+
+/* ------------------------------------------------------------------ device calibration scoring (Data/calibration.py; csrc/calibration.hip)
+ * The fourth scorer: does the model's composed probability mean anything?  Per-level logits at network size against
+ * ground-truth label maps at the SOURCE size -> per tree node, and per level for the decoded path's top label, a reliability
+ * histogram of exact integers from which ECE, MCE and the Brier score follow on the host.  No full-size probability plane
+ * exists at any point.
+ * z, C, tree and S as for hrseg_decode_labels; gt, gdesc and path_lut as for hrseg_score_labels (an entry of path_lut that
+ * names a channel above C[L], has no level-0 node or a node at a level >= nlevels counts as 0).  inv_temp: HOST array of
+ * nlevels floats, 1 / temperature per level.  Rows: R = sum_L C[L] + nlevels; the node rows first, in breadth-first channel
+ * order (level 0's channels, then level 1's, ...), then the nlevels "top-label" rows.  For pixel (y, x) of sample b (H_b x W_b
+ * from gdesc):
+ *   1. g = path_lut[gt byte]; g == 0: ignored[per_image ? b : 0] += 1 and nothing else happens;
+ *   2. EVERY logit of EVERY level is resampled S x S -> H_b x W_b with the same multiplies and adds, in the same order, as
+ *      hrseg_decode_labels step 1 (the same taps and weights, every product and sum rounded on its own), then multiplied
+ *      once (one rounding) by inv_temp[L]: v_L[c].  inv_temp[L] == 1.0f is the identity bit for bit;
+ *   3. node probabilities are the model's own composition: P_0[c] = sigmoid(v_0[c]) (with root_softmax: the soft-max over
+ *      level 0); P_L[c] = P_{L-1}[parent(c)] * softmax_group(v_L)[c] for L >= 1, parent and groups from first_child /
+ *      n_children.  A channel of level L+1 that is in no child group (or in two) is refused before launch;
+ *   4. the decoded path c_0, c_1, ... is exactly that of hrseg_decode_labels (arg-max of the logits, strict >, lowest index
+ *      wins); T_L = P_L[c_L] for every level the path reaches;
+ *   5. events (p, y): node row (L, c): p = P_L[c], y = (byte L of g) - 1 == c -- one event per valid pixel, always (a leaf
+ *      shallower than L has byte 0 there: y = 0).  Top row L: only where the path reaches level L AND byte L of g is
+ *      non-zero: p = T_L, y = (c_L == byte L of g - 1).  A pixel where exactly one of the two -- decoded path, ground
+ *      truth -- has a node at level L produces NO top-label event (hrseg_score_labels counts those pixels, in row or
+ *      column 0 of its level matrix);
+ *   6. an event goes to hist[img][row][bin][4] = (n, pos, sum_q, sum_e2), int64, +=, n_bins + 1 bins per row:
+ *      q = (unsigned)rintf(clamp(p, 0, 1) * 16777216.f); bin = min(n_bins - 1, (q * n_bins) >> 24);
+ *      e = y ? 16777216 - q : q; e12 = (e + 2048) >> 12; the cell gets n += 1, pos += y, sum_q += q, sum_e2 += e12 * e12.
+ *      A NaN p goes to the extra bin n_bins with n and pos only (tested before the clamp, which would swallow it), so the
+ *      sum over all n_bins + 1 bins of n is the row's event count exactly and a non-finite logit stays visible.
+ * Capacity: sum_q <= 2^24 N and sum_e2 <= 2^24 N for N events, so a dataset total of 2^39 events per cell fits an int64.
+ * That is why the squared error is taken on a 2^-12 grid: the square of a 2^-24 error is up to 2^48, which overflows int64
+ * after 2^15 events -- inside one large image.
+ * hist: DEVICE int64 [per_image ? B : 1][R][n_bins + 1][4]; ignored: DEVICE int64 [per_image ? B : 1]; both += (a dataset total
+ * accumulates in place).  Everything accumulated is an integer: the result depends neither on the block order nor on the
+ * "deterministic" knob.  One launch (family "score_calibration", outside the NULL total), no workspace, no device
+ * allocation, no synchronisation.  The kernel never reads outside [offset, offset + H*W) of gt.  A sample with H*W > 2^31
+ * is not counted at all (the host wrapper refuses it).
+ * Refused with a message before anything is launched: null pointers; B outside 1..65535; S outside 1..32768; n_bins outside
+ * 1..HRSEG_CALIBRATION_MAX_BINS; hist, ignored or path_lut not 8-byte aligned; every limit of hrseg_decode_labels on nlevels,
+ * C and the tree (nlevels <= 8, C[L] <= 16, sum <= 64); an inv_temp[L] that is not finite and > 0; an uncovered channel. */
+#define HRSEG_CALIBRATION_MAX_BINS 32
+int hrseg_score_calibration(int nlevels, const float* const* z, const int* C, const hrseg_decode_tree_t* tree,
+                            const float* inv_temp /* HOST [nlevels] */, const unsigned char* gt, const long* gdesc,
+                            const unsigned long long* path_lut, int n_bins, long long* hist, long long* ignored,
+                            int B, int S, int per_image, hrseg_stream_t stream);
 
 /* ------------------------------------------------------------------ level synthesis for flat models (evaluation side; csrc/targets.hip)
  * predictEval.py:85-129 get_parent_masks (parent = union of its descendant leaves, "any > 0") and :134-185

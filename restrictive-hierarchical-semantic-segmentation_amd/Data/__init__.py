@@ -6,3 +6,4 @@ from .score import DeviceScore, SourceScores, build_score_tables  # noqa: F401
 from .postprocess import ComponentTables, DevicePostprocess, build_component_tables  # noqa: F401
 from .boundary import BoundaryScores, DeviceBoundaryScore  # noqa: F401
 from .instances import DeviceInstanceScore, InstanceScores  # noqa: F401
+from .calibration import CalibrationScores, DeviceCalibrationScore  # noqa: F401

@@ -149,6 +149,8 @@ PROTOTYPES = {
     "hrseg_score_boundaries": [_p, _p, _p, _p, _p, _p, _i, C.POINTER(C.c_int), _l, _i, _p, _p, _i, _p],
     "hrseg_mask_void_labels": [_p, _p, _p, _p, _p, _p, _i, _p, _i, _p],
     "hrseg_score_instances": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, C.POINTER(C.c_int), _p, _p, _p, _p, _p, _i, _i, _p],
+    "hrseg_score_calibration": [_i, _p, C.POINTER(C.c_int), C.POINTER(DecodeTree), C.POINTER(C.c_float), _p, _p, _p, _i, _p, _p,
+                                _i, _i, _i, _p],
     "hrseg_combine_levels": [_p, _i, _p, _i, _p, _p, _p, _i, _i, _l, _p],
     "hrseg_weight_images_refresh": [_p],
 }
@@ -251,7 +253,7 @@ def launch_count(family=None, reset=False) -> int:
     pipeline under "score_labels", test-time augmentation under "decode_views" / "flip_views", sliding-window inference
     under "window_crops" / "decode_windows", the post-processing under "label_components" / "filter_components", the
     boundary scoring under "score_boundaries", the instance scoring's masked copy and scoring launches under
-    "score_instances")"""
+    "score_instances", the calibration scoring under "score_calibration")"""
     return int(_lib.hrseg_launch_count(None if family is None else family.encode(), int(reset)))
 
 

@@ -950,6 +950,74 @@ def score_labels(pred, pdesc, pdesc_host, gt, gdesc, gdesc_host, tables, out=Non
     return counts, ignored
 
 
+CALIBRATION_MAX_BINS = 32
+
+
+def check_calibration_tables(tables, score_tables):
+    """the limits of hrseg_score_calibration on a Data.decode.DecodeTables and the Data.score.ScoreTables of the same levels:
+    those of decode_labels and score_labels, the same channel counts in both, and every channel of a child level in exactly
+    one child group (ValueError otherwise; needs no GPU)"""
+    check_decode_tables(tables)
+    check_score_tables(score_tables)
+    if list(tables.C) != list(score_tables.C):
+        raise ValueError(f"score_calibration: the decode tables have {list(tables.C)} channels per level, the path table "
+                         f"{list(score_tables.C)}")
+    for L in range(len(tables.C) - 1):
+        owner = [None] * tables.C[L + 1]
+        for p, (first, kids) in enumerate(zip(tables.first_child[L], tables.n_children[L])):
+            for c in range(first, first + kids):
+                if owner[c] is not None:
+                    raise ValueError(f"score_calibration: channel {c} of level {L + 1} is in the child groups of channels "
+                                     f"{owner[c]} and {p}")
+                owner[c] = p
+        for c, p in enumerate(owner):
+            if p is None:
+                raise ValueError(f"score_calibration: channel {c} of level {L + 1} is in no child group")
+
+
+def score_calibration(logits, tables, gt, score_tables, inv_temp=None, n_bins=15, out=None, per_image=False):
+    """per-level logits (list of [B,C_L,S,S] fp32 device tensors, or one tensor) + a Data.decode.DecodeTables against the
+    ground-truth maps gt = (packed uint8 device buffer, [B,4] int64 descriptors on the device, their host copy) + the
+    Data.score.ScoreTables of the same levels -> (hist [R, rows, n_bins + 1, 4] int64, ignored [R] int64), R = B (per_image)
+    or 1, rows = sum C_L + levels: the reliability records (n, pos, sum_q, sum_e2) as hrseg_score_calibration states them.
+    inv_temp: one fp32 value per level (None: all 1).  out = (hist, ignored) of an earlier call: both are added to.  One
+    launch, no synchronisation."""
+    check_calibration_tables(tables, score_tables)
+    logits, B, S = _decode_logits("score_calibration", logits, tables)
+    if S > DECODE_MAX_SIZE:
+        raise ValueError(f"score_calibration: logits of side {S}, at most {DECODE_MAX_SIZE}")
+    n_bins = int(n_bins)
+    if not 1 <= n_bins <= CALIBRATION_MAX_BINS:
+        raise ValueError(f"score_calibration: n_bins={n_bins}, supported 1..{CALIBRATION_MAX_BINS}")
+    inv = [1.0] * len(logits) if inv_temp is None else [float(v) for v in inv_temp]
+    if len(inv) != len(logits) or not all(0.0 < v < float("inf") for v in inv):
+        raise ValueError(f"score_calibration: inv_temp {inv} must hold one finite positive value per level ({len(logits)})")
+    gbuf, gdesc, ghost = gt
+    _check_ragged(gbuf, gdesc, ghost, (1,))
+    rows = ghost.tolist()
+    if len(rows) != B:
+        raise ValueError(f"score_calibration: logits of {B} samples against {len(rows)} ground-truth maps")
+    for b, (_, H, W, _) in enumerate(rows):
+        if H * W > SCORE_MAX_PIXELS:
+            raise ValueError(f"score_calibration: sample {b}: {H}x{W} has more than 2^31 pixels")
+    device = logits[0].device
+    if gbuf.device != device or gdesc.device != device:
+        raise ValueError("score_calibration: the logits and the ground truth live on different devices")
+    R, nrows = (B if per_image else 1), sum(tables.C) + len(tables.C)
+    shape = (R, nrows, n_bins + 1, 4)
+    if out is None:
+        hist, ignored = zeros(shape, torch.int64, device), zeros((R,), torch.int64, device)
+    else:
+        hist, ignored = out
+        for t, want in ((hist, shape), (ignored, (R,))):
+            if t.dtype != torch.int64 or not t.is_cuda or tuple(t.shape) != want or not t.is_contiguous():
+                raise ValueError(f"score_calibration: out must hold contiguous int64 device tensors of shapes {shape} and {(R,)}")
+    call("hrseg_score_calibration", len(logits), _lib.ptr_array(logits), _lib.int_array(list(tables.C)),
+         C.byref(_decode_tree_struct(tables)), (C.c_float * len(inv))(*inv), ptr(gbuf), ptr(gdesc),
+         ptr(score_tables.device_lut(device)), n_bins, ptr(hist), ptr(ignored), B, S, int(bool(per_image)))
+    return hist, ignored
+
+
 COMPONENTS_MAX_PIXELS = (1 << 31) - 1
 LABEL_COMPONENTS_LAUNCHES, FILTER_COMPONENTS_LAUNCHES = 3, 3
 

@@ -274,7 +274,9 @@ class Predictor:
     counts pixels of the map being produced -- the source's size in a call, the ground truth's size in `score` -- not
     pixels at network size.  postprocess=None: exactly the calls described above, no launch and no allocation more.
     `predictor.score_boundaries(images, labels)` decodes as `score` does and scores the outlines (Data/boundary.py);
-    `predictor.score_instances(images, labels)` likewise matches the objects of the two maps (Data/instances.py)."""
+    `predictor.score_instances(images, labels)` likewise matches the objects of the two maps (Data/instances.py);
+    `predictor.score_calibration(images, labels)` scores the plain path's logits themselves: reliability, ECE and Brier per
+    tree node (Data/calibration.py)."""
 
     def __init__(self, model, class_tree, class_map, args, want_confidence=False, keep_logits=False, tta=None, window=None,
                  postprocess=None):
@@ -282,6 +284,7 @@ class Predictor:
         self.model, self.class_tree, self.class_map, self.args = model, class_tree, class_map, args
         self.scorer, self.boundary_scorer, self.last_labels = None, None, None
         self.instance_scorer, self._instance_key = None, None
+        self.calibration_scorer, self._calibration_key = None, None
         self.size = int(args.img_size)
         self.decoder = DeviceDecode(class_tree, class_map, args.model_type)
         self.want_confidence = bool(want_confidence)
@@ -339,6 +342,46 @@ class Predictor:
         gt = self._ground_truth("Predictor.score_instances", images, labels)
         self.last_labels = self._predict(images, [(H, W) for _, H, W, _ in gt[2].tolist()])
         return self.instance_scorer.score(self.last_labels, gt)
+
+    @torch.no_grad()
+    def score_calibration(self, images, labels=None, n_bins=15, temperature=None, out=None, per_image=False):
+        """images and labels as for `score`: the eval-mode resize and forward of the plain path, then the logits -- not a
+        decoded map -- are scored against the labels on the device (Data/calibration.py; the scorer is kept per (n_bins,
+        temperature)) -> CalibrationScores; out accumulates a dataset total in place.  keep_logits=True keeps the logits in
+        `last_logits`.  The kernel reads single-view logits: with tta or window set the call is refused.  postprocess does
+        not matter to it (no map is produced)."""
+        from . import train as T
+        from .Data.calibration import DeviceCalibrationScore
+        from .Data.decode import pack_images
+        from .Data.loader import RaggedBatch
+        for what, on in (("tta", self.tta), ("window", self.window)):
+            if on is not None:
+                raise ValueError(f"Predictor.score_calibration: {what} is set, but the calibration kernel reads single-view "
+                                 "logits (multi-view and window variants are not implemented)")
+        key = (int(n_bins), tuple(float(v) for v in temperature) if isinstance(temperature, (tuple, list)) else
+               (None if temperature is None else float(temperature)))
+        if self.calibration_scorer is None or self._calibration_key != key:
+            self.calibration_scorer = DeviceCalibrationScore(self.class_tree, self.class_map, self.args.model_type, n_bins,
+                                                             temperature)
+            self._calibration_key = key
+        gt = self._ground_truth("Predictor.score_calibration", images, labels)
+        device = next(self.model.parameters()).device
+        if isinstance(images, RaggedBatch):
+            src, desc, desc_host = images.src, images.desc, images.desc_host
+        else:
+            src, desc_host = pack_images(images)
+            desc = desc_host
+        src, desc = src.to(device, non_blocking=True), desc.to(device, non_blocking=True)
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            x = ops.augment_image(src, desc, desc_host, None, self.size, False)
+            _, output_logits = T._model_call(self.model, x, self.args, self.class_tree)
+        finally:
+            self.model.train(was_training)
+        if self.keep_logits:
+            self.last_logits = output_logits
+        return self.calibration_scorer.score(output_logits, gt, out, per_image)
 
     @staticmethod
     def _ground_truth(who, images, labels):
@@ -425,7 +468,7 @@ def write_metrics_csv(path, accuracy, iou, dice, precision, recall, class_metric
 @torch.no_grad()
 def predict_loop(model, device, test_loader, args, class_tree, Accuracy, Iou, perf_measure, Precision, Recall,
                  save_dir=None, target_paths=None, label_dir=None, class_map=None, score_sources=False, postprocess=None,
-                 boundary=None, instances=None):
+                 boundary=None, instances=None, calibration=None):
     """The per-fold body of the reference's predict() (predictEval.py:305-573) on a built model and loader: eval-mode
     forward, prediction_prep, get_metrics per batch, optional PNG dump of each batch's first image and metrics.csv.
     -> dict(accuracy, iou, dice, precision, recall, class_metrics, performance).
@@ -449,7 +492,11 @@ def predict_loop(model, device, test_loader, args, class_tree, Accuracy, Iou, pe
     instances (a Data.DeviceInstanceScore; needs score_sources): the maps that are scored also have their connected
     components matched with those of the sources' label maps on the device (Data/instances.py).  The result gains the key
     "instances" -- the InstanceScores.summary() of the dataset -- and save_dir gets metrics_instances.csv, one row per thing
-    group plus "all".  instances=None: exactly the launches and files described above."""
+    group plus "all".  instances=None: exactly the launches and files described above.
+    calibration (a Data.DeviceCalibrationScore; needs score_sources): every batch's logits are also scored against the
+    sources' label maps on the device (Data/calibration.py), one launch per batch into one dataset total.  The result gains
+    the key "calibration" -- the CalibrationScores.summary() of the dataset -- and save_dir gets metrics_calibration.csv,
+    one row per tree node and "top@L" row.  calibration=None: exactly the launches and files described above."""
     import os
     import numpy as np
     from . import train as T
@@ -478,6 +525,9 @@ def predict_loop(model, device, test_loader, args, class_tree, Accuracy, Iou, pe
     matched = []
     if instances is not None and not score_sources:
         raise ValueError("instances needs score_sources=True (the sources' own label maps)")
+    calibrated = None
+    if calibration is not None and not score_sources:
+        raise ValueError("calibration needs score_sources=True (the sources' own label maps)")
     for i, batch in enumerate(test_loader):
         data, target = batch[0].to(device), batch[1].to(device)
         _, output_logits = T._model_call(model, data, args, class_tree)
@@ -516,6 +566,8 @@ def predict_loop(model, device, test_loader, args, class_tree, Accuracy, Iou, pe
                 outlines.append(boundary.score(decoded, batch[2]))
             if instances is not None:
                 matched.append(instances.score(decoded, batch[2]))
+            if calibration is not None:
+                calibrated = calibration.score(output_logits, batch[2], out=calibrated)
     if save_dir is not None:
         os.makedirs(save_dir, exist_ok=True)
         write_metrics_csv(os.path.join(save_dir, "metrics.csv"), acc2, iou2, dice2, prec2, rec2, cls2)
@@ -538,7 +590,25 @@ def predict_loop(model, device, test_loader, args, class_tree, Accuracy, Iou, pe
         result["instances"] = InstanceScores.cat(matched).summary()
         if save_dir is not None:
             write_instances_csv(os.path.join(save_dir, "metrics_instances.csv"), result["instances"])
+    if calibration is not None:
+        result["calibration"] = calibrated.summary()
+        if save_dir is not None:
+            write_calibration_csv(os.path.join(save_dir, "metrics_calibration.csv"), result["calibration"])
     return result
+
+
+def write_calibration_csv(path, summary):
+    """metrics_calibration.csv: one row per tree node and "top@L" row of a CalibrationScores.summary() (empty cells where a
+    row had no event), then the ignored pixels"""
+    import csv
+    keys = ("n", "prevalence", "mean_confidence", "ece", "mce", "brier", "nonfinite")
+    with open(path, "w", newline="") as f:
+        wr = csv.writer(f)
+        wr.writerow(["Row", "Events", "Prevalence", "MeanConfidence", "ECE", "MCE", "Brier", "NonFinite"])
+        for name, row in summary.items():
+            if isinstance(row, dict):
+                wr.writerow([name] + ["" if isinstance(row[k], float) and math.isnan(row[k]) else row[k] for k in keys])
+        wr.writerow(["ignored", summary["ignored"]] + [""] * 6)
 
 
 def write_instances_csv(path, summary):
