@@ -178,7 +178,8 @@ int hrseg_conv_wgrad_group_ws(int n, const float* const* x, const float* const* 
  * example mining: 1 launch per hrseg_ohem_scores, 7 per hrseg_ohem_select, 1 per hrseg_loss_partials_ohem / hrseg_loss_bwd_ohem call),
  * "label_components" / "filter_components" (post-processing) and "score_boundaries" (boundary scoring, HRSEG_SCORE_BOUNDARIES_LAUNCHES
  * per hrseg_score_boundaries call), "score_instances" (instance scoring) and "score_calibration" (calibration scoring, 1 launch
- * per hrseg_score_calibration call) are families of their own, outside the NULL total and the convolution counts. */
+ * per hrseg_score_calibration call) and "decode_hedged" (the hedged decode, 1 launch per hrseg_decode_hedged call) are families
+ * of their own, outside the NULL total and the convolution counts. */
 long hrseg_launch_count(const char* family, int reset);
 /* tile-plan overrides and A/B switches for the sweep tools under tools/ (value 0 = automatic plan).  Keys: igemm_wtm,
  * igemm_kc, igemm_db, igemm_ksplit, group_wtm, wgrad_pix, wgrad_db, wgrad_blocks, wgrad_group_mult,
@@ -684,6 +685,42 @@ typedef struct {
 int hrseg_decode_labels(int nlevels, const float* const* z, const int* C, const hrseg_decode_tree_t* tree,
                         const long* desc, unsigned char* labels, float* confidence, int B, int S,
                         hrseg_stream_t stream);
+
+/* ------------------------------------------------------------------ hedged decode (Data/hedge.py, csrc/decode_hedged.hip)
+ * hrseg_decode_hedged: the decode above, but the walk may end at the parent where the child is unsure.  Inputs as for
+ * hrseg_decode_labels plus the hedge table and a counter buffer.  Per output pixel:
+ *   1. steps 1-3 of hrseg_decode_labels unchanged: the same resampling, the same strict > arg-max, the same group
+ *      restriction; c_0, c_1, ... is the decode's path;
+ *   2. T_L is the decode's own running confidence after level L: sigmoid(z_0[c_0]) * prod_{l <= L} softmax_group(z_l)[c_l],
+ *      the same product in the same order and with the same rounding as the `confidence` output of hrseg_decode_labels
+ *      (as csrc/decode.hip spells it);
+ *   3. after choosing c_L the test T_L < tau[L][c_L] is made in fp32 with <; a NaN does not stop the walk, so all-zero
+ *      thresholds reproduce hrseg_decode_labels exactly, labels and confidence, non-finite values included.
+ *        - true at L == 0: the label is reject_val, the confidence T_0, the row "rejected" is counted;
+ *        - true at L >= 1: the label is stop_val[L-1][c_{L-1}], the confidence T_{L-1}, node (L-1, c_{L-1}) is counted; the
+ *          pixel fetches nothing deeper;
+ *        - otherwise, c_L a leaf: the label is its pixel value, the confidence T_L, node (L, c_L) is counted;
+ *        - otherwise the walk descends;
+ *   4. stops: DEVICE int64 [B][sum C + 2], accumulated with +=: one cell per tree node in breadth-first channel order, then
+ *      "rejected", then "nonfinite".  "nonfinite" counts the pixels whose confidence (step 3; counted whether or not it is
+ *      stored) is NaN, on top of their node cell, so the node cells plus "rejected" sum to H*W of the sample.  stops may be
+ *      NULL.  Everything counted is an integer: the same bytes in every run and under the "deterministic" knob.
+ * Refused, each with a message before anything is launched: every limit and alignment rule of hrseg_decode_labels;
+ * tree->root_softmax set (a flat model has no path to shorten); a tau outside [0, 1] or NaN; a stop_val of an internal node
+ * outside 0..255; reject_val outside -1..255, or -1 together with a non-zero level-0 tau; any two of {leaf values, internal
+ * stop_vals, reject_val} equal; stops not 8-byte aligned.  The sizes live in the device descriptor table, so H*W > 2^31 of a
+ * sample is refused by the host wrapper (ops.decode_hedged), as the scorers do it; the kernel leaves such a sample untouched
+ * (its 32-bit block counters could wrap).  Entries of tau and stop_val beyond the tree's channels are not read.
+ * 1 launch, family "decode_hedged" (never "decode_labels"), outside the NULL total; the tree, the thresholds and the stop
+ * values travel as kernel arguments: no workspace, no device allocation, no synchronisation. */
+typedef struct {
+  float tau[HRSEG_DECODE_MAX_LEVELS][HRSEG_DECODE_MAX_CHANNELS];      /* entering node (L, c) needs T_L >= tau[L][c]; 0 never stops */
+  int   stop_val[HRSEG_DECODE_MAX_LEVELS][HRSEG_DECODE_MAX_CHANNELS]; /* internal nodes: the byte written when the walk ends ON that node */
+  int   reject_val;                                                   /* byte written where level 0 itself fails; -1: no rejection (then every tau[0][c] must be 0) */
+} hrseg_hedge_t;
+int hrseg_decode_hedged(int nlevels, const float* const* z, const int* C, const hrseg_decode_tree_t* tree,
+                        const hrseg_hedge_t* hedge, const long* desc, unsigned char* labels, float* confidence,
+                        long long* stops, int B, int S, hrseg_stream_t stream);
 
 /* ------------------------------------------------------------------ test-time augmentation (predictEval.TestTimeAugment)
  * hrseg_decode_views: the decode above on the MEAN logit of an ensemble of views.  A view v is one set of per-level logits

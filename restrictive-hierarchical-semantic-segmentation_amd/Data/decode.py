@@ -15,7 +15,11 @@ test-time augmentation, predictEval.TestTimeAugment), still in one launch (csrc/
 predictEval.SlidingWindow), blended where they overlap, in one launch and without a canvas-size tensor (csrc/windows.hip);
 `plan_windows` lays the windows out on the host.
 
-The tables are built on the host without a GPU; only `decode` / `decode_views` / `decode_windows` launch.
+`decode_hedged` is `decode` with a policy (Data/hedge.py): where the composed confidence of the path falls below a node's
+threshold the pixel keeps the byte of the node above it, and the call counts how many pixels ended on every node
+(csrc/decode_hedged.hip) -> HedgedLabels.
+
+The tables are built on the host without a GPU; only `decode` / `decode_views` / `decode_windows` / `decode_hedged` launch.
 """
 from __future__ import annotations
 
@@ -182,6 +186,47 @@ class RaggedLabels:
         return None if self.confidence is None else self._split(self.confidence.cpu().numpy())
 
 
+class HedgedLabels(RaggedLabels):
+    """A hedged decode (`DeviceDecode.decode_hedged`): a RaggedLabels whose maps may hold internal nodes' bytes and the
+    reject value (`hedge.value_names`), plus `stops` [B, sum C + 2] int64 (device): the pixels ended per tree node in
+    breadth-first order, then "rejected", then "nonfinite" -- of this call, or of every call it was accumulated over."""
+
+    def __init__(self, labels, confidence, desc, desc_host, stops, hedge):
+        super().__init__(labels, confidence, desc, desc_host)
+        self.stops, self.hedge = stops, hedge
+
+    def summary(self):
+        """the counters summed over the batch, from ONE device-to-host copy: dict(
+        pixels: all pixels counted;
+        ended {node: pixels whose label is that node's byte};
+        abstained {internal node: ended[node] / (ended[node] + pixels ended below it)} -- of the pixels that entered the
+          node, the share that the hedge kept there (NaN where none entered);
+        coverage [per level]: the share of the pixels whose path was not cut before it settled on a node of that level --
+          1 - rejected / pixels at level 0, then minus the pixels the hedge stopped on the level above (a pixel whose path
+          ends in a shallower LEAF is not cut);
+        rejected, nonfinite: pixels)"""
+        t = self.hedge.tables
+        host = self.stops.sum(0).cpu().tolist()
+        nodes = sum(t.C)
+        cell0 = [sum(t.C[:L]) for L in range(len(t.C))]
+        total = sum(host[:nodes]) + host[nodes]
+        below = [[0] * n for n in t.C]                      # pixels ended on the node or anywhere below it
+        for L in range(len(t.C) - 1, -1, -1):
+            for c in range(t.C[L]):
+                kids = range(t.first_child[L][c], t.first_child[L][c] + t.n_children[L][c]) if t.n_children[L][c] else ()
+                below[L][c] = host[cell0[L] + c] + sum(below[L + 1][k] for k in kids)
+        ended, abstained, coverage, cut = {}, {}, [], host[nodes]
+        for L, names in enumerate(t.names):
+            coverage.append(1.0 - cut / total if total else float("nan"))
+            for c, name in enumerate(names):
+                ended[name] = host[cell0[L] + c]
+                if t.n_children[L][c]:
+                    abstained[name] = host[cell0[L] + c] / below[L][c] if below[L][c] else float("nan")
+                    cut += host[cell0[L] + c]
+        return dict(pixels=total, ended=ended, abstained=abstained, coverage=coverage, rejected=host[nodes],
+                    nonfinite=host[nodes + 1])
+
+
 class DeviceDecode:
     """`dec = DeviceDecode(class_tree, class_map, model_type); out = dec.decode(output_logits, desc, desc_host)` with
     the models' `output_logits` (a list of per-level [B,C_L,S,S] tensors, or the flat model's single tensor) and the label
@@ -214,6 +259,26 @@ class DeviceDecode:
     def decode_sizes(self, output_logits, sizes, want_confidence=False) -> RaggedLabels:
         """decode to a densely packed batch of the given [(H, W), ...]"""
         return self.decode(output_logits, label_desc(sizes), None, want_confidence)
+
+    def decode_hedged(self, output_logits, hedge, desc, desc_host=None, want_confidence=False, out=None) -> HedgedLabels:
+        """`decode` that stops at the parent where the child is unsure: `hedge` is a Data.Hedge of this decoder's tree
+        (model_type 1 only).  With all-zero thresholds the maps and the confidence are `decode`'s, bit for bit.  out: a
+        HedgedLabels of an earlier call with the same batch size, whose counters this call adds to (the returned object
+        shares them): a dataset total accumulates in place.  One launch (csrc/decode_hedged.hip)."""
+        require_gpu()
+        if self.model_type == 0:
+            raise ValueError("decode_hedged: model_type 0 (a flat model) has no path to shorten")
+        if hedge.tables.names != self.tables.names or hedge.tables.pixel_val != self.tables.pixel_val:
+            raise ValueError("decode_hedged: the hedge was built for another class tree or class map")
+        logits = [output_logits] if torch.is_tensor(output_logits) else list(output_logits)
+        desc, desc_host = self._descriptors(desc, desc_host, logits)
+        labels, conf, stops = ops.decode_hedged(logits, hedge, desc, desc_host, want_confidence,
+                                                None if out is None else out.stops)
+        return HedgedLabels(labels, conf, desc, desc_host, stops, hedge)
+
+    def decode_hedged_sizes(self, output_logits, hedge, sizes, want_confidence=False, out=None) -> HedgedLabels:
+        """decode_hedged to a densely packed batch of the given [(H, W), ...]"""
+        return self.decode_hedged(output_logits, hedge, label_desc(sizes), None, want_confidence, out)
 
     def decode_views(self, views, desc, desc_host=None, want_confidence=False) -> RaggedLabels:
         """test-time augmentation: `views` is a list of (output_logits, flags), each the logits of the same batch as the

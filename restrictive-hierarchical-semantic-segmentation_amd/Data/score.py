@@ -45,9 +45,14 @@ class ScoreTables:
         return self._lut[key]
 
 
-def build_score_tables(class_tree, class_map) -> ScoreTables:
+def build_score_tables(class_tree, class_map, internal_values=None) -> ScoreTables:
     """class_tree + class_map (any form TargetEncoder accepts) -> ScoreTables.  KeyError for a leaf without a pixel value,
-    ValueError for one outside uint8 (both as Data.decode.build_tables) and for two leaves sharing a value."""
+    ValueError for one outside uint8 (both as Data.decode.build_tables) and for two leaves sharing a value.
+    internal_values ({internal node name: byte}, e.g. a Data.Hedge's `values`): each such byte gets a path entry that ENDS
+    at that node, with zero bytes below it -- a prediction of that byte competes down to the node and falls into the
+    synthetic-background column of the levels below, as hrseg_score_labels states it for a path that ends above the ground
+    truth's leaf.  The consequence on the other side: such a byte in a GROUND-TRUTH map then counts as labelled down to that
+    node (row 0 of the levels below) instead of being ignored.  None builds exactly the leaf-only table."""
     name2pix = TargetEncoder._name2pix(class_map)
     index = TreeIndex(class_tree)
     levels = index.levels
@@ -65,6 +70,20 @@ def build_score_tables(class_tree, class_map) -> ScoreTables:
         node = leaf
         while node is not None:
             if index.depth[node] < 8:                   # (deeper trees are refused below, by their level count)
+                path[v] |= (1 + chan[node]) << (8 * index.depth[node])
+            node = index.parent[node]
+    for name, v in (internal_values or {}).items():
+        if name not in chan or not index.children[name]:
+            raise ValueError(f"internal value for '{name}', which is no internal node of the class tree")
+        v = int(v)
+        if not 0 <= v <= 255:
+            raise ValueError(f"value {v} of internal node '{name}' does not fit a uint8 label image")
+        if v in owner:
+            raise ValueError(f"classes '{owner[v]}' and '{name}' share the pixel value {v}")
+        owner[v] = name
+        node = name
+        while node is not None:
+            if index.depth[node] < 8:
                 path[v] |= (1 + chan[node]) << (8 * index.depth[node])
             node = index.parent[node]
     tables = ScoreTables(path, [len(n) for n in levels], [list(n) for n in levels])
@@ -107,11 +126,12 @@ class SourceScores:
 class DeviceScore:
     """`sc = DeviceScore(class_tree, class_map); scores = sc.score(pred, gt)` with `pred` a RaggedLabels (DeviceDecode /
     Predictor) or a (buffer, desc, desc_host) triple, `gt` a RaggedBatch (its label / ldesc / ldesc_host) or such a triple
-    -> SourceScores.  out: a SourceScores of an earlier call with the same per_image and batch size, which is added to."""
+    -> SourceScores.  out: a SourceScores of an earlier call with the same per_image and batch size, which is added to.
+    internal_values: bytes of internal nodes (build_score_tables), for scoring hedged maps (Data.Hedge.values)."""
 
-    def __init__(self, class_tree, class_map):
+    def __init__(self, class_tree, class_map, internal_values=None):
         self.class_tree = class_tree
-        self.tables = build_score_tables(class_tree, class_map)
+        self.tables = build_score_tables(class_tree, class_map, internal_values)
 
     @staticmethod
     def _triple(x, fields):

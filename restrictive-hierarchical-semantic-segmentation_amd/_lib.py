@@ -66,6 +66,11 @@ class DecodeTree(C.Structure):
     _fields_ = [("first_child", (_i * 16) * 8), ("n_children", (_i * 16) * 8), ("pixel_val", (_i * 16) * 8), ("root_softmax", _i)]
 
 
+class Hedge(C.Structure):
+    """hrseg_hedge_t"""
+    _fields_ = [("tau", (_f * 16) * 8), ("stop_val", (_i * 16) * 8), ("reject_val", _i)]
+
+
 # name -> argtypes, exactly the prototypes of include/hrseg.h
 PROTOTYPES = {
     "hrseg_conv_fwd_group": [_i, _p, _p, _p, _p, C.POINTER(ConvShape), _p],
@@ -138,6 +143,7 @@ PROTOTYPES = {
     "hrseg_augment_image": [_p, _p, _p, _p, _i, _i, _i, _p, C.c_size_t, _p],
     "hrseg_augment_targets": [_p, _p, _p, C.POINTER(C.c_int), _p, _p, _i, _i, _i, _i, _i, _p, C.c_size_t, _p],
     "hrseg_decode_labels": [_i, _p, C.POINTER(C.c_int), C.POINTER(DecodeTree), _p, _p, _p, _i, _i, _p],
+    "hrseg_decode_hedged": [_i, _p, C.POINTER(C.c_int), C.POINTER(DecodeTree), C.POINTER(Hedge), _p, _p, _p, _p, _i, _i, _p],
     "hrseg_decode_views": [_i, C.POINTER(C.c_int), C.POINTER(C.c_int), _i, _p, C.POINTER(C.c_int), C.POINTER(DecodeTree), _p, _p, _p,
                            _i, _p],
     "hrseg_flip_views": [_p, _p, _i, C.POINTER(C.c_int), _i, _i, _i, _i, _p],
@@ -253,7 +259,7 @@ def launch_count(family=None, reset=False) -> int:
     pipeline under "score_labels", test-time augmentation under "decode_views" / "flip_views", sliding-window inference
     under "window_crops" / "decode_windows", the post-processing under "label_components" / "filter_components", the
     boundary scoring under "score_boundaries", the instance scoring's masked copy and scoring launches under
-    "score_instances", the calibration scoring under "score_calibration")"""
+    "score_instances", the calibration scoring under "score_calibration", the hedged decode under "decode_hedged")"""
     return int(_lib.hrseg_launch_count(None if family is None else family.encode(), int(reset)))
 
 

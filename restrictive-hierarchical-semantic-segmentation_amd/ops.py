@@ -734,6 +734,78 @@ def decode_labels(logits, tables, desc, desc_host, want_confidence=False):
     return labels, conf
 
 
+HEDGE_MAX_PIXELS = 1 << 31
+
+
+def check_hedge(hedge):
+    """the rules of hrseg_decode_hedged on a Data.hedge.Hedge (or anything with its host tables `tables` -- a
+    Data.decode.DecodeTables --, `tau` and `stop_val` per level and channel, `reject_val`): the limits of decode_labels, a
+    tree model, thresholds in [0, 1], internal stop values and the reject value in uint8, no rejection (-1) only with all-zero
+    level-0 thresholds, and no byte written by two of {leaves, internal nodes, rejection}.  The messages name the nodes
+    (ValueError otherwise; needs no GPU)."""
+    tables = hedge.tables
+    check_decode_tables(tables)
+    if tables.root_softmax:
+        raise ValueError("decode_hedged: model_type 0 (a flat model) has no path to shorten")
+    name = lambda L, c: f"'{tables.names[L][c]}'" if tables.names else f"(level {L}, channel {c})"      # noqa: E731
+    reject = int(hedge.reject_val)
+    if not -1 <= reject <= 255:
+        raise ValueError(f"decode_hedged: reject value {reject} not in -1..255")
+    owner = {} if reject < 0 else {reject: "the reject value"}
+    for L, n in enumerate(tables.C):
+        if len(hedge.tau[L]) != n or len(hedge.stop_val[L]) != n:
+            raise ValueError(f"decode_hedged: the hedge tables of level {L} do not have {n} entries")
+        for c in range(n):
+            t = float(hedge.tau[L][c])
+            if not 0.0 <= t <= 1.0:                                            # (a NaN fails both comparisons)
+                raise ValueError(f"decode_hedged: threshold {t} of {name(L, c)} is not in 0..1")
+            if L == 0 and t != 0.0 and reject < 0:
+                raise ValueError(f"decode_hedged: {name(L, c)} has the level-0 threshold {t}, but there is no reject value")
+            v = int(tables.pixel_val[L][c])
+            if tables.n_children[L][c]:
+                v = int(hedge.stop_val[L][c])
+                if not 0 <= v <= 255:
+                    raise ValueError(f"decode_hedged: internal node {name(L, c)} has the stop value {v}, not in 0..255")
+            if v in owner:
+                raise ValueError(f"decode_hedged: {owner[v]} and {name(L, c)} share the byte {v}")
+            owner[v] = name(L, c)
+
+
+def _hedge_struct(hedge):
+    h = _lib.Hedge()
+    for L, n in enumerate(hedge.tables.C):
+        for c in range(n):
+            h.tau[L][c] = float(hedge.tau[L][c])
+            h.stop_val[L][c] = int(hedge.stop_val[L][c])
+    h.reject_val = int(hedge.reject_val)
+    return h
+
+
+def decode_hedged(logits, hedge, desc, desc_host, want_confidence=False, stops=None):
+    """decode_labels that stops at the parent where the child is unsure (hrseg_decode_hedged): per-level logits + a
+    Data.hedge.Hedge + [B,4] int64 label descriptors (device, and their host copy) -> (packed uint8 labels, packed fp32
+    confidence or None, stops [B, sum C + 2] int64: pixels ended per tree node in breadth-first order, then "rejected", then
+    "nonfinite").  stops = the counters of an earlier call with the same batch size: they are added to.  The tables are
+    read afresh on every call.  One launch, no synchronisation."""
+    check_hedge(hedge)
+    tables = hedge.tables
+    logits, B, S = _decode_logits("decode_hedged", logits, tables)
+    n = _decode_desc("decode_hedged", desc, desc_host, B)
+    for b, (_, H, W, _) in enumerate(desc_host.tolist()):
+        if H * W > HEDGE_MAX_PIXELS:
+            raise ValueError(f"decode_hedged: sample {b}: {H}x{W} has more than 2^31 pixels")
+    device = logits[0].device
+    shape = (B, sum(tables.C) + 2)
+    if stops is None:
+        stops = zeros(shape, torch.int64, device)
+    elif stops.dtype != torch.int64 or not stops.is_cuda or tuple(stops.shape) != shape or not stops.is_contiguous():
+        raise ValueError(f"decode_hedged: stops must be a contiguous int64 device tensor of shape {shape}")
+    labels, conf = _decode_outputs(n, device, want_confidence)
+    call("hrseg_decode_hedged", len(logits), _lib.ptr_array(logits), _lib.int_array(list(tables.C)),
+         C.byref(_decode_tree_struct(tables)), C.byref(_hedge_struct(hedge)), ptr(desc), ptr(labels), ptr(conf), ptr(stops), B, S)
+    return labels, conf, stops
+
+
 DECODE_MAX_VIEWS, DECODE_MAX_SIZE = 8, 32768
 VIEW_HFLIP, VIEW_VFLIP = 1, 2
 

@@ -276,11 +276,24 @@ class Predictor:
     `predictor.score_boundaries(images, labels)` decodes as `score` does and scores the outlines (Data/boundary.py);
     `predictor.score_instances(images, labels)` likewise matches the objects of the two maps (Data/instances.py);
     `predictor.score_calibration(images, labels)` scores the plain path's logits themselves: reliability, ECE and Brier per
-    tree node (Data/calibration.py)."""
+    tree node (Data/calibration.py).
+    hedge=Data.Hedge(...): the plain path decodes hedged (Data.DeviceDecode.decode_hedged): a pixel whose composed
+    confidence falls below a node's threshold keeps the byte of the node above it (`hedge.value_names`).  The call returns
+    a HedgedLabels (the maps plus the `stops` counters of the call), `score` scores the hedged maps with a DeviceScore
+    built with `hedge.values` and `last_labels` is the HedgedLabels.  hedge together with tta, window or postprocess is
+    refused (multi-view, window and cleaned-up hedged maps are not implemented), and so is model_type 0.  hedge=None:
+    exactly the calls described above."""
 
     def __init__(self, model, class_tree, class_map, args, want_confidence=False, keep_logits=False, tta=None, window=None,
-                 postprocess=None):
+                 postprocess=None, hedge=None):
         from .Data.decode import DeviceDecode
+        if hedge is not None:
+            for what, on in (("tta", tta), ("window", window), ("postprocess", postprocess)):
+                if on is not None:
+                    raise ValueError(f"Predictor: hedge together with {what} is not supported")
+            if int(args.model_type) == 0:
+                raise ValueError("Predictor: hedge needs a hierarchical model; model_type 0 has no path to shorten")
+        self.hedge = hedge
         self.model, self.class_tree, self.class_map, self.args = model, class_tree, class_map, args
         self.scorer, self.boundary_scorer, self.last_labels = None, None, None
         self.instance_scorer, self._instance_key = None, None
@@ -310,7 +323,7 @@ class Predictor:
         RaggedBatch's own label maps) -> SourceScores of the maps decoded at the labels' sizes"""
         from .Data.score import DeviceScore
         if self.scorer is None:
-            self.scorer = DeviceScore(self.class_tree, self.class_map)
+            self.scorer = DeviceScore(self.class_tree, self.class_map, None if self.hedge is None else self.hedge.values)
         gt = self._ground_truth("Predictor.score", images, labels)
         self.last_labels = self._predict(images, [(H, W) for _, H, W, _ in gt[2].tolist()])
         return self.scorer.score(self.last_labels, gt, out, per_image)
@@ -449,6 +462,8 @@ class Predictor:
         else:
             if self.keep_logits:
                 self.last_logits = output_logits
+            if self.hedge is not None:
+                return self.decoder.decode_hedged(output_logits, self.hedge, ldesc, None, self.want_confidence)
             maps = self.decoder.decode(output_logits, ldesc, None, self.want_confidence)
         return maps if self.postprocess is None else self.postprocess.apply(maps)
 
@@ -468,7 +483,7 @@ def write_metrics_csv(path, accuracy, iou, dice, precision, recall, class_metric
 @torch.no_grad()
 def predict_loop(model, device, test_loader, args, class_tree, Accuracy, Iou, perf_measure, Precision, Recall,
                  save_dir=None, target_paths=None, label_dir=None, class_map=None, score_sources=False, postprocess=None,
-                 boundary=None, instances=None, calibration=None):
+                 boundary=None, instances=None, calibration=None, hedge=None):
     """The per-fold body of the reference's predict() (predictEval.py:305-573) on a built model and loader: eval-mode
     forward, prediction_prep, get_metrics per batch, optional PNG dump of each batch's first image and metrics.csv.
     -> dict(accuracy, iou, dice, precision, recall, class_metrics, performance).
@@ -496,7 +511,15 @@ def predict_loop(model, device, test_loader, args, class_tree, Accuracy, Iou, pe
     calibration (a Data.DeviceCalibrationScore; needs score_sources): every batch's logits are also scored against the
     sources' label maps on the device (Data/calibration.py), one launch per batch into one dataset total.  The result gains
     the key "calibration" -- the CalibrationScores.summary() of the dataset -- and save_dir gets metrics_calibration.csv,
-    one row per tree node and "top@L" row.  calibration=None: exactly the launches and files described above."""
+    one row per tree node and "top@L" row.  calibration=None: exactly the launches and files described above.
+    hedge (a Data.Hedge; with label_dir or score_sources): every source-size map is decoded hedged
+    (Data.DeviceDecode.decode_hedged) before it is written or scored; the scorer is built with `hedge.values`, so a
+    prediction that ends on an internal node competes down to that node.  The `stops` counters accumulate over the
+    dataset (batch rows summed; every hedged decode that ran is counted, so where label_dir and score_sources decode one
+    batch at different sizes, both maps are); the result gains the key "hedge" -- their HedgedLabels.summary() -- and save_dir gets
+    metrics_hedge.csv, one row per tree node, then "rejected" and "nonfinite".  hedge together with postprocess, boundary or
+    instances is refused (they read leaf maps), and so is model_type 0.  hedge=None: exactly the launches and files
+    described above."""
     import os
     import numpy as np
     from . import train as T
@@ -505,6 +528,24 @@ def predict_loop(model, device, test_loader, args, class_tree, Accuracy, Iou, pe
     acc2, iou2, dice2, prec2, rec2, perf = [], [], [], [], [], []
     cls2 = T._new_class_metrics(n_cls)
     decoder, n_images = None, 0
+    hedge_stops = None
+    if hedge is not None:
+        for what, on in (("postprocess", postprocess), ("boundary", boundary), ("instances", instances)):
+            if on is not None:
+                raise ValueError(f"predict_loop: hedge together with {what} is not supported")
+        if int(args.model_type) == 0:
+            raise ValueError("predict_loop: hedge needs a hierarchical model; model_type 0 has no path to shorten")
+        if label_dir is None and not score_sources:
+            raise ValueError("hedge needs label_dir or score_sources=True (a source-size decode to hedge)")
+
+    def decode_maps(dec, logits, ldesc):
+        nonlocal hedge_stops
+        if hedge is None:
+            return dec.decode(logits, ldesc)
+        maps = dec.decode_hedged(logits, hedge, ldesc)
+        total = maps.stops.sum(0, keepdim=True)
+        hedge_stops = total if hedge_stops is None else hedge_stops + total
+        return maps
     if label_dir is not None:
         from .Data.decode import DeviceDecode, label_desc
         if class_map is None:
@@ -516,7 +557,7 @@ def predict_loop(model, device, test_loader, args, class_tree, Accuracy, Iou, pe
         from .Data.score import DeviceScore, SourceScores
         if class_map is None:
             raise ValueError("score_sources needs the class_map (leaf pixel values)")
-        scorer = DeviceScore(class_tree, class_map)
+        scorer = DeviceScore(class_tree, class_map, None if hedge is None else hedge.values)
         if source_decoder is None:
             source_decoder = DeviceDecode(class_tree, class_map, args.model_type)
     outlines = []
@@ -547,7 +588,7 @@ def predict_loop(model, device, test_loader, args, class_tree, Accuracy, Iou, pe
             sizes = [(H, W) for _, H, W, _ in batch[2].desc_host.tolist()]
             names = [os.path.basename(target_paths[n_images + j]) if target_paths is not None else f"{n_images + j:05d}.png"
                      for j in range(len(sizes))]
-            decoded = decoder.decode(output_logits, label_desc(sizes))
+            decoded = decode_maps(decoder, output_logits, label_desc(sizes))
             if postprocess is not None:
                 decoded = postprocess.apply(decoded)
             save_label_maps(label_dir, names, decoded)
@@ -558,7 +599,7 @@ def predict_loop(model, device, test_loader, args, class_tree, Accuracy, Iou, pe
                                  "e.g. DeviceAugmentLoader(..., with_sources=True)")
             gt_sizes = [(H, W) for _, H, W, _ in batch[2].ldesc_host.tolist()]
             if decoder is None or gt_sizes != sizes:
-                decoded = source_decoder.decode(output_logits, label_desc(gt_sizes))
+                decoded = decode_maps(source_decoder, output_logits, label_desc(gt_sizes))
                 if postprocess is not None:
                     decoded = postprocess.apply(decoded)
             scored.append(scorer.score(decoded, batch[2]))
@@ -594,7 +635,31 @@ def predict_loop(model, device, test_loader, args, class_tree, Accuracy, Iou, pe
         result["calibration"] = calibrated.summary()
         if save_dir is not None:
             write_calibration_csv(os.path.join(save_dir, "metrics_calibration.csv"), result["calibration"])
+    if hedge is not None:
+        from .Data.decode import HedgedLabels
+        result["hedge"] = HedgedLabels(None, None, None, None, hedge_stops, hedge).summary()
+        if save_dir is not None:
+            write_hedge_csv(os.path.join(save_dir, "metrics_hedge.csv"), result["hedge"])
     return result
+
+
+def write_hedge_csv(path, summary):
+    """metrics_hedge.csv: one row per tree node of a HedgedLabels.summary() (pixels ended there, its share of all pixels, the
+    abstained share of an internal node; empty cells where a share has no denominator), then "rejected" and "nonfinite",
+    then the coverage per level"""
+    import csv
+    total = summary["pixels"]
+    share = lambda n: n / total if total else ""        # noqa: E731
+    with open(path, "w", newline="") as f:
+        wr = csv.writer(f)
+        wr.writerow(["Row", "Pixels", "Share", "Abstained"])
+        for name, n in summary["ended"].items():
+            a = summary["abstained"].get(name, "")
+            wr.writerow([name, n, share(n), "" if isinstance(a, float) and math.isnan(a) else a])
+        for name in ("rejected", "nonfinite"):
+            wr.writerow([name, summary[name], share(summary[name]), ""])
+        for L, c in enumerate(summary["coverage"]):
+            wr.writerow([f"coverage@{L}", "", "" if math.isnan(c) else c, ""])
 
 
 def write_calibration_csv(path, summary):
