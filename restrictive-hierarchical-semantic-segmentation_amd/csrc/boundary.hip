@@ -9,8 +9,9 @@
 //      per-image bitmap / distance-map sizes into the table at the head of the workspace; an image whose descriptors are
 //      not acceptable, or that would not fit the sizes the host computed, is flagged and skipped by every later launch.
 //   2. bd_mark_kernel, grid (blocks, B): a wave takes 64 consecutive pixels of a row.  A lane turns its pixel of both maps
-//      into paths (the table in LDS; the prediction's path is dropped where the ground truth is unlabelled), gets the west /
-//      east neighbours' paths by shuffle and the north / south ones by load, and per level and map ballots the lanes that
+//      into paths (the table in LDS, its entries passed through LM_PATH_ENTRY of labelmap_common.h; the prediction's path is
+//      dropped where the ground truth is unlabelled), gets the west / east neighbours' paths by shuffle and the north /
+//      south ones by load, and per level and map ballots the lanes that
 //      are border pixels of the same node: the two halves of the ballot ARE the two bitmap words, stored by lanes 0 and 32
 //      where they are not zero.  Border pixels are counted per block in LDS, then one 64-bit atomic per non-zero cell.
 //   3. bd_search_kernel, grid (blocks, 2 N, B): a block belongs to one (node, direction); it leaves at once when either set is
@@ -30,11 +31,7 @@
 // A node absent from either map is never searched or selected: its fields other than n keep the zeros of launch 1.
 #include <limits.h>
 
-#include "common.h"
-
-typedef unsigned char u8;
-typedef unsigned u32;
-typedef unsigned long long u64;
+#include "labelmap_common.h"
 
 #define BD_TPB 256
 #define BD_WAVES (BD_TPB / HRSEG_WAVE)
@@ -44,7 +41,6 @@ typedef unsigned long long u64;
 #define BD_SEG_K 256
 #define BD_SEG_PREFIX 257
 #define BD_FIELDS 5
-#define BD_PEEL 4
 #define BD_PROBE 32                                    // horizontal reach of the wave's first round
 #define BD_LOCAL 3                                     // rows above and below that a lane tries alone: decides d2 <= 16
 #define BD_MAX_SIDE HRSEG_BOUNDARY_MAX_SIDE
@@ -102,12 +98,6 @@ __device__ __forceinline__ BdImage bd_image(const BdWs& ws, const long long* __r
   im.W = (int)pdesc[4 * b + 2];
   im.wpr = (im.W + 31) / 32;
   return im;
-}
-
-__device__ __forceinline__ int bd_wave_min(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  return v;
 }
 
 // floor(sqrt(d2 << 32)): the distance in 16.16 fixed point.  The floating-point root is a first guess only; the two loops
@@ -190,15 +180,9 @@ __global__ __launch_bounds__(BD_TPB) void bd_mark_kernel(BdArgs a, BdWs ws, cons
   const long long nchunks = (long long)H * cpr;
   if ((long long)blockIdx.x * BD_WAVES >= nchunks) return;
   {
-    // the path table: an entry that names a channel outside its level, or no level-0 node, counts as "no leaf"
-    u64 e = path_lut[tid];
-    bool ok = e != 0;
-#pragma unroll
-    for (int L = 0; L < BD_MAX_LEVELS; ++L) {
-      const int c = (int)((e >> (8 * L)) & 0xffu);
-      if (L >= a.nlevels ? c != 0 : (c > a.C[L] || (L == 0 && c == 0))) ok = false;
-    }
-    lut[tid] = ok ? e : 0;
+    u64 e = path_lut[tid];                                                    // BD_TPB == 256: one table entry per thread
+    LM_PATH_ENTRY(e, a)
+    lut[tid] = e;
   }
   if (tid < 2 * BD_MAX_NODES) cnt[tid] = 0;
   __syncthreads();
@@ -307,7 +291,7 @@ __device__ __forceinline__ int bd_nearest(const u32* __restrict__ T, int H, int 
       const int dx = min(bd_word_dx(vm, m, x), min(bd_word_dx(va, a, x), bd_word_dx(vb, b, x)));
       if (dx < BD_FAR) cand = dl0 * dl0 + dx * dx;
     }
-    best = bd_wave_min(cand);
+    best = lm_wave_min(cand);
   }
   // bounded: d0 grows by 32 per round and the loop ends once the rows at offset d0 lie outside the image on both sides
   for (int d0 = 0; d0 <= y || d0 <= H - 1 - y; d0 += 32) {
@@ -320,7 +304,7 @@ __device__ __forceinline__ int bd_nearest(const u32* __restrict__ T, int H, int 
       const int dx = bd_row(T + (size_t)yy * wpr, W, x, r);
       if (dx < BD_FAR) cand = dl * dl + dx * dx;
     }
-    best = min(best, bd_wave_min(cand));
+    best = min(best, lm_wave_min(cand));
   }
   return best;
 }
@@ -403,22 +387,7 @@ __global__ __launch_bounds__(BD_TPB) void bd_search_kernel(BdArgs a, BdWs ws, co
 }
 
 // ------------------------------------------------------------------------------------------------ 4. nearest-rank select
-// every lane with `has` adds 1 to hist[key]; called by whole waves.  Equal keys of a wave are added once (BD_PEEL rounds:
-// real outlines have a few distances many times), what is left adds for itself.
-__device__ __forceinline__ void bd_wave_add(u32* hist, u32 key, bool has, int lane) {
-  u64 todo = __ballot(has);
-  for (int it = 0; it < BD_PEEL && todo; ++it) {
-    const int leader = __ffsll((long long)todo) - 1;
-    const u32 k = (u32)__builtin_amdgcn_readlane((int)key, leader);
-    const bool same = has && key == k;
-    const u64 m = __ballot(same);
-    if (lane == leader) atomicAdd(&hist[k], (u32)__popcll(m));
-    has = has && !same;
-    todo &= ~m;
-  }
-  if (has) atomicAdd(&hist[key], 1u);
-}
-
+// (the digits go through lm_wave_add: real outlines have a few distances many times)
 __global__ __launch_bounds__(BD_TPB) void bd_hist_kernel(BdArgs a, BdWs ws, const long long* __restrict__ pdesc,
                                                          const long long* __restrict__ gdesc, int shift, const u64* __restrict__ records) {
   __shared__ u32 hist[256];
@@ -447,7 +416,7 @@ __global__ __launch_bounds__(BD_TPB) void bd_hist_kernel(BdArgs a, BdWs ws, cons
         w &= w - 1;
       }
       const bool match = has && (shift == 24 || (v >> (shift + 8)) == (prefix >> (shift + 8)));
-      bd_wave_add(hist, (v >> shift) & 0xffu, match, lane);
+      lm_wave_add(hist, (v >> shift) & 0xffu, 1u, match, lane);
     }
   }
   __syncthreads();
@@ -500,16 +469,14 @@ static int bd_levels(const char* who, int nlevels, const int* C, BdArgs* a) {
   return 0;
 }
 
-// rows [0, B) of the host table: every image acceptable -> words of all bitmaps / distance maps, words and chunks of the largest
+// rows [0, B) of the host table: every image acceptable (lm_host_image, then this unit's side limit) -> words of all bitmaps / distance maps, words and chunks of the largest
 static int bd_scan(const char* who, const long* desc_host, int B, const BdArgs& a, u64* bm_words, u64* d2_words, long long* max_words,
                    long long* max_chunks) {
   *bm_words = *d2_words = 0;
   *max_words = *max_chunks = 0;
   for (int b = 0; b < B; ++b) {
-    const long long off = desc_host[4 * b], H = desc_host[4 * b + 1], W = desc_host[4 * b + 2], ch = desc_host[4 * b + 3];
-    HRSEG_CHECK_ARG(off >= 0 && H >= 1 && W >= 1 && ch == 1, "%s: image %d: bad descriptor (offset %lld, %lld x %lld, %lld channels)", who,
-                    b, off, H, W, ch);
-    HRSEG_CHECK_ARG(H <= ((1ll << 31) - 1) / W, "%s: image %d: %lld x %lld has 2^31 pixels or more", who, b, H, W);
+    long long off, H, W;
+    if (int rc = lm_host_image(who, "", desc_host, b, &off, &H, &W)) return rc;
     HRSEG_CHECK_ARG(H <= BD_MAX_SIDE && W <= BD_MAX_SIDE, "%s: image %d: %lld x %lld, a side above %d", who, b, H, W, BD_MAX_SIDE);
     u64 wb, wd;
     bd_image_words(H, W, a.N, a.nlevels, &wb, &wd);
@@ -554,12 +521,7 @@ extern "C" int hrseg_score_boundaries(const unsigned char* pred, const long* pde
   u64 gb, gd;
   long long gw, gc;
   if (int rc = bd_scan(who, desc_host + 4 * (size_t)B, B, a, &gb, &gd, &gw, &gc)) return rc;
-  for (int b = 0; b < B; ++b) {
-    const long* p = desc_host + 4 * (size_t)b;
-    const long* g = p + 4 * (size_t)B;
-    HRSEG_CHECK_ARG(p[1] == g[1] && p[2] == g[2], "%s: image %d: predicted map %ld x %ld, ground truth %ld x %ld", who, b, p[1], p[2], g[1],
-                    g[2]);
-  }
+  if (int rc = lm_host_same_sizes(who, desc_host, B)) return rc;
   ws.tab = (u64*)workspace;
   ws.seg = (u32*)((char*)workspace + (size_t)B * 16);
   ws.bm = ws.seg + (size_t)B * a.N * 2 * BD_SEG_WORDS;

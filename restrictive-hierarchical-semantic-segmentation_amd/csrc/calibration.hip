@@ -23,11 +23,9 @@
 // a block counts pixels of one image, H*W <= 2^31, so n and pos fit 32 bits): 24 bytes per cell, sized per launch -- 3.8 KB for
 // the tl tree at 15 bins, 57 KB at the limits (72 rows x 33 bins).  At the block's end the non-zero words go to the int64
 // records with 64-bit vector atomics.  Real maps are dominated by confident background, so most lanes of a wave add to the
-// same cell; the LDS atomic unit serialises them.  Folding equal cells inside the wave first (as score.hip does) has not been
-// tried: the sums are 64-bit and differ per lane.
+// same cell; the LDS atomic unit serialises them.  Folding equal cells inside the wave first (lm_wave_add, labelmap_common.h)
+// has not been tried: the sums are 64-bit and differ per lane.
 #include "decode_common.h"
-
-typedef unsigned long long u64;
 
 #define CAL_TPB DEC_TPB
 #define CAL_ROWS (CAL_TPB / HRSEG_WAVE)            // rows per tile: one per wave
@@ -83,14 +81,9 @@ __global__ __launch_bounds__(CAL_TPB) void score_calibration_kernel(CalArgs a, c
   for (int i = tid; i <= words; i += CAL_TPB) hist[i] = 0;
   if (tid < DEC_NODES) tab[tid] = a.node[tid];
   {
-    u64 e = path_lut[tid];                         // CAL_TPB == 256: one table entry per thread; validated as score.hip does
-    bool ok = e != 0;
-#pragma unroll
-    for (int L = 0; L < HRSEG_DECODE_MAX_LEVELS; ++L) {
-      const int c = (int)((e >> (8 * L)) & 0xffu);
-      if (L >= a.nlevels ? c != 0 : (c > a.C[L] || (L == 0 && c == 0))) ok = false;
-    }
-    lut[tid] = ok ? e : 0;
+    u64 e = path_lut[tid];                         // CAL_TPB == 256: one table entry per thread
+    LM_PATH_ENTRY(e, a)
+    lut[tid] = e;
   }
   __syncthreads();
 

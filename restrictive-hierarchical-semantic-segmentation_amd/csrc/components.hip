@@ -26,10 +26,7 @@
 //      block in LDS first.
 //   5. cc_filter_kernel: 16 pixels per lane (one aligned 16-byte load of the labels where the span allows), the verdict of
 //      a root is kept from pixel to pixel; statistics per block in LDS, then one 64-bit atomicAdd per non-zero cell.
-#include "common.h"
-
-typedef unsigned char u8;
-typedef unsigned long long u64;
+#include "labelmap_common.h"
 
 #define CC_TW HRSEG_COMPONENTS_TILE_W
 #define CC_TH HRSEG_COMPONENTS_TILE_H
@@ -221,12 +218,6 @@ __global__ __launch_bounds__(CC_MERGE_TPB) void cc_merge_kernel(const u8* __rest
 }
 
 // ------------------------------------------------------------------------------------------------ 3. roots and areas
-__device__ __forceinline__ int cc_wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(CC_TPB) void cc_flatten_kernel(const long long* __restrict__ desc, int* __restrict__ roots,
                                                             int* __restrict__ area) {
   __shared__ int block_key;
@@ -283,7 +274,7 @@ __global__ __launch_bounds__(CC_TPB) void cc_flatten_kernel(const long long* __r
       mine += cnt[j];
       cnt[j] = 0;
     }
-  mine = cc_wave_sum(mine);
+  mine = lm_wave_sum(mine);
   if (lane == 0 && mine) atomicAdd(&block_sum, mine);
   // ---- the other roots: once per wave where lanes share one, CC_PEEL rounds per run slot, then every lane for itself
 #pragma unroll
@@ -294,7 +285,7 @@ __global__ __launch_bounds__(CC_TPB) void cc_flatten_kernel(const long long* __r
       const int leader = __ffsll((long long)todo) - 1;
       const int k = __builtin_amdgcn_readlane(key[j], leader);
       const bool same = has && key[j] == k;
-      const int s = cc_wave_sum(same ? cnt[j] : 0);
+      const int s = lm_wave_sum(same ? cnt[j] : 0);
       if (lane == leader) atomicAdd(&A[k], s);
       has = has && !same;
       todo &= ~__ballot(same);
@@ -434,14 +425,13 @@ __global__ __launch_bounds__(CC_TPB) void cc_filter_kernel(const u8* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------------------ C ABI
-// the host copy of the descriptors: every image fits, H*W < 2^31; -> tiles and pixels of the largest image, bytes spanned
+// the host copy of the descriptors, every row acceptable to lm_host_image (labelmap_common.h: H*W < 2^31) -> tiles and
+// pixels of the largest image, bytes spanned
 static int cc_scan(const char* who, const long* desc_host, int B, long long* max_tiles, long long* max_hw, long long* extent) {
   *max_tiles = *max_hw = *extent = 0;
   for (int b = 0; b < B; ++b) {
-    const long long off = desc_host[4 * b], H = desc_host[4 * b + 1], W = desc_host[4 * b + 2], ch = desc_host[4 * b + 3];
-    HRSEG_CHECK_ARG(off >= 0 && H >= 1 && W >= 1 && ch == 1, "%s: image %d: bad descriptor (offset %lld, %lld x %lld, %lld channels)", who,
-                    b, off, H, W, ch);
-    HRSEG_CHECK_ARG(H <= ((1ll << 31) - 1) / W, "%s: image %d: %lld x %lld has 2^31 pixels or more", who, b, H, W);
+    long long off, H, W;
+    if (int rc = lm_host_image(who, "", desc_host, b, &off, &H, &W)) return rc;
     const long long tiles = ((W + CC_TW - 1) / CC_TW) * ((H + CC_TH - 1) / CC_TH);
     *max_tiles = tiles > *max_tiles ? tiles : *max_tiles;
     *max_hw = H * W > *max_hw ? H * W : *max_hw;

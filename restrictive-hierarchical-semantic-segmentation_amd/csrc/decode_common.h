@@ -2,9 +2,7 @@
 // blend of overlapping windows): the tile shape, the bilinear taps of one output coordinate, the arithmetic of a channel step and,
 // on the host, the validation and packing of the tree and the prelude and launch of the three entry points.
 #pragma once
-#include "common.h"
-
-typedef unsigned char u8;
+#include "labelmap_common.h"      // u8 / u32 / u64; calibration.hip and decode_hedged.hip also take its label-map helpers
 
 #define DEC_TPB 256
 #define DEC_PX 4                                  // pixels per lane: one dword of labels

@@ -15,9 +15,8 @@
 //     internal node's stop value -- so a pixel keeps (byte, counter cell, confidence) of the node it stands on and a
 //     failed test simply stops updating them;
 //   * counters: sum C + 2 32-bit cells per block in LDS (a block counts pixels of one image, H*W <= 2^31).  Confident
-//     background sends most lanes of a wave to one cell, so equal cells are folded before the LDS atomic as score.hip
-//     folds its pairs: a lane whose 4 pixels share a cell adds 4 once, the wave elects a leader per distinct cell and the
-//     leader adds count * popcount; after HDG_PEEL rounds the lanes left add for themselves.  At the block's end the
+//     background sends most lanes of a wave to one cell, so a lane whose 4 pixels share a cell adds 4 once, and equal
+//     cells of a wave are folded before the LDS atomic (lm_wave_add, labelmap_common.h).  At the block's end the
 //     non-zero cells go to the int64 table with one 64-bit vector atomic each.  Integer sums: the same bytes in every
 //     run, whatever the block order, so there is no deterministic variant.
 //
@@ -25,9 +24,6 @@
 // tables to LDS once because lanes index them with their own channel.
 #include "decode_common.h"
 
-typedef unsigned long long u64;
-
-#define HDG_PEEL 4
 #define HDG_MAX_CELLS (64 + 2)                      // sum C <= 64 tree nodes, then "rejected" and "nonfinite"
 
 struct HedgeArgs {
@@ -38,21 +34,6 @@ struct HedgeArgs {
   float tau[DEC_NODES];
   int nlevels, nodes, reject_val;                 // nodes = sum C: cell `nodes` is "rejected", `nodes + 1` "nonfinite"
 };
-
-// every lane with `has` adds `cnt` (the same in all of them) to cells[key]; called by whole waves
-__device__ __forceinline__ void hdg_wave_add(unsigned* cells, unsigned key, unsigned cnt, bool has, int lane) {
-  u64 todo = __ballot(has);
-  for (int it = 0; it < HDG_PEEL && todo; ++it) {
-    const int leader = __ffsll((long long)todo) - 1;
-    const unsigned k = (unsigned)__builtin_amdgcn_readlane((int)key, leader);
-    const bool same = has && key == k;
-    const u64 m = __ballot(same);
-    if (lane == leader) atomicAdd(&cells[k], cnt * (unsigned)__popcll(m));
-    has = has && !same;
-    todo &= ~m;
-  }
-  if (has) atomicAdd(&cells[key], cnt);
-}
 
 template <bool CONF>
 __global__ __launch_bounds__(DEC_TPB) void decode_hedged_kernel(HedgeArgs a, const long long* __restrict__ desc,
@@ -188,10 +169,10 @@ __global__ __launch_bounds__(DEC_TPB) void decode_hedged_kernel(HedgeArgs a, con
 
     if (stops) {                                                          // whole waves from here on
       const bool one = full && cell[1] == cell[0] && cell[2] == cell[0] && cell[3] == cell[0];
-      hdg_wave_add(cells, (unsigned)cell[0], DEC_PX, one, lane);
+      lm_wave_add(cells, (unsigned)cell[0], DEC_PX, one, lane);
       if (__ballot(!one && some) != 0) {
 #pragma unroll
-        for (int p = 0; p < DEC_PX; ++p) hdg_wave_add(cells, (unsigned)cell[p], 1, !one && in[p], lane);
+        for (int p = 0; p < DEC_PX; ++p) lm_wave_add(cells, (unsigned)cell[p], 1, !one && in[p], lane);
       }
       bool bad[DEC_PX];
       bool any = false;
@@ -202,7 +183,7 @@ __global__ __launch_bounds__(DEC_TPB) void decode_hedged_kernel(HedgeArgs a, con
       }
       if (__ballot(any) != 0) {
 #pragma unroll
-        for (int p = 0; p < DEC_PX; ++p) hdg_wave_add(cells, (unsigned)(a.nodes + 1), 1, bad[p], lane);
+        for (int p = 0; p < DEC_PX; ++p) lm_wave_add(cells, (unsigned)(a.nodes + 1), 1, bad[p], lane);
       }
     }
   }

@@ -23,11 +23,7 @@
 //   4. in_decide_kernel: at every true first pixel of a thing group the test 3 inter > |P| + |G| with the candidate's area;
 //      gmatch, ginter and pmatch[candidate] are written (a P has at most one partner: no two writers), the sums per block
 //      in LDS, then one 64-bit add per non-zero cell.
-#include "common.h"
-
-typedef unsigned char u8;
-typedef unsigned u32;
-typedef unsigned long long u64;
+#include "labelmap_common.h"
 
 #define IN_TPB 256
 #define IN_WAVES (IN_TPB / HRSEG_WAVE)
@@ -297,14 +293,13 @@ __global__ __launch_bounds__(IN_TPB) void in_decide_kernel(const long long* __re
 }
 
 // ------------------------------------------------------------------------------------------------------------ C ABI
-// rows [0, B) of a host table by the rules of hrseg_label_components -> pixels of the largest image, bytes spanned
+// rows [0, B) of a host table, each acceptable to lm_host_image (labelmap_common.h) -> pixels of the largest image, bytes
+// spanned
 static int in_scan(const char* who, const char* what, const long* desc_host, int B, long long* max_hw, long long* extent) {
   *max_hw = *extent = 0;
   for (int b = 0; b < B; ++b) {
-    const long long off = desc_host[4 * b], H = desc_host[4 * b + 1], W = desc_host[4 * b + 2], ch = desc_host[4 * b + 3];
-    HRSEG_CHECK_ARG(off >= 0 && H >= 1 && W >= 1 && ch == 1, "%s: %s image %d: bad descriptor (offset %lld, %lld x %lld, %lld channels)", who,
-                    what, b, off, H, W, ch);
-    HRSEG_CHECK_ARG(H <= ((1ll << 31) - 1) / W, "%s: %s image %d: %lld x %lld has 2^31 pixels or more", who, what, b, H, W);
+    long long off, H, W;
+    if (int rc = lm_host_image(who, what, desc_host, b, &off, &H, &W)) return rc;
     *max_hw = H * W > *max_hw ? H * W : *max_hw;
     *extent = off + H * W > *extent ? off + H * W : *extent;
   }
@@ -314,15 +309,9 @@ static int in_scan(const char* who, const char* what, const long* desc_host, int
 // both halves of the [2][B][4] host table, and that they agree on every size
 static int in_tables(const char* who, const long* desc_host, int B, long long* max_hw, long long* pext, long long* gext) {
   long long ghw;
-  if (int rc = in_scan(who, "predicted", desc_host, B, max_hw, pext)) return rc;
-  if (int rc = in_scan(who, "ground-truth", desc_host + 4 * (size_t)B, B, &ghw, gext)) return rc;
-  for (int b = 0; b < B; ++b) {
-    const long* p = desc_host + 4 * (size_t)b;
-    const long* g = p + 4 * (size_t)B;
-    HRSEG_CHECK_ARG(p[1] == g[1] && p[2] == g[2], "%s: image %d: predicted map %ld x %ld, ground truth %ld x %ld", who, b, p[1], p[2], g[1],
-                    g[2]);
-  }
-  return 0;
+  if (int rc = in_scan(who, "predicted ", desc_host, B, max_hw, pext)) return rc;
+  if (int rc = in_scan(who, "ground-truth ", desc_host + 4 * (size_t)B, B, &ghw, gext)) return rc;
+  return lm_host_same_sizes(who, desc_host, B);
 }
 
 static inline unsigned in_steps(long long max_hw) { return (unsigned)((max_hw + IN_TPB * IN_STEPS - 1) / (IN_TPB * IN_STEPS)); }
@@ -334,7 +323,7 @@ extern "C" size_t hrseg_instances_workspace_bytes(const long* desc_host, int B) 
     return 0;
   }
   long long hw, gext;
-  if (in_scan(who, "ground-truth", desc_host + 4 * (size_t)B, B, &hw, &gext)) return 0;
+  if (in_scan(who, "ground-truth ", desc_host + 4 * (size_t)B, B, &hw, &gext)) return 0;
   return (size_t)gext * 8 + (((size_t)gext * 4 + 7) & ~(size_t)7);
 }
 

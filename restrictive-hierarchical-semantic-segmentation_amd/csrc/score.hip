@@ -8,25 +8,21 @@
 // last step leaves at once.  The kernel reads 2 bytes per pixel; what it has to manage is contention: real maps are
 // dominated by one pair (background on background).  So a block counts PAIRS OF LEAVES, not cells of the level
 // matrices, and folds equal pairs three times before an LDS atomic is issued:
-//   0. setup: thread v reads path_lut[v], drops an entry that names a channel outside its level, and numbers the
-//      remaining ones (ballot + popcount prefix): leaf ids 1..NL <= 64 per byte value, the path of every leaf id.
+//   0. setup: thread v reads path_lut[v], drops an entry that is no leaf (LM_PATH_ENTRY, labelmap_common.h), and numbers
+//      the remaining ones (ballot + popcount prefix): leaf ids 1..NL <= 64 per byte value, the path of every leaf id.
 //   1. a lane takes SCORE_LANE_STEP = 16 consecutive pixels of both maps.  The lane steps are cut at 16-byte boundaries of
 //      the PREDICTION span (one aligned 16-byte load); the ground-truth span starts at an unrelated byte, so the lane
 //      loads the 5 aligned dwords around its 16 bytes and funnel-shifts them (v_alignbyte).  Lanes whose 16 pixels or whose
 //      aligned windows would leave [offset, offset + H*W) of either buffer -- only the first and last of an image --
 //      load single bytes instead.  Runs fold in three tiers: all 16 pixels one pair / a dword of 4 pixels one pair /
 //      single pixels; a tier runs only when some lane of the wave needs it.
-//   2. inside a tier every participating lane holds one key and the same count (16, 4 or 1): the wave elects the first
-//      such lane, ballots the lanes with the same key and the leader adds count * popcount once; after SCORE_PEEL such
-//      rounds the lanes that are left (many distinct pairs: a noisy map) add for themselves.
+//   2. inside a tier every participating lane holds one key and the same count (16, 4 or 1): equal keys of a wave are
+//      folded before the LDS atomic (lm_wave_add, labelmap_common.h).
 //   3. LDS: a 64 x 64 histogram of leaf pairs (+ the two ignored counts), 32-bit: a block counts pixels of ONE image,
 //      H*W <= 2^31.
 // Flush: every non-zero pair is expanded into one cell per level of a second LDS array (the level matrices, side by side),
 // whose non-zero cells go to the int64 counts with one 64-bit atomic add each.
-#include "common.h"
-
-typedef unsigned char u8;
-typedef unsigned long long u64;
+#include "labelmap_common.h"
 
 #define SCORE_TPB 256
 #define SCORE_LANE_STEP HRSEG_SCORE_LANE_STEP       // 16: the tests take the three step sizes from the header
@@ -40,7 +36,6 @@ static_assert(SCORE_LANE_STEP == 16 && SCORE_WAVE_STEP == HRSEG_WAVE * SCORE_LAN
 #define SCORE_IGN_PRED (SCORE_PAIRS + 1)
 #define SCORE_MAX_CELLS (HRSEG_SCORE_MAX_CHANNELS * HRSEG_SCORE_MAX_CHANNELS + \
                          (HRSEG_SCORE_MAX_LEVELS - 1) * (HRSEG_SCORE_MAX_CHANNELS + 1) * (HRSEG_SCORE_MAX_CHANNELS + 1))
-#define SCORE_PEEL 4
 #define SCORE_BLOCKS 1024                          // blocks of a launch, over all samples
 
 struct ScoreArgs {
@@ -99,39 +94,24 @@ __device__ __forceinline__ unsigned score_key(const u8* leafid, unsigned g, unsi
   return gi == 0 ? SCORE_IGN_GT : (pi == 0 ? SCORE_IGN_PRED : (gi - 1) * SCORE_MAX_LEAVES + (pi - 1));
 }
 
-// every lane with `has` adds `cnt` (the same in all of them) to hist[key]; called by whole waves
-__device__ __forceinline__ void score_wave_add(unsigned* hist, unsigned key, unsigned cnt, bool has, int lane) {
-  u64 todo = __ballot(has);
-  for (int it = 0; it < SCORE_PEEL && todo; ++it) {
-    const int leader = __ffsll((long long)todo) - 1;
-    const unsigned k = (unsigned)__builtin_amdgcn_readlane((int)key, leader);
-    const bool same = has && key == k;
-    const u64 m = __ballot(same);
-    if (lane == leader) atomicAdd(&hist[k], cnt * (unsigned)__popcll(m));
-    has = has && !same;
-    todo &= ~m;
-  }
-  if (has) atomicAdd(&hist[key], cnt);
-}
-
 __device__ __forceinline__ void score_count(unsigned* hist, const u8* leafid, const ScoreTile& t, int lane) {
   if (__ballot(t.valid != 0) == 0) return;
   const unsigned p0 = (t.p[0] & 0xffu) * 0x01010101u, g0 = (t.g[0] & 0xffu) * 0x01010101u;
   const bool one = t.valid == 0xffffu && t.p[0] == p0 && t.p[1] == p0 && t.p[2] == p0 && t.p[3] == p0 && t.g[0] == g0 &&
                    t.g[1] == g0 && t.g[2] == g0 && t.g[3] == g0;
-  score_wave_add(hist, score_key(leafid, t.g[0] & 0xffu, t.p[0] & 0xffu), SCORE_LANE_STEP, one, lane);
+  lm_wave_add(hist, score_key(leafid, t.g[0] & 0xffu, t.p[0] & 0xffu), SCORE_LANE_STEP, one, lane);
   const bool rest = !one && t.valid != 0;
   if (__ballot(rest) == 0) return;
 #pragma unroll
   for (int d = 0; d < 4; ++d) {
     const unsigned pd = t.p[d], gd = t.g[d], vd = (t.valid >> (4 * d)) & 0xfu;
     const bool four = rest && vd == 0xfu && pd == (pd & 0xffu) * 0x01010101u && gd == (gd & 0xffu) * 0x01010101u;
-    score_wave_add(hist, score_key(leafid, gd & 0xffu, pd & 0xffu), 4, four, lane);
+    lm_wave_add(hist, score_key(leafid, gd & 0xffu, pd & 0xffu), 4, four, lane);
     const bool single = rest && !four && vd != 0;
     if (__ballot(single) == 0) continue;
     for (int j = 0; j < 4; ++j) {
       const bool has = single && ((vd >> j) & 1u);
-      score_wave_add(hist, score_key(leafid, (gd >> (8 * j)) & 0xffu, (pd >> (8 * j)) & 0xffu), 1, has, lane);
+      lm_wave_add(hist, score_key(leafid, (gd >> (8 * j)) & 0xffu, (pd >> (8 * j)) & 0xffu), 1, has, lane);
     }
   }
 }
@@ -161,15 +141,7 @@ __global__ __launch_bounds__(SCORE_TPB) void score_labels_kernel(ScoreArgs a, co
   for (int i = tid; i < SCORE_PAIRS + 2; i += SCORE_TPB) hist[i] = 0;
   for (int i = tid; i < a.total; i += SCORE_TPB) cells[i] = 0;
   u64 e = path_lut[tid];                                               // SCORE_TPB == 256: one table entry per thread
-  {
-    bool ok = e != 0;
-#pragma unroll
-    for (int L = 0; L < HRSEG_SCORE_MAX_LEVELS; ++L) {
-      const int c = (int)((e >> (8 * L)) & 0xffu);
-      if (L >= a.nlevels ? c != 0 : (c > a.C[L] || (L == 0 && c == 0))) ok = false;
-    }
-    if (!ok) e = 0;
-  }
+  LM_PATH_ENTRY(e, a)
   const u64 nz = __ballot(e != 0);
   if (lane == 0) wave_leaves[wave] = __popcll(nz);
   __syncthreads();

@@ -964,7 +964,8 @@ SCORE_MAX_PIXELS = 1 << 31
 
 def check_score_tables(tables):
     """the limits of hrseg_score_labels on a Data.score.ScoreTables: <= 8 levels, <= 16 channels per level, <= 64 in all,
-    and a path table whose bytes name channels of their levels (ValueError otherwise; needs no GPU)"""
+    and a path table whose bytes name channels of their levels (ValueError otherwise; needs no GPU).  The path rule is
+    the one the kernels apply entry by entry: LM_PATH_ENTRY in csrc/labelmap_common.h is its device-side statement."""
     Cs = list(tables.C)
     if not 1 <= len(Cs) <= SCORE_MAX_LEVELS:
         raise ValueError(f"score_labels: {len(Cs)} levels, supported 1..{SCORE_MAX_LEVELS}")

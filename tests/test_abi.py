@@ -161,6 +161,65 @@ def test_group_table_refusals_name_their_entry_point():
             assert rc == -1 and f"{name}: {want}" in msg, (name, bad, msg)
 
 
+def test_host_descriptor_refusals_name_their_entry_point():
+    """The seven entry points that read a host descriptor table refuse a bad row, an image of 2^31 pixels or more and (the
+    three that take a [2][B][4] pair) unequal sizes with the full message behind their own name, before anything is launched
+    (placeholder pointers, never dereferenced; only the host table, C and the thresholds are real memory)"""
+    from hrseg_amd import _lib
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    lib.hrseg_last_error_string.restype = ctypes.c_char_p
+    P, one, zeros = ctypes.c_void_p(4096), _lib.int_array([2]), _lib.int_array([0, 0, 0, 0])
+    protos = dict(_lib.PROTOTYPES)
+    protos.update(_lib.RAW_PROTOTYPES)
+    # name -> (call(table), halves of the table, the word in front of "image" per half)
+    entry = {
+        "hrseg_label_components": (lambda t: (P, P, t, 1, P, 8, P, P, None), 1, ("",)),
+        "hrseg_filter_components": (lambda t: (P, P, t, 1, P, P, P, P, P, P, P, None), 1, ("",)),
+        "hrseg_boundary_workspace_bytes": (lambda t: (t, 1, 1, one), 1, ("",)),
+        "hrseg_score_boundaries": (lambda t: (P, P, P, P, t, P, 1, one, 0, 50, P, P, 1, None), 2, ("", "")),
+        "hrseg_instances_workspace_bytes": (lambda t: (t, 1), 2, (None, "ground-truth ")),     # reads the second half only
+        "hrseg_mask_void_labels": (lambda t: (P, P, P, P, t, P, -1, P, 1, None), 2, ("predicted ", "ground-truth ")),
+        "hrseg_score_instances": (lambda t: (P, P, P, P, P, P, P, P, t, P, P, zeros, P, P, P, P, P, 1, 0, None), 2,
+                                  ("predicted ", "ground-truth ")),
+    }
+    assert len(entry) == 7
+    good = (0, 4, 5, 1)
+
+    def call(name, rows):
+        fn = getattr(lib, name)
+        fn.argtypes = protos[name]
+        sizes = name.endswith("_workspace_bytes")
+        fn.restype = ctypes.c_size_t if sizes else ctypes.c_int
+        table = (ctypes.c_long * (4 * len(rows)))(*[v for row in rows for v in row])
+        rc = fn(*entry[name][0](ctypes.cast(table, ctypes.c_void_p)))
+        return (rc, 0 if sizes else -1), lib.hrseg_last_error_string().decode()
+
+    for name, (_, halves, words) in entry.items():
+        for half, what in enumerate(words):
+            if what is None:
+                continue
+
+            def refused(row):
+                rows = [good] * halves
+                rows[half] = row
+                (rc, want), msg = call(name, rows)
+                assert rc == want, (name, row, rc)
+                return msg
+            for row in ((-1, 4, 5, 1), (0, 0, 5, 1), (0, 4, 0, 1), (0, 4, 5, 3)):
+                off, H, W, ch = row
+                assert refused(row) == f"{name}: {what}image 0: bad descriptor (offset {off}, {H} x {W}, {ch} channels)", (name, row)
+            assert refused((0, 65536, 32768, 1)) == f"{name}: {what}image 0: 65536 x 32768 has 2^31 pixels or more", name
+    for name in ("hrseg_score_boundaries", "hrseg_mask_void_labels", "hrseg_score_instances"):
+        (rc, want), msg = call(name, [(0, 4, 5, 1), (0, 4, 6, 1)])
+        assert rc == want and msg == f"{name}: image 0: predicted map 4 x 5, ground truth 4 x 6", (name, msg)
+    # only the boundary scorer has a side limit below 2^31 pixels
+    for name in ("hrseg_boundary_workspace_bytes", "hrseg_score_boundaries"):
+        (rc, want), msg = call(name, [(0, 40000, 4, 1)] * entry[name][1])
+        assert rc == want and msg == f"{name}: image 0: 40000 x 4, a side above 32768", (name, msg)
+    (rc, _), _ = call("hrseg_instances_workspace_bytes", [(0, 40000, 4, 1)] * 2)
+    assert rc == 160000 * 8 + 160000 * 4, "40000 x 4 is an image like any other to the instance scorer"
+
+
 KNOBS = ["igemm_wtm", "igemm_kc", "igemm_db", "igemm_ksplit", "group_wtm", "wgrad_pix", "wgrad_db", "wgrad_blocks",
          "wgrad_group_mult", "wgrad_group_min", "wgrad_group_max", "sp_wtm", "sp_wtn", "sp_ksplit", "sp_patch", "sp_persist",
          "sp_ws", "sp_ws_waste", "small_cin3", "sp_ws_bf16", "sp_ws_n48", "sp_img", "wgrad9", "ws_epi_early", "exp_nosplit_x",
