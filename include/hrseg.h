@@ -658,6 +658,45 @@ int hrseg_augment_targets(const unsigned char* label, const long* desc, const un
                           const int* parent, const float* params, float* y, int B, int C, int S, int warp,
                           int antialias, void* work, size_t work_bytes, hrseg_stream_t stream);
 
+/* ------------------------------------------------------------------ partial labels (csrc/targets.hip, csrc/augment.hip)
+ * Label maps that say less than a leaf per pixel: an IGNORE byte (the pixel takes no part in loss or gradient) and the byte
+ * of an INTERNAL node ("tooth", child unknown: the pixel supervises the levels down to that node and nothing below).  This
+ * is the one statement of the semantics; everything else refers here.
+ *
+ * Every byte v has two sets over the emitted channels (all nodes breadth first, or the leaves in flat mode):
+ *   leaf byte               on[v] = the leaf and its ancestors             unk[v] = empty
+ *   internal byte of node n on[v] = n and its ancestors (where channels)   unk[v] = every channel strictly below n
+ *   ignore byte             on[v] = empty                                  unk[v] = every channel
+ *   any other byte          on[v] = empty                                  unk[v] = empty
+ * Channel c of a pixel with the sets (ON, UNK):
+ *   1. 1 if c is in ON;  2. else -1 if c is in UNK;  3. else 0 if c is a root or its direct parent is in ON;  4. else -1.
+ * With UNK empty this is the rule of hrseg_encode_targets.  So a "tooth" pixel has tooth and its ancestors 1, their
+ * siblings 0, and every channel below tooth -1 (with tooth a root: the other roots 0, everything below level 0 -1); an ignored pixel is -1 in every channel, level 0
+ * included; in flat mode an internal byte gives -1 on the leaves below the node and 0 on the others.  The loss kernels mask
+ * per channel with t != -1, and a pixel whose channels are all -1 at a level gets a gradient of exactly 0 there.
+ *
+ * Resized targets accumulate two coverages per channel over the footprint of hrseg_augment_targets, with exactly its
+ * weights, order and fp32 arithmetic: cover_on[c] = sum of w where on_c holds, cover_may[c] = sum of w where on_c or unk_c
+ * holds.  ON_c = cover_on[c] >= 0.5, MAY_c = cover_may[c] >= 0.5, UNK_c = MAY_c and not ON_c: a channel is called off (0)
+ * only where the known-off share of the footprint is the majority; other mixed footprints fall to unknown.  Adding the same
+ * non-negative terms in the same order is monotone in fp32, so cover_may >= cover_on and ON is a subset of MAY; with
+ * unk_lut all zero the two sums are bit-equal and the output is that of hrseg_augment_targets.  The nearest warp moves both
+ * thresholded sets.  Outside the source frame: fill_unknown == 0 is the rule of hrseg_augment_targets (ON = {channel 0} if
+ * channel 0 is covered anywhere in the image, else empty; UNK empty), fill_unknown != 0 sets ON empty and UNK to every
+ * channel (the corners a rotation brings in are unlabelled).  The image fill is the same either way.
+ *
+ * on_lut / unk_lut: DEVICE tables [256] of uint64 (bits at or above C are not read); everything else as for the entry
+ * points they stand next to.  hrseg_augment_workspace_partial: the warp workspace holds two uint64 per pixel plus the
+ * per-block flags.  Launches count under "augment_targets": 1 without the warp, 2 with. */
+int hrseg_encode_targets_partial(const unsigned char* label, const unsigned long long* on_lut,
+                                 const unsigned long long* unk_lut, const int* parent, float* out, int B, int C, long hw,
+                                 hrseg_stream_t stream);
+int hrseg_augment_workspace_partial(int B, int S, size_t* target_bytes);
+int hrseg_augment_targets_partial(const unsigned char* label, const long* desc, const unsigned long long* on_lut,
+                                  const unsigned long long* unk_lut, const int* parent, const float* params, float* y, int B,
+                                  int C, int S, int warp, int antialias, int fill_unknown, void* work, size_t work_bytes,
+                                  hrseg_stream_t stream);
+
 /* ------------------------------------------------------------------ device output pipeline (Data/decode.py)
  * The inverse of the input pipeline: per-level logits at network size -> one label map per source image, at the source's
  * own size, in the pixel values of class_map.csv.  z: HOST array of nlevels DEVICE pointers, level L is [B, C[L], S, S]

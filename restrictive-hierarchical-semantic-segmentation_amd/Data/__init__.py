@@ -1,4 +1,4 @@
-from .dataset import TargetEncoder  # noqa: F401
+from .dataset import TargetEncoder, build_target_luts  # noqa: F401
 from .loader import DeviceAugmentLoader, PngPairDataset, RaggedBatch, ragged_collate  # noqa: F401
 from .augment import DeviceAugment  # noqa: F401
 from .decode import DeviceDecode, HedgedLabels, RaggedLabels, WindowPlan, plan_windows, window_profile  # noqa: F401

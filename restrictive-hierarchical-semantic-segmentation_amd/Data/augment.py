@@ -107,16 +107,29 @@ class DeviceAugment:
 
     train=True: the reference's transform_input4train + hflip / vflip / affine of the train SegDataset; train=False:
     transform_input4test (resize + normalise), targets resized and encoded, no randomness.  target_antialias=False
-    selects torchvision < 0.17's plain bilinear resize of the masks."""
+    selects torchvision < 0.17's plain bilinear resize of the masks.
+
+    Partial labels (include/hrseg.h): internal_values / ignore_values as for TargetEncoder (`internal_values=h.values,
+    ignore_values=[h.reject_val]` trains on the hedged maps of a `Hedge` h); fill="ignore" marks what the affine warp brings in
+    from outside the source frame as unlabelled (-1 in every channel) instead of the reference's fill.  With none of the three
+    the object launches `hrseg_augment_targets` as before."""
 
     def __init__(self, img_size, class_tree, class_map, model_type=1, train=True, hflip=True, vflip=False, affine=True,
-                 target_antialias=True, seed=0, device="cuda"):
+                 target_antialias=True, seed=0, device="cuda", internal_values=None, ignore_values=(), fill="reference"):
         require_gpu()
+        if fill not in ("reference", "ignore"):
+            raise ValueError(f"fill '{fill}' is neither 'reference' nor 'ignore'")
+        self.fill = fill
         self.size, self.train = int(img_size), bool(train)
         self.hflip, self.vflip, self.affine, self.target_antialias = bool(hflip), bool(vflip), bool(affine), bool(target_antialias)
         if self.train and self.size <= 12:
             raise ValueError("train mode needs img_size > 12 (the 25x25 blur pads by reflection)")
-        self.encoder = TargetEncoder(class_tree, class_map, model_type, device=device)
+        self.encoder = TargetEncoder(class_tree, class_map, model_type, device=device, internal_values=internal_values,
+                                     ignore_values=ignore_values)
+        # the partial kernels run wherever the targets can hold an unknown: a table of them, or unlabelled corners
+        self.partial = self.encoder.partial or fill == "ignore"
+        if self.partial and self.encoder.unk_lut is None:
+            self.encoder.unk_lut = torch.zeros_like(self.encoder.on_lut)
         self.device = self.encoder.on_lut.device
         self.names = self.encoder.names
         self.generator = torch.Generator().manual_seed(int(seed))
@@ -140,6 +153,11 @@ class DeviceAugment:
             self.last_params = p
         dev = batch.to(self.device, non_blocking=True)
         x = ops.augment_image(dev.src, dev.desc, dev.desc_host, table, self.size, self.train)
-        y = ops.augment_targets(dev.label, dev.ldesc, dev.ldesc_host, self.encoder.on_lut, self.encoder.parent, table,
-                                self.size, self.train, self.target_antialias)
+        enc = self.encoder
+        if self.partial:
+            y = ops.augment_targets_partial(dev.label, dev.ldesc, dev.ldesc_host, enc.on_lut, enc.unk_lut, enc.parent, table,
+                                            self.size, self.train, self.target_antialias, self.fill == "ignore")
+        else:
+            y = ops.augment_targets(dev.label, dev.ldesc, dev.ldesc_host, enc.on_lut, enc.parent, table, self.size, self.train,
+                                    self.target_antialias)
         return x, y

@@ -142,6 +142,8 @@ PROTOTYPES = {
     "hrseg_encode_targets": [_p, _p, C.POINTER(C.c_int), _p, _i, _i, _l, _p],
     "hrseg_augment_image": [_p, _p, _p, _p, _i, _i, _i, _p, C.c_size_t, _p],
     "hrseg_augment_targets": [_p, _p, _p, C.POINTER(C.c_int), _p, _p, _i, _i, _i, _i, _i, _p, C.c_size_t, _p],
+    "hrseg_encode_targets_partial": [_p, _p, _p, C.POINTER(C.c_int), _p, _i, _i, _l, _p],
+    "hrseg_augment_targets_partial": [_p, _p, _p, _p, C.POINTER(C.c_int), _p, _p, _i, _i, _i, _i, _i, _i, _p, C.c_size_t, _p],
     "hrseg_decode_labels": [_i, _p, C.POINTER(C.c_int), C.POINTER(DecodeTree), _p, _p, _p, _i, _i, _p],
     "hrseg_decode_hedged": [_i, _p, C.POINTER(C.c_int), C.POINTER(DecodeTree), C.POINTER(Hedge), _p, _p, _p, _p, _i, _i, _p],
     "hrseg_decode_views": [_i, C.POINTER(C.c_int), C.POINTER(C.c_int), _i, _p, C.POINTER(C.c_int), C.POINTER(DecodeTree), _p, _p, _p,
@@ -170,6 +172,7 @@ RAW_PROTOTYPES = {
     "hrseg_set_scratch": [_p, C.c_size_t],
     "hrseg_set_weight_image_arena": [_p, C.c_size_t, _p, C.c_size_t, _p, _p, _p, _p],
     "hrseg_augment_workspace": [_i, _i, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)],
+    "hrseg_augment_workspace_partial": [_i, _i, C.POINTER(C.c_size_t)],
     "hrseg_grad_sumsq_chunk_len": [],
     "hrseg_grad_sumsq_max_blocks": [],
     "hrseg_grad_sumsq_chunks": [_l],

@@ -18,6 +18,7 @@
 // channel 0 takes max(mask0) -> 1 if any pixel of it survived the threshold, every other channel 0) and the encode.
 #include "common.h"
 #include "resize_u8.h"
+#include "target_encode.h"
 
 typedef unsigned char u8;
 typedef unsigned long long u64;
@@ -26,8 +27,6 @@ typedef unsigned long long u64;
 #define AUG_HALO 12
 #define AUG_IN (AUG_TILE + 2 * AUG_HALO)
 #define AUG_TPB 256
-
-struct AugParents { int parent[64]; };
 
 __device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.f), 1.f); }
 
@@ -244,72 +243,90 @@ __device__ __forceinline__ AaSpan aa_span(int dst, int in, int out) {
   return a;
 }
 
-__device__ __forceinline__ void encode_write(u64 m, const AugParents& pr, float* __restrict__ o, int C, size_t plane) {
-  for (int c = 0; c < C; ++c) {
-    const int par = pr.parent[c];
-    float v;
-    if ((m >> c) & 1ull) v = 1.f;
-    else if (par < 0 || ((m >> par) & 1ull)) v = 0.f;
-    else v = -1.f;
-    o[(size_t)c * plane] = v;
-  }
-}
+// One tap of weight w on the pixel value v: every accumulator of the chunk that starts at channel c0 (written out in the
+// kernel's own scope: through a function taking the arrays by reference the 64-wide instance needs 154 registers, not 109)
+#define AUG_COVER_TAP(v, w)                                                   \
+  do {                                                                        \
+    const u64 nb_ = lut[v] >> c0;                                             \
+    _Pragma("unroll") for (int c = 0; c < NC; ++c) acc[c] += ((nb_ >> c) & 1ull) ? (w) : 0.f; \
+    if constexpr (PARTIAL) {                                                  \
+      const u64 mb_ = mlut[v] >> c0;                                          \
+      _Pragma("unroll") for (int c = 0; c < NC; ++c) accm[c] += ((mb_ >> c) & 1ull) ? (w) : 0.f; \
+    }                                                                         \
+  } while (0)
 
 // coverage of every node at output pixel p of the un-warped frame, thresholded (< 0.5 -> 0); direct: encode and
-// write y, else write the bits and this block's "channel 0 covered anywhere" flag
-template <int NC>
+// write y, else write the bits and this block's "channel 0 covered anywhere" flag.
+// PARTIAL (partial labels, include/hrseg.h): a second accumulator per channel, may[c], adds the same weights in the same
+// order over the pixels where the node is on OR unknown, so may[c] >= on[c] and with unk_lut all zero the two are
+// bit-equal; UNK = (may >= 0.5) and not (on >= 0.5).  The channels go in chunks of NC, each chunk a walk of its own over
+// the footprint (one chunk wherever C <= NC); the bits of a pixel are two words, ON then UNK.
+template <int NC, bool PARTIAL>
 __global__ __launch_bounds__(AUG_TPB) void aug_targets_cover(const u8* __restrict__ label, const long long* __restrict__ desc,
-                                                             const u64* __restrict__ on_lut, AugParents pr,
-                                                             float* __restrict__ y, u64* __restrict__ bits,
+                                                             const u64* __restrict__ on_lut, const u64* __restrict__ unk_lut,
+                                                             TargetParents pr, float* __restrict__ y, u64* __restrict__ bits,
                                                              int* __restrict__ flags, int C, int S, int antialias, int direct) {
   __shared__ u64 lut[256];
+  __shared__ u64 mlut[PARTIAL ? 256 : 1];
   lut[threadIdx.x] = on_lut[threadIdx.x];
+  if constexpr (PARTIAL) mlut[threadIdx.x] = on_lut[threadIdx.x] | unk_lut[threadIdx.x];
   __syncthreads();
   const int b = blockIdx.y;
   const long p = (long)blockIdx.x * AUG_TPB + threadIdx.x;
   const size_t plane = (size_t)S * S;
   const bool valid = p < (long)plane;
-  u64 m = 0;
+  u64 m = 0, may = 0;
   if (valid) {
     const int i = (int)(p / S), j = (int)(p - (long)i * S);
     const long long off = desc[4 * b], H = desc[4 * b + 1], W = desc[4 * b + 2];
     const u8* l = label + off;
-    float acc[NC];
+    for (int c0 = 0; c0 < (PARTIAL ? C : 1); c0 += NC) {
+      float acc[NC], accm[PARTIAL ? NC : 1];
 #pragma unroll
-    for (int c = 0; c < NC; ++c) acc[c] = 0.f;
-    if (antialias) {
-      const AaSpan ay = aa_span(i, (int)H, S), ax = aa_span(j, (int)W, S);
-      for (int ky = 0; ky < ay.n; ++ky) {
-        const float wy = ay.total != 0.f ? aa_weight(ay, ky) / ay.total : aa_weight(ay, ky);
-        if (wy == 0.f) continue;
-        const u8* row = l + (long)(ay.lo + ky) * W + ax.lo;
-        for (int kx = 0; kx < ax.n; ++kx) {
-          const float wx = ax.total != 0.f ? aa_weight(ax, kx) / ax.total : aa_weight(ax, kx);
-          const float w = wy * wx;
-          const u64 nb = lut[row[kx]];
+      for (int c = 0; c < NC; ++c) acc[c] = 0.f;
+      if constexpr (PARTIAL) {
 #pragma unroll
-          for (int c = 0; c < NC; ++c) acc[c] += ((nb >> c) & 1ull) ? w : 0.f;
-        }
+        for (int c = 0; c < NC; ++c) accm[c] = 0.f;
       }
-    } else {
-      const Lin iy = lin_index(i, (float)H / (float)S, (int)H), ix = lin_index(j, (float)W / (float)S, (int)W);
-      const int ys[2] = {iy.i0, iy.i1}, xs[2] = {ix.i0, ix.i1};
-      const float wys[2] = {iy.l0, iy.l1}, wxs[2] = {ix.l0, ix.l1};
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const float w = wys[a] * wxs[q];
-          const u64 nb = lut[l[(long)ys[a] * W + xs[q]]];
-#pragma unroll
-          for (int c = 0; c < NC; ++c) acc[c] += ((nb >> c) & 1ull) ? w : 0.f;
+      if (antialias) {
+        const AaSpan ay = aa_span(i, (int)H, S), ax = aa_span(j, (int)W, S);
+        for (int ky = 0; ky < ay.n; ++ky) {
+          const float wy = ay.total != 0.f ? aa_weight(ay, ky) / ay.total : aa_weight(ay, ky);
+          if (wy == 0.f) continue;
+          const u8* row = l + (long)(ay.lo + ky) * W + ax.lo;
+          for (int kx = 0; kx < ax.n; ++kx) {
+            const float wx = ax.total != 0.f ? aa_weight(ax, kx) / ax.total : aa_weight(ax, kx);
+            const float w = wy * wx;
+            const u8 v = row[kx];
+            AUG_COVER_TAP(v, w);
+          }
         }
-    }
+      } else {
+        const Lin iy = lin_index(i, (float)H / (float)S, (int)H), ix = lin_index(j, (float)W / (float)S, (int)W);
+        const int ys[2] = {iy.i0, iy.i1}, xs[2] = {ix.i0, ix.i1};
+        const float wys[2] = {iy.l0, iy.l1}, wxs[2] = {ix.l0, ix.l1};
 #pragma unroll
-    for (int c = 0; c < NC; ++c)
-      if (c < C && acc[c] >= 0.5f) m |= 1ull << c;
-    if (direct) encode_write(m, pr, y + (size_t)b * C * plane + p, C, plane);
-    else bits[(size_t)b * plane + p] = m;
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int q = 0; q < 2; ++q) {
+            const float w = wys[a] * wxs[q];
+            const u8 v = l[(long)ys[a] * W + xs[q]];
+            AUG_COVER_TAP(v, w);
+          }
+      }
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        if (c0 + c < C && acc[c] >= 0.5f) m |= 1ull << (c0 + c);
+        if constexpr (PARTIAL)
+          if (c0 + c < C && accm[c] >= 0.5f) may |= 1ull << (c0 + c);
+      }
+    }
+    const u64 unk = may & ~m;
+    if (direct) encode_write(m, unk, pr, y + (size_t)b * C * plane + p, C, plane);
+    else if (PARTIAL) {
+      bits[2 * ((size_t)b * plane + p)] = m;
+      bits[2 * ((size_t)b * plane + p) + 1] = unk;
+    } else bits[(size_t)b * plane + p] = m;
   }
   if (!direct) {
     const int any = __syncthreads_or((int)(m & 1ull));
@@ -317,9 +334,14 @@ __global__ __launch_bounds__(AUG_TPB) void aug_targets_cover(const u8* __restric
   }
 }
 
+#undef AUG_COVER_TAP
+
+// the warp moves the thresholded sets; out of frame: ON = {channel 0} if channel 0 is covered anywhere in the image, UNK
+// empty (the reference's fill), or with fill_unknown (PARTIAL only) ON empty and UNK every channel
+template <bool PARTIAL>
 __global__ __launch_bounds__(AUG_TPB) void aug_targets_warp(const u64* __restrict__ bits, const int* __restrict__ flags,
-                                                            const float* __restrict__ params, AugParents pr,
-                                                            float* __restrict__ y, int C, int S) {
+                                                            const float* __restrict__ params, TargetParents pr,
+                                                            float* __restrict__ y, int C, int S, int fill_unknown) {
   const int b = blockIdx.y, nblk = gridDim.x;
   int any = 0;
   for (int t = threadIdx.x; t < nblk; t += AUG_TPB) any |= flags[(size_t)b * nblk + t];
@@ -329,9 +351,17 @@ __global__ __launch_bounds__(AUG_TPB) void aug_targets_warp(const u64* __restric
   if (p >= (long)plane) return;
   const int i = (int)(p / S), j = (int)(p - (long)i * S);
   int si, sj;
-  const u64 m = warp_source(params + (size_t)b * HRSEG_AUG_PARAMS, S, i, j, si, sj) ? bits[(size_t)b * plane + (size_t)si * S + sj]
-                                                                                   : (u64)(any ? 1 : 0);
-  encode_write(m, pr, y + (size_t)b * C * plane + p, C, plane);
+  const bool inside = warp_source(params + (size_t)b * HRSEG_AUG_PARAMS, S, i, j, si, sj);
+  const size_t src = (size_t)b * plane + (size_t)si * S + sj;
+  u64 m, unk = 0;
+  if (PARTIAL) {
+    const u64 all = C == 64 ? ~0ull : (1ull << C) - 1;
+    m = inside ? bits[2 * src] : (u64)(!fill_unknown && any ? 1 : 0);
+    unk = inside ? bits[2 * src + 1] : (fill_unknown ? all : 0ull);
+  } else {
+    m = inside ? bits[src] : (u64)(any ? 1 : 0);
+  }
+  encode_write(m, unk, pr, y + (size_t)b * C * plane + p, C, plane);
 }
 
 // ------------------------------------------------------------------------------------------------------------ C ABI
@@ -376,42 +406,75 @@ extern "C" int hrseg_augment_image(const unsigned char* src, const long* desc, c
   return 0;
 }
 
-extern "C" int hrseg_augment_targets(const unsigned char* label, const long* desc, const unsigned long long* on_lut,
-                                     const int* parent, const float* params, float* y, int B, int C, int S, int warp,
-                                     int antialias, void* work, size_t work_bytes, hrseg_stream_t stream) {
-  HRSEG_CHECK_ARG(label && desc && on_lut && parent && y && B > 0 && B <= 65535 && S > 0, "hrseg_augment_targets: bad arguments");
-  HRSEG_CHECK_ARG(C >= 1 && C <= 64, "hrseg_augment_targets: C=%d not in 1..64", C);
-  AugParents pr;
-  for (int c = 0; c < 64; ++c) pr.parent[c] = -1;
-  for (int c = 0; c < C; ++c) {
-    HRSEG_CHECK_ARG(parent[c] >= -1 && parent[c] < C, "hrseg_augment_targets: parent[%d]=%d out of range", c, parent[c]);
-    pr.parent[c] = parent[c];
-  }
+extern "C" int hrseg_augment_workspace_partial(int B, int S, size_t* target_bytes) {
+  HRSEG_CHECK_ARG(B > 0 && S > 0 && target_bytes, "hrseg_augment_workspace_partial: bad arguments");
+  const size_t plane = (size_t)S * S;
+  *target_bytes = align256((size_t)B * plane * 2 * sizeof(u64)) + align256((size_t)B * ceil_div((long)plane, AUG_TPB) * sizeof(int));
+  return 0;
+}
+
+// both target entry points: `name` is the one that was called.  Coverage instances: 16 accumulators per set where C <= 16;
+// above that the fully labelled path keeps all 64 channels in one walk, the partial path walks once per 32 channels
+// (2 x 32 accumulators: DESIGN.md section 25 has the register counts behind the choice).
+static int augment_targets(const char* name, const unsigned char* label, const long* desc, const u64* on_lut, const u64* unk_lut,
+                           bool partial, const int* parent, const float* params, float* y, int B, int C, int S, int warp,
+                           int antialias, int fill_unknown, void* work, size_t work_bytes, hrseg_stream_t stream) {
+  HRSEG_CHECK_ARG(label && desc && on_lut && (!partial || unk_lut) && parent && y && B > 0 && B <= 65535 && S > 0,
+                  "%s: bad arguments", name);
+  HRSEG_CHECK_ARG(C >= 1 && C <= 64, "%s: C=%d not in 1..64", name, C);
+  TargetParents pr;
+  const int bad = target_parents(parent, C, pr);
+  HRSEG_CHECK_ARG(bad < 0, "%s: parent[%d]=%d out of range", name, bad, parent[bad < 0 ? 0 : bad]);
   const hipStream_t st = (hipStream_t)stream;
   const long plane = (long)S * S;
   const dim3 grid_px((unsigned)ceil_div(plane, AUG_TPB), (unsigned)B);
   u64* bits = nullptr;
   int* flags = nullptr;
   if (warp) {
-    HRSEG_CHECK_ARG(params && work, "hrseg_augment_targets: the warp needs params and a workspace");
+    HRSEG_CHECK_ARG(params && work, "%s: the warp needs params and a workspace", name);
     size_t need_i, need_t;
-    hrseg_augment_workspace(B, S, &need_i, &need_t);
-    HRSEG_CHECK_ARG(work_bytes >= need_t, "hrseg_augment_targets: workspace %zu bytes, needs %zu", work_bytes, need_t);
+    if (partial) hrseg_augment_workspace_partial(B, S, &need_t);
+    else hrseg_augment_workspace(B, S, &need_i, &need_t);
+    HRSEG_CHECK_ARG(work_bytes >= need_t, "%s: workspace %zu bytes, needs %zu", name, work_bytes, need_t);
     bits = (u64*)work;
-    flags = (int*)((char*)work + align256((size_t)B * plane * sizeof(u64)));
+    flags = (int*)((char*)work + align256((size_t)B * plane * (partial ? 2 : 1) * sizeof(u64)));
   }
   const long long* d = (const long long*)desc;
-  if (C <= 16)
-    hipLaunchKernelGGL(aug_targets_cover<16>, grid_px, dim3(AUG_TPB), 0, st, label, d, on_lut, pr, y, bits, flags, C, S,
-                       antialias, warp ? 0 : 1);
-  else
-    hipLaunchKernelGGL(aug_targets_cover<64>, grid_px, dim3(AUG_TPB), 0, st, label, d, on_lut, pr, y, bits, flags, C, S,
-                       antialias, warp ? 0 : 1);
+  const int direct = warp ? 0 : 1;
+#define COVER(NC, P) \
+  hipLaunchKernelGGL((aug_targets_cover<NC, P>), grid_px, dim3(AUG_TPB), 0, st, label, d, on_lut, unk_lut, pr, y, bits, flags, C, S, \
+                     antialias, direct)
+  if (partial) {
+    if (C <= 16) COVER(16, true);
+    else COVER(32, true);
+  } else {
+    if (C <= 16) COVER(16, false);
+    else COVER(64, false);
+  }
+#undef COVER
   HRSEG_LAUNCH_CHECK("augment_targets_cover");
   if (warp) {
-    hipLaunchKernelGGL(aug_targets_warp, grid_px, dim3(AUG_TPB), 0, st, bits, flags, params, pr, y, C, S);
+    if (partial)
+      hipLaunchKernelGGL(aug_targets_warp<true>, grid_px, dim3(AUG_TPB), 0, st, bits, flags, params, pr, y, C, S, fill_unknown);
+    else
+      hipLaunchKernelGGL(aug_targets_warp<false>, grid_px, dim3(AUG_TPB), 0, st, bits, flags, params, pr, y, C, S, 0);
     HRSEG_LAUNCH_CHECK("augment_targets_warp");
   }
   hrseg_count(CNT_AUG_TARGETS, warp ? 2 : 1);
   return 0;
+}
+
+extern "C" int hrseg_augment_targets(const unsigned char* label, const long* desc, const unsigned long long* on_lut,
+                                     const int* parent, const float* params, float* y, int B, int C, int S, int warp,
+                                     int antialias, void* work, size_t work_bytes, hrseg_stream_t stream) {
+  return augment_targets("hrseg_augment_targets", label, desc, on_lut, nullptr, false, parent, params, y, B, C, S, warp, antialias,
+                         0, work, work_bytes, stream);
+}
+
+extern "C" int hrseg_augment_targets_partial(const unsigned char* label, const long* desc, const unsigned long long* on_lut,
+                                             const unsigned long long* unk_lut, const int* parent, const float* params, float* y,
+                                             int B, int C, int S, int warp, int antialias, int fill_unknown, void* work,
+                                             size_t work_bytes, hrseg_stream_t stream) {
+  return augment_targets("hrseg_augment_targets_partial", label, desc, on_lut, unk_lut, true, parent, params, y, B, C, S, warp,
+                         antialias, fill_unknown, work, work_bytes, stream);
 }

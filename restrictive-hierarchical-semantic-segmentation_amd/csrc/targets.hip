@@ -2,6 +2,7 @@
 // target planes of the losses and metrics) and level synthesis for flat models.  gfx950.
 #include "common.h"
 #include "level_common.h"
+#include "target_encode.h"
 
 // --------------------------------------------------------------------------- target encoding
 // Label image (one pixel value per leaf class) -> the per-node target planes the losses and
@@ -9,44 +10,56 @@
 // (Data/dataset.py:41-124, 227-265) for an identity spatial transform.  on_lut[v] has bit c set when
 // channel c's node contains the leaf whose pixel value is v (a parent = OR of its leaves), so one
 // 8-byte table read per pixel replaces the per-node mask images.  HBM-bound: 1 byte in, 4*C out.
-struct EncodeParents { int parent[64]; };
+// Partial labels (PARTIAL): a second table, unk_lut[v], names the channels a pixel of value v says nothing about (the
+// strict descendants of an internal node's byte, every channel for an ignore byte); the rule is encode_write's.
+template <bool PARTIAL>
 __global__ __launch_bounds__(256) void encode_targets_kernel(const unsigned char* __restrict__ label,
                                                              const unsigned long long* __restrict__ on_lut,
-                                                             EncodeParents pr, float* __restrict__ out, int C,
-                                                             long hw, long n) {
+                                                             const unsigned long long* __restrict__ unk_lut,
+                                                             TargetParents pr, float* __restrict__ out, int C, long hw,
+                                                             long n) {
   __shared__ unsigned long long lut[256];
+  __shared__ unsigned long long ulut[PARTIAL ? 256 : 1];
   lut[threadIdx.x] = on_lut[threadIdx.x];
+  if constexpr (PARTIAL) ulut[threadIdx.x] = unk_lut[threadIdx.x];
   __syncthreads();
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
     const long b = i / hw, pix = i - b * hw;
-    const unsigned long long bits = lut[label[i]];
-    float* o = out + (size_t)b * C * hw + pix;
-    for (int c = 0; c < C; ++c) {
-      const int par = pr.parent[c];
-      float v;
-      if ((bits >> c) & 1ull) v = 1.f;
-      else if (par < 0 || ((bits >> par) & 1ull)) v = 0.f;   // root, or inside the direct parent's area
-      else v = -1.f;                                          // outside the parent: ignored by loss and metrics
-      o[(size_t)c * hw] = v;
-    }
+    const unsigned char v = label[i];
+    encode_write(lut[v], PARTIAL ? ulut[v] : 0ull, pr, out + (size_t)b * C * hw + pix, C, (size_t)hw);
   }
 }
 
-extern "C" int hrseg_encode_targets(const unsigned char* label, const unsigned long long* on_lut,
-                                    const int* parent, float* out, int B, int C, long hw, hrseg_stream_t stream) {
-  HRSEG_CHECK_ARG(label && on_lut && parent && out && B > 0 && hw > 0, "hrseg_encode_targets: bad arguments");
-  HRSEG_CHECK_ARG(C >= 1 && C <= 64, "hrseg_encode_targets: C=%d not in 1..64", C);
-  EncodeParents pr;
-  for (int c = 0; c < 64; ++c) pr.parent[c] = -1;
-  for (int c = 0; c < C; ++c) {
-    HRSEG_CHECK_ARG(parent[c] >= -1 && parent[c] < C, "hrseg_encode_targets: parent[%d]=%d out of range", c, parent[c]);
-    pr.parent[c] = parent[c];
-  }
+// both entry points: `name` is the one that was called
+static int encode_targets(const char* name, const unsigned char* label, const unsigned long long* on_lut,
+                          const unsigned long long* unk_lut, bool partial, const int* parent, float* out, int B, int C,
+                          long hw, hrseg_stream_t stream) {
+  HRSEG_CHECK_ARG(label && on_lut && (!partial || unk_lut) && parent && out && B > 0 && hw > 0, "%s: bad arguments", name);
+  HRSEG_CHECK_ARG(C >= 1 && C <= 64, "%s: C=%d not in 1..64", name, C);
+  TargetParents pr;
+  const int bad = target_parents(parent, C, pr);
+  HRSEG_CHECK_ARG(bad < 0, "%s: parent[%d]=%d out of range", name, bad, parent[bad < 0 ? 0 : bad]);
   const long n = (long)B * hw;
-  hipLaunchKernelGGL(encode_targets_kernel, dim3(pixel_blocks(n, 8192)), dim3(256), 0, (hipStream_t)stream, label, on_lut, pr,
-                     out, C, hw, n);
-  HRSEG_LAUNCH_CHECK("encode_targets");
+  const dim3 grid(pixel_blocks(n, 8192));
+  if (partial)
+    hipLaunchKernelGGL(encode_targets_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, label, on_lut, unk_lut, pr, out, C,
+                       hw, n);
+  else
+    hipLaunchKernelGGL(encode_targets_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, label, on_lut, unk_lut, pr, out, C,
+                       hw, n);
+  HRSEG_LAUNCH_CHECK(partial ? "encode_targets_partial" : "encode_targets");
   return 0;
+}
+
+extern "C" int hrseg_encode_targets(const unsigned char* label, const unsigned long long* on_lut, const int* parent,
+                                    float* out, int B, int C, long hw, hrseg_stream_t stream) {
+  return encode_targets("hrseg_encode_targets", label, on_lut, nullptr, false, parent, out, B, C, hw, stream);
+}
+
+extern "C" int hrseg_encode_targets_partial(const unsigned char* label, const unsigned long long* on_lut,
+                                            const unsigned long long* unk_lut, const int* parent, float* out, int B, int C,
+                                            long hw, hrseg_stream_t stream) {
+  return encode_targets("hrseg_encode_targets_partial", label, on_lut, unk_lut, true, parent, out, B, C, hw, stream);
 }
 
 // --------------------------------------------------------------------------- level synthesis for flat models

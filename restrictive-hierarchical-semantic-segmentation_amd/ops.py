@@ -641,6 +641,51 @@ def augment_targets(label, desc, desc_host, on_lut, parent, params, S, warp, ant
     return y
 
 
+def _check_lut(lut, what):
+    assert lut.dtype == torch.int64 and lut.numel() == 256 and lut.is_cuda and lut.is_contiguous(), what
+
+
+def encode_targets_partial(label, on_lut, unk_lut, parent):
+    """encode_targets for partial labels (include/hrseg.h, "partial labels"): unk_lut [256] int64 bit table (device) of the
+    channels a pixel value says nothing about"""
+    assert label.dtype == torch.uint8 and label.is_cuda and label.dim() == 3
+    _check_lut(on_lut, "on_lut")
+    _check_lut(unk_lut, "unk_lut")
+    label = label.contiguous()
+    B, H, W = label.shape
+    Cn = len(parent)
+    out = torch.empty((B, Cn, H, W), dtype=torch.float32, device=label.device)
+    call("hrseg_encode_targets_partial", ptr(label), ptr(on_lut), ptr(unk_lut), _lib.int_array(list(parent)), ptr(out), B, Cn,
+         H * W)
+    return out
+
+
+def augment_workspace_partial(B, S):
+    """bytes of device workspace the warp of augment_targets_partial needs"""
+    tgt = C.c_size_t(0)
+    _lib.call_raw("hrseg_augment_workspace_partial", int(B), int(S), C.byref(tgt))
+    return int(tgt.value)
+
+
+def augment_targets_partial(label, desc, desc_host, on_lut, unk_lut, parent, params, S, warp, antialias=True, fill_unknown=False):
+    """augment_targets for partial labels: two coverages per channel, both thresholded sets warped; fill_unknown: out of
+    frame every channel is unknown (-1) instead of the reference's fill"""
+    _check_ragged(label, desc, desc_host, (1,))
+    _check_lut(on_lut, "on_lut")
+    _check_lut(unk_lut, "unk_lut")
+    B, Cn = desc.shape[0], len(parent)
+    y = torch.empty((B, Cn, S, S), dtype=torch.float32, device=label.device)
+    work, nbytes = None, 0
+    if warp:
+        assert params is not None and params.is_cuda and params.dtype == torch.float32 and params.shape == (B, 48)
+        nbytes = augment_workspace_partial(B, S)
+        work = torch.empty(nbytes, dtype=torch.uint8, device=label.device)
+    call("hrseg_augment_targets_partial", ptr(label), ptr(desc), ptr(on_lut), ptr(unk_lut), _lib.int_array(list(parent)),
+         ptr(params) if warp else None, ptr(y), B, Cn, S, int(bool(warp)), int(bool(antialias)), int(bool(fill_unknown)),
+         ptr(work), nbytes)
+    return y
+
+
 DECODE_MAX_LEVELS, DECODE_MAX_CHANNELS, DECODE_MAX_TOTAL = 8, 16, 64
 
 

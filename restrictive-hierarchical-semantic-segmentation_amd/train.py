@@ -16,6 +16,7 @@ Dataset / checkpoint / CSV orchestration (build, train, main) is out of scope
 from __future__ import annotations
 
 import contextlib
+import gc
 import time
 
 import numpy as np
@@ -631,9 +632,20 @@ class TapedTrainStep:
         self.tape = _lib.Tape()
         self.replays = 0
         self._load(data, target, copy=False)
-        with torch.cuda.use_mem_pool(self.pool, device=dev), torch.no_grad():
-            with self.tape:
-                self.out = self._body()
+        # The cyclic collector stays out of the recording.  An earlier step and its model's tape cache refer to each other,
+        # so that step's MemPool and buffers are finalised by the collector, whenever it next runs; a collection that
+        # started inside the recording aborted the process in a whole-suite run.  Collect before the
+        # pool is entered, hold the collector off until it is left.
+        gc.collect()
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.use_mem_pool(self.pool, device=dev), torch.no_grad():
+                with self.tape:
+                    self.out = self._body()
+        finally:
+            if gc_was_on:
+                gc.enable()
         _unwrap(self.model).notify_parameters_changed()
 
     # ------------------------------------------------------------------ the recorded body
