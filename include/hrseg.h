@@ -178,8 +178,9 @@ int hrseg_conv_wgrad_group_ws(int n, const float* const* x, const float* const* 
  * example mining: 1 launch per hrseg_ohem_scores, 7 per hrseg_ohem_select, 1 per hrseg_loss_partials_ohem / hrseg_loss_bwd_ohem call),
  * "label_components" / "filter_components" (post-processing) and "score_boundaries" (boundary scoring, HRSEG_SCORE_BOUNDARIES_LAUNCHES
  * per hrseg_score_boundaries call), "score_instances" (instance scoring) and "score_calibration" (calibration scoring, 1 launch
- * per hrseg_score_calibration call) and "decode_hedged" (the hedged decode, 1 launch per hrseg_decode_hedged call) are families
- * of their own, outside the NULL total and the convolution counts. */
+ * per hrseg_score_calibration call), "decode_hedged" (the hedged decode, 1 launch per hrseg_decode_hedged call) and "mix" (the
+ * mixing augmentation, 1 launch per hrseg_mix_* call) are families of their own, outside the NULL total and the convolution
+ * counts. */
 long hrseg_launch_count(const char* family, int reset);
 /* tile-plan overrides and A/B switches for the sweep tools under tools/ (value 0 = automatic plan).  Keys: igemm_wtm,
  * igemm_kc, igemm_db, igemm_ksplit, group_wtm, wgrad_pix, wgrad_db, wgrad_blocks, wgrad_group_mult,
@@ -696,6 +697,61 @@ int hrseg_augment_targets_partial(const unsigned char* label, const long* desc, 
                                   const unsigned long long* unk_lut, const int* parent, const float* params, float* y, int B,
                                   int C, int S, int warp, int antialias, int fill_unknown, void* work, size_t work_bytes,
                                   hrseg_stream_t stream);
+
+/* ------------------------------------------------------------------ mixing (Data/mix.py; csrc/mix.hip)
+ * ClassMix / CutMix / paste by tree node: lay pixels of a DONOR sample of the batch, labels included, over a recipient.  This
+ * is the one statement of the semantics; everything else refers here.
+ *
+ * Inputs: x [B,3,S,S] fp32 and y [B,C,S,S] fp32 as hrseg_augment_* write them; in general any in [B,K,S,S] fp32.  A target is
+ * one ternary column per pixel (hrseg_encode_targets), so a pasted pixel takes the donor's whole column and stays consistent at
+ * every level; an ignored pixel (partial labels) is -1 in every channel and is therefore never chosen by a node, an internal
+ * "tooth" pixel is pasted with its unknown children.
+ *
+ * params: DEVICE table [B][HRSEG_MIX_PARAMS] of int32, one row per sample:
+ *   HRSEG_MIX_P_FLAGS   HRSEG_MIX_APPLY | HRSEG_MIX_BOX
+ *   HRSEG_MIX_P_DONOR   sample index in [0,B) (a row whose donor is outside is treated as not applied)
+ *   HRSEG_MIX_P_DX, _DY the donor's content is moved by (dx, dy) whole pixels: output pixel (r, c) looks at donor pixel
+ *                       (r - dy, c - dx); a donor pixel outside the frame is never taken; any int32
+ *   HRSEG_MIX_P_BOX     [4] r0, c0, r1, c1, half-open, in output coordinates
+ *   the rest            reserved, zero
+ *
+ * Counts: counts[b][c] = the number of pixels of sample b with y[b][c] == 1.0f, exact int32, over the whole unshifted frame,
+ * for all C channels.
+ *
+ * Node choice, for a sample b with APPLY and without BOX, donor d:
+ *   P = {c : cand[c] != 0 and counts[d][c] >= min_pixels},  n = |P|,  k = k_of_n[n],
+ *   chosen[b] = the k members of P with the smallest prio[b][c].
+ * prio: DEVICE [B][C] int32, each row a permutation of 0..C-1 (no ties; equal values would fall back to the channel index).
+ * k_of_n: DEVICE [65] int32 built on the host, k_of_n[0] = 0, else min(n, max(1, ceil(share * n))): the device does no float
+ * arithmetic for the choice.  cand: HOST [C] int32 of 0/1, passed like `parent` of hrseg_encode_targets.  chosen is written as
+ * one uint64 per sample (bit c = channel c), 0 for BOX samples and for samples that are not applied.  counts may be NULL when
+ * no applied sample is without BOX; a sample that would need it then chooses nothing.
+ *
+ * Mask, uint8 [B,S,S] of 0 / 1:  not APPLY: 0;  BOX: 1 where r0 <= r < r1, c0 <= c < c1 and the moved donor pixel is in the
+ * frame;  otherwise: 1 where the moved donor pixel is in the frame and some c in chosen[b] has y[d][c][r-dy][c-dx] == 1.0f.
+ *
+ * Gather: out[b][k][r][c] = mask[b][r][c] ? in[d][k][r-dy][c-dx] : in[b][k][r][c].  The 32 bits are copied, never blended
+ * arithmetically: NaN payloads, infinities and -0.0 come through unchanged.  out must not alias in (a donor can itself be a
+ * recipient).  A set mask byte is honoured only on an applied sample and where the moved donor pixel is in the frame (always
+ * so for the mask of hrseg_mix_masks with the same params).
+ *
+ * hrseg_mix_counts clears counts itself (an async memset on the stream) and launches once; hrseg_mix_masks and
+ * hrseg_mix_gather are one launch each; all count under "mix".  No entry point synchronises or copies to the host.
+ * Limits: 1 <= C <= 64, hw < 2^31, B*C*S*S < 2^31 (masks), B*K*S*S < 2^31 (gather), min_pixels >= 1. */
+#define HRSEG_MIX_PARAMS 16
+#define HRSEG_MIX_P_FLAGS 0
+#define HRSEG_MIX_P_DONOR 1
+#define HRSEG_MIX_P_DX 2
+#define HRSEG_MIX_P_DY 3
+#define HRSEG_MIX_P_BOX 4
+#define HRSEG_MIX_APPLY 1
+#define HRSEG_MIX_BOX 2
+int hrseg_mix_counts(const float* y, int* counts, int B, int C, long hw, hrseg_stream_t stream);
+int hrseg_mix_masks(const float* y, const int* counts, const int* params, const int* prio, const int* k_of_n,
+                    const int* cand, int min_pixels, unsigned char* mask, unsigned long long* chosen,
+                    int B, int C, int S, hrseg_stream_t stream);
+int hrseg_mix_gather(const float* in, const unsigned char* mask, const int* params, float* out,
+                     int B, int K, int S, hrseg_stream_t stream);
 
 /* ------------------------------------------------------------------ device output pipeline (Data/decode.py)
  * The inverse of the input pipeline: per-level logits at network size -> one label map per source image, at the source's

@@ -8,3 +8,4 @@ from .boundary import BoundaryScores, DeviceBoundaryScore  # noqa: F401
 from .instances import DeviceInstanceScore, InstanceScores  # noqa: F401
 from .calibration import CalibrationScores, DeviceCalibrationScore  # noqa: F401
 from .hedge import Hedge  # noqa: F401
+from .mix import DeviceMix  # noqa: F401

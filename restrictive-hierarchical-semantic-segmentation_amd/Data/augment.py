@@ -112,10 +112,13 @@ class DeviceAugment:
     Partial labels (include/hrseg.h): internal_values / ignore_values as for TargetEncoder (`internal_values=h.values,
     ignore_values=[h.reject_val]` trains on the hedged maps of a `Hedge` h); fill="ignore" marks what the affine warp brings in
     from outside the source frame as unlabelled (-1 in every channel) instead of the reference's fill.  With none of the three
-    the object launches `hrseg_augment_targets` as before."""
+    the object launches `hrseg_augment_targets` as before.
+
+    mix: a `DeviceMix` (Data/mix.py) over the same channels; with train=True the pair that comes back is the mixed one
+    (ClassMix / CutMix across the batch; `mix.last_params` holds its draws).  None, or train=False: nothing changes."""
 
     def __init__(self, img_size, class_tree, class_map, model_type=1, train=True, hflip=True, vflip=False, affine=True,
-                 target_antialias=True, seed=0, device="cuda", internal_values=None, ignore_values=(), fill="reference"):
+                 target_antialias=True, seed=0, device="cuda", internal_values=None, ignore_values=(), fill="reference", mix=None):
         require_gpu()
         if fill not in ("reference", "ignore"):
             raise ValueError(f"fill '{fill}' is neither 'reference' nor 'ignore'")
@@ -132,6 +135,10 @@ class DeviceAugment:
             self.encoder.unk_lut = torch.zeros_like(self.encoder.on_lut)
         self.device = self.encoder.on_lut.device
         self.names = self.encoder.names
+        if mix is not None and list(mix.names) != list(self.names):
+            raise ValueError(f"mix speaks of the channels {list(mix.names)}, the augment's encoder of {list(self.names)}: "
+                             "build both from the same class tree, class map and model type")
+        self.mix = mix
         self.generator = torch.Generator().manual_seed(int(seed))
         self.last_params = None
 
@@ -160,4 +167,6 @@ class DeviceAugment:
         else:
             y = ops.augment_targets(dev.label, dev.ldesc, dev.ldesc_host, enc.on_lut, enc.parent, table, self.size, self.train,
                                     self.target_antialias)
+        if self.mix is not None and self.train:
+            return self.mix(x, y)
         return x, y

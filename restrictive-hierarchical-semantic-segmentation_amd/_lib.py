@@ -144,6 +144,9 @@ PROTOTYPES = {
     "hrseg_augment_targets": [_p, _p, _p, C.POINTER(C.c_int), _p, _p, _i, _i, _i, _i, _i, _p, C.c_size_t, _p],
     "hrseg_encode_targets_partial": [_p, _p, _p, C.POINTER(C.c_int), _p, _i, _i, _l, _p],
     "hrseg_augment_targets_partial": [_p, _p, _p, _p, C.POINTER(C.c_int), _p, _p, _i, _i, _i, _i, _i, _i, _p, C.c_size_t, _p],
+    "hrseg_mix_counts": [_p, _p, _i, _i, _l, _p],
+    "hrseg_mix_masks": [_p, _p, _p, _p, _p, C.POINTER(C.c_int), _i, _p, _p, _i, _i, _i, _p],
+    "hrseg_mix_gather": [_p, _p, _p, _p, _i, _i, _i, _p],
     "hrseg_decode_labels": [_i, _p, C.POINTER(C.c_int), C.POINTER(DecodeTree), _p, _p, _p, _i, _i, _p],
     "hrseg_decode_hedged": [_i, _p, C.POINTER(C.c_int), C.POINTER(DecodeTree), C.POINTER(Hedge), _p, _p, _p, _p, _i, _i, _p],
     "hrseg_decode_views": [_i, C.POINTER(C.c_int), C.POINTER(C.c_int), _i, _p, C.POINTER(C.c_int), C.POINTER(DecodeTree), _p, _p, _p,
@@ -262,7 +265,8 @@ def launch_count(family=None, reset=False) -> int:
     pipeline under "score_labels", test-time augmentation under "decode_views" / "flip_views", sliding-window inference
     under "window_crops" / "decode_windows", the post-processing under "label_components" / "filter_components", the
     boundary scoring under "score_boundaries", the instance scoring's masked copy and scoring launches under
-    "score_instances", the calibration scoring under "score_calibration", the hedged decode under "decode_hedged")"""
+    "score_instances", the calibration scoring under "score_calibration", the hedged decode under "decode_hedged", the mixing augmentation
+    under "mix")"""
     return int(_lib.hrseg_launch_count(None if family is None else family.encode(), int(reset)))
 
 

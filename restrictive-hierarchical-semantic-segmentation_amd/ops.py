@@ -686,6 +686,74 @@ def augment_targets_partial(label, desc, desc_host, on_lut, unk_lut, parent, par
     return y
 
 
+MIX_PARAMS = 16                     # HRSEG_MIX_PARAMS
+
+
+def _check_mix_planes(who, t, what):
+    """a [B,K,S,S] fp32 device tensor, contiguous, below 2^31 elements -> (B, K, S)"""
+    if t.dim() != 4 or t.shape[2] != t.shape[3] or min(t.shape) < 1:
+        raise ValueError(f"{who}: {what} must be [B,K,S,S], got {tuple(t.shape)}")
+    if t.numel() >= 1 << 31:
+        raise ValueError(f"{who}: {what} {tuple(t.shape)} has 2^31 elements or more")
+    assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous(), f"{who}: {what} must be contiguous fp32 on the device"
+    return t.shape[0], t.shape[1], t.shape[2]
+
+
+def _check_mix_table(who, t, what, shape):
+    assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous(), f"{who}: {what} must be contiguous int32 on the device"
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{who}: {what} must be {tuple(shape)}, got {tuple(t.shape)}")
+
+
+def mix_counts(y):
+    """y [B,C,S,S] fp32 targets -> counts [B,C] int32: pixels with y == 1 (include/hrseg.h, "mixing")"""
+    B, Cn, S = _check_mix_planes("mix_counts", y, "y")
+    if Cn > 64:
+        raise ValueError(f"mix_counts: {Cn} channels, at most 64")
+    counts = torch.empty((B, Cn), dtype=torch.int32, device=y.device)
+    call("hrseg_mix_counts", ptr(y), ptr(counts), B, Cn, S * S)
+    return counts
+
+
+def mix_masks(y, counts, params, prio, k_of_n, cand, min_pixels=1):
+    """y [B,C,S,S], counts [B,C] int32 or None (no applied sample without a box), params [B,16] / prio [B,C] / k_of_n [65]
+    int32 (device), cand list of C 0/1 (host) -> (mask [B,S,S] uint8, chosen [B] int64 bit sets)"""
+    B, Cn, S = _check_mix_planes("mix_masks", y, "y")
+    if Cn > 64:
+        raise ValueError(f"mix_masks: {Cn} channels, at most 64")
+    if counts is not None:
+        _check_mix_table("mix_masks", counts, "counts", (B, Cn))
+    _check_mix_table("mix_masks", params, "params", (B, MIX_PARAMS))
+    _check_mix_table("mix_masks", prio, "prio", (B, Cn))
+    _check_mix_table("mix_masks", k_of_n, "k_of_n", (65,))
+    if len(cand) != Cn:
+        raise ValueError(f"mix_masks: {len(cand)} candidate flags for {Cn} channels")
+    if int(min_pixels) < 1:
+        raise ValueError(f"mix_masks: min_pixels {min_pixels} below 1")
+    mask = torch.empty((B, S, S), dtype=torch.uint8, device=y.device)
+    chosen = torch.empty((B,), dtype=torch.int64, device=y.device)
+    call("hrseg_mix_masks", ptr(y), ptr(counts), ptr(params), ptr(prio), ptr(k_of_n), _lib.int_array([int(bool(v)) for v in cand]),
+         int(min_pixels), ptr(mask), ptr(chosen), B, Cn, S)
+    return mask, chosen
+
+
+def mix_gather(t, mask, params, out=None):
+    """out[b] = mask[b] ? t[donor(b)] moved by (dx, dy) : t[b], as bits; t [B,K,S,S] fp32, mask [B,S,S] uint8, params [B,16] int32"""
+    B, K, S = _check_mix_planes("mix_gather", t, "the input")
+    assert mask.dtype == torch.uint8 and mask.is_cuda and mask.is_contiguous(), "mix_gather: mask must be contiguous uint8 on the device"
+    if tuple(mask.shape) != (B, S, S):
+        raise ValueError(f"mix_gather: mask must be {(B, S, S)}, got {tuple(mask.shape)}")
+    _check_mix_table("mix_gather", params, "params", (B, MIX_PARAMS))
+    if out is None:
+        out = torch.empty_like(t)
+    else:
+        assert out.dtype == torch.float32 and out.is_cuda and out.is_contiguous() and out.shape == t.shape
+        if out is t or out.data_ptr() == t.data_ptr():
+            raise ValueError("mix_gather: out must not alias the input (a donor can itself be a recipient)")
+    call("hrseg_mix_gather", ptr(t), ptr(mask), ptr(params), ptr(out), B, K, S)
+    return out
+
+
 DECODE_MAX_LEVELS, DECODE_MAX_CHANNELS, DECODE_MAX_TOTAL = 8, 16, 64
 
 
