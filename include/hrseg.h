@@ -179,7 +179,7 @@ int hrseg_conv_wgrad_group_ws(int n, const float* const* x, const float* const* 
  * "label_components" / "filter_components" (post-processing) and "score_boundaries" (boundary scoring, HRSEG_SCORE_BOUNDARIES_LAUNCHES
  * per hrseg_score_boundaries call), "score_instances" (instance scoring) and "score_calibration" (calibration scoring, 1 launch
  * per hrseg_score_calibration call), "decode_hedged" (the hedged decode, 1 launch per hrseg_decode_hedged call) and "mix" (the
- * mixing augmentation, 1 launch per hrseg_mix_* call) are families of their own, outside the NULL total and the convolution
+ * mixing augmentation, 1 launch per hrseg_mix_* call) and "border_weights" (2 launches per hrseg_border_weights call) are families of their own, outside the NULL total and the convolution
  * counts. */
 long hrseg_launch_count(const char* family, int reset);
 /* tile-plan overrides and A/B switches for the sweep tools under tools/ (value 0 = automatic plan).  Keys: igemm_wtm,
@@ -530,6 +530,51 @@ int hrseg_loss_partials_ohem(const float* z, const float* t, const float* q, con
 int hrseg_loss_bwd_ohem(const float* z, const float* t, const float* q, const void* record, float thresh,
                         const float* coef, const float* g, float* dz, int accumulate, int B, int C, long hw,
                         float gamma, hrseg_stream_t stream);
+/* ---- border weights (csrc/border_weight.hip, csrc/loss.hip; Metrics/border.py)
+ * The U-Net weight map w(x) = 1 + w0 exp(-d(x)^2 / (2 sigma^2)), d = the distance to the nearest border of the level's label
+ * map, computed on the device per step and per level, and the per-pixel weight on the CE term that consumes it.
+ *
+ * Weight map of one level.  Input t [B,C,H,W] fp32, the level's target planes as hrseg_encode_targets / the partial-label
+ * rules write them (-1 / 0 / 1), 1 <= C <= 16.
+ *   on_c(i)   iff t[b,c,i] == 1.0f.
+ *   void(i)   iff every channel is -1.0f (the loss gives such a pixel a gradient of exactly 0 at this level).
+ *   label(i)  the smallest c with on_c(i), or C when no channel is on; any other value (0, NaN, 0.5, ...) is "not on, not -1".
+ *             The label byte written to `labels` is label(i) (0..C), or 255 for a void pixel.
+ *   d2(i)     for a non-void pixel the minimum of dx^2 + dy^2 over the pixels j of the same image that are not void, have
+ *             label(j) != label(i) and dx^2 + dy^2 <= radius^2; 0 when there is no such j, and for void pixels.  Void pixels
+ *             are never a source: an ignored region or an unlabelled corner makes no border, and a different label behind a
+ *             void gap still counts.  Images do not see each other, and nothing exists outside the frame.
+ *   v(i)      lut[d2(i)].  lut is a DEVICE table of radius^2 + 1 floats built on the host: lut[0] = 1.0f,
+ *             lut[k] = (float)(1 + w0 exp(-k / (2 sigma^2))) evaluated in fp64.
+ * Everything up to the table lookup is integer arithmetic: labels, d2 and v are exact, the same bytes in every run and equal
+ * bit for bit to a host reference that uses the same table.
+ *   hrseg_border_weights   labels (B*H*W bytes) and v (B*H*W floats) are required outputs, d2 (B*H*W ints) may be NULL.  Two
+ *             launches (label extraction, then the search from LDS tiles of hrseg_border_tile pixels plus a radius-wide halo),
+ *             no host read, no synchronisation; counted under the family "border_weights" (outside the NULL total).  Refused
+ *             (-1, the message starts with the entry point's name) before any launch: a null t, lut, labels or v, B < 1,
+ *             C outside 1..16, H < 1 or W < 1, H*W >= 2^31, radius outside 1..32.
+ *
+ * Per-pixel weights in the fused loss.  pw [B*hw] fp32 holds one weight per pixel and applies to the CE term only (as the
+ * OHEM selection does):
+ *   hrseg_loss_partials_pw   hrseg_loss_partials_opt with slots 0 and 1 of partial[b][c][5] = sum pw and
+ *             sum pw t (1-p)^gamma log p over t != -1; slots 2..4 are those of the plain call.  hrseg_loss_finalize[_opt]
+ *             runs unchanged behind it, so the CE of a class mask is the pw-weighted mean, a mask whose weighted mass is <= 0
+ *             counts as empty (the item is the constant 1.0) and a constant map gives the loss of the unweighted call.
+ *   hrseg_loss_bwd_pw        hrseg_loss_bwd_opt with the CE part of dz at a pixel multiplied by pw there; the Dice part is
+ *             untouched.
+ * pw finite and >= 0 is the caller's duty; no gradient flows to pw.  A NaN logit gives a NaN CE and a NaN dz at its pixel
+ * whatever its weight (0 * NaN stays NaN).  Not combined with OHEM.  The refusals of the _opt entry points apply, plus a null
+ * pw, each under the _pw entry point's name; the launches are counted like those of the plain loss calls (not at all). */
+#define HRSEG_BORDER_TILE_W 64
+#define HRSEG_BORDER_TILE_H 16
+#define HRSEG_BORDER_MAX_RADIUS 32
+int hrseg_border_tile(int* w, int* h);    /* the tile of the search kernel, for tests (as hrseg_components_tile) */
+int hrseg_border_weights(const float* t, int B, int C, int H, int W, int radius, const float* lut,
+                         unsigned char* labels, float* v, int* d2, hrseg_stream_t stream);
+int hrseg_loss_partials_pw(const float* z, const float* t, const float* pw, double* partial, int B, int C, long hw,
+                           float gamma, hrseg_stream_t stream);
+int hrseg_loss_bwd_pw(const float* z, const float* t, const float* pw, const float* coef, const float* g, float* dz,
+                      int accumulate, int B, int C, long hw, float gamma, hrseg_stream_t stream);
 /* per-class metric vectors of nlevels (1..8) levels from their confusion counts in ONE launch: cm[L] (DEVICE, int64
  * [K_L][K_L], (target, predicted) as hrseg_predict_metrics counts them), child[L] != 0: label 0 is the synthetic background
  * of a child level (its row is dropped, its class not reported).  out (DEVICE) receives [5][sum_L (K_L - child_L)] floats:

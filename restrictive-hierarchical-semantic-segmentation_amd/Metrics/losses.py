@@ -18,6 +18,9 @@ Online hard example mining on the CE term (OhemOptions):
 ``CrossEntropyLoss(ohem_thresh=0.7, ohem_min_kept=100000)`` averages the CE over the
 pixels of the level's batch whose true-class probability is below the threshold, and
 over at least the ``ohem_min_kept`` hardest ones; the Dice term is untouched.
+Border weights on the CE term (Metrics/border.py): ``CrossEntropyLoss(border=BorderWeights(w0, sigma))``
+weighs every pixel's CE by 1 + w0 exp(-d^2 / (2 sigma^2)), d = its distance to the nearest border of the level's label map;
+``fused_ce_dice(pixel_weight=)`` takes any per-pixel map.  The Dice term is untouched.
 """
 from __future__ import annotations
 
@@ -28,6 +31,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from .border import BorderOptions, BorderWeights  # noqa: F401  (re-exported)
 
 _weight_cache = {}
 
@@ -107,15 +111,18 @@ class OhemOptions(NamedTuple):
 
 
 class _FusedLoss(torch.autograd.Function):
-    """(logits, targets, w, options, ohem, record_to) -> [ce, dice, n_valid_dice_items]"""
+    """(logits, targets, w, options, ohem, record_to, pixel_weight) -> [ce, dice, n_valid_dice_items]"""
 
     @staticmethod
-    def forward(ctx, z, t, w, options, ohem, record_to):
+    def forward(ctx, z, t, w, options, ohem, record_to, pixel_weight=None):
         z = z.contiguous()
         t = t.contiguous()
         ctx.options = options
         ctx.ohem = None
-        if ohem is None:
+        ctx.pixel_weight = pixel_weight         # a constant of the step: no gradient flows to it
+        if pixel_weight is not None:
+            out, coef = ops.loss_fwd(z, t, w, options, pixel_weight=pixel_weight)
+        elif ohem is None:
             out, coef = ops.loss_fwd(z, t, w, options)
         else:
             out, coef, ctx.ohem = ops.loss_fwd(z, t, w, options, ohem=ohem)
@@ -127,19 +134,43 @@ class _FusedLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         z, t, coef = ctx.saved_tensors
-        return ops.loss_bwd(z, t, coef, g.contiguous(), options=ctx.options, ohem=ctx.ohem), None, None, None, None, None
+        if ctx.pixel_weight is not None:
+            dz = ops.loss_bwd(z, t, coef, g.contiguous(), options=ctx.options, pixel_weight=ctx.pixel_weight)
+        else:
+            dz = ops.loss_bwd(z, t, coef, g.contiguous(), options=ctx.options, ohem=ctx.ohem)
+        return dz, None, None, None, None, None, None
 
 
-def fused_ce_dice(logits, targets, class_weight, options=None, ohem=None, record_to=None):
+def _pixel_weight(pixel_weight, logits):
+    """pixel_weight as a contiguous [B,H,W] fp32 tensor on the logits' device, or ValueError"""
+    B, _, H, W = logits.shape
+    if not isinstance(pixel_weight, torch.Tensor) or tuple(pixel_weight.shape) not in ((B, H, W), (B, 1, H, W)):
+        raise ValueError(f"pixel_weight must be a [B,H,W] or [B,1,H,W] tensor matching the logits ({B}, {H}, {W}), got "
+                         f"{tuple(pixel_weight.shape) if isinstance(pixel_weight, torch.Tensor) else type(pixel_weight).__name__}")
+    if pixel_weight.dtype != torch.float32:
+        raise ValueError(f"pixel_weight must be float32, got {pixel_weight.dtype}")
+    if pixel_weight.device != logits.device:
+        raise ValueError(f"pixel_weight is on {pixel_weight.device}, the logits are on {logits.device}")
+    return pixel_weight.detach().reshape(B, H, W).contiguous()
+
+
+def fused_ce_dice(logits, targets, class_weight, options=None, ohem=None, record_to=None, pixel_weight=None):
     """-> tensor [3] = (CE, Dice, number of valid Dice items); differentiable w.r.t. logits.  `options`: a LossOptions
     (None = the defaults).  `ohem`: an OhemOptions / (thresh, min_kept) pair, None = off; the selection's device record
-    (int32[4]: lam_k as fp32 bits, n_candidates, n_kept, reserved) is left in `record_to.last_ohem` when an object is given."""
+    (int32[4]: lam_k as fp32 bits, n_candidates, n_kept, reserved) is left in `record_to.last_ohem` when an object is given.
+    `pixel_weight`: [B,H,W] or [B,1,H,W] fp32 on the logits' device, one weight per pixel on the CE term (finite and >= 0 is
+    the caller's duty; no gradient flows to it); not together with `ohem`."""
     if logits.shape[1] != len(class_weight):
         raise ValueError(f"class_weight has {len(class_weight)} entries, logits have {logits.shape[1]} channels")
+    if pixel_weight is not None and ohem is not None:
+        raise ValueError("pixel_weight and ohem are not combined: pass one of them")
     options = None if options is None else LossOptions(*options).or_none()
     if ohem is not None:
         ohem = OhemOptions(_ohem_thresh(ohem[0]), _ohem_min_kept(ohem[1]))
-    return _FusedLoss.apply(logits, targets, _weights(class_weight, logits.device), options, ohem, record_to)
+    w = _weights(class_weight, logits.device)
+    if pixel_weight is None:
+        return _FusedLoss.apply(logits, targets, w, options, ohem, record_to)
+    return _FusedLoss.apply(logits, targets, w, options, None, record_to, _pixel_weight(pixel_weight, logits))
 
 
 def global_batch_dice(res, group=None):
@@ -178,15 +209,31 @@ class CrossEntropyLoss(nn.Module):
     ``ohem_thresh`` (None = off) switches online hard example mining on: the CE then runs over the pixels of the level's batch
     whose true-class probability is below it, and over the ``ohem_min_kept`` hardest at least (OhemOptions).  ``last_ohem`` is
     the device record of the latest selection (int32[4]: lam_k as fp32 bits, n_candidates, n_kept, reserved; None before the
-    first), written without a sync: ``kept_fraction()`` reads it."""
+    first), written without a sync: ``kept_fraction()`` reads it.
+    ``border`` (a BorderWeights, None = off) weighs every pixel's CE by the border weight map of the level's targets, computed
+    per call on the device; ``last_border`` is the latest map ([B,H,W], None before the first).  Not together with
+    ``ohem_thresh``."""
 
-    def __init__(self, smooth=0.0, focal_gamma=0.0, ohem_thresh=None, ohem_min_kept=0):
+    def __init__(self, smooth=0.0, focal_gamma=0.0, ohem_thresh=None, ohem_min_kept=0, border=None):
         super().__init__()
         self.smooth = smooth
         self.focal_gamma = _option("focal_gamma", focal_gamma)
         self.ohem_thresh = None if ohem_thresh is None else _ohem_thresh(ohem_thresh)
         self.ohem_min_kept = _ohem_min_kept(ohem_min_kept)
         self.last_ohem = None
+        if border is not None and not isinstance(border, BorderWeights):
+            raise ValueError(f"border must be a BorderWeights or None, got {type(border).__name__}")
+        if border is not None and self.ohem_thresh is not None:
+            raise ValueError("CrossEntropyLoss: ohem_thresh and border are not combined: pass one of them")
+        self.border = border
+        self.last_border = None
+
+    def border_map(self, targets):
+        """the level's border weight map (None when the option is off), kept in ``last_border``"""
+        if self.border is None:
+            return None
+        self.last_border = self.border(targets)
+        return self.last_border
 
     def kept_fraction(self):
         """n_kept / n_candidates of the latest selection (a host read: for logging), None when there is none"""
@@ -197,7 +244,7 @@ class CrossEntropyLoss(nn.Module):
 
     def forward(self, outs, targets, logits_input=False, class_weight=None):
         return fused_ce_dice(_as_logits(outs, logits_input, True), targets, class_weight, LossOptions.from_pair(self, None),
-                             ohem=OhemOptions.from_ce(self), record_to=self)[0]
+                             ohem=OhemOptions.from_ce(self), record_to=self, pixel_weight=self.border_map(targets))[0]
 
 
 class SoftDiceLoss(nn.Module):

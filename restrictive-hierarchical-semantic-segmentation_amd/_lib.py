@@ -123,6 +123,9 @@ PROTOTYPES = {
     "hrseg_ohem_select": [_p, _l, _f, _l, _p, _p, _p],
     "hrseg_loss_partials_ohem": [_p, _p, _p, _p, _f, _p, _i, _i, _l, _f, _p],
     "hrseg_loss_bwd_ohem": [_p, _p, _p, _p, _f, _p, _p, _p, _i, _i, _i, _l, _f, _p],
+    "hrseg_border_weights": [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p],
+    "hrseg_loss_partials_pw": [_p, _p, _p, _p, _i, _i, _l, _f, _p],
+    "hrseg_loss_bwd_pw": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _l, _f, _p],
     "hrseg_consistency": [_p, _p, _p, _i, _i, _i, _l, _i, _p, _p, _p],
     "hrseg_consistency_bwd": [_p, _p, _p, _f, _p, _p, _i, _i, _i, _l, _i, _p, _p, _p],
     "hrseg_group_kl": [_p, _p, _p, _i, _i, _i, _l, _i, _p, _p, _p],
@@ -181,6 +184,7 @@ RAW_PROTOTYPES = {
     "hrseg_grad_sumsq_chunks": [_l],
     "hrseg_ohem_workspace_bytes": [],
     "hrseg_components_tile": [C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "hrseg_border_tile": [C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "hrseg_filter_components_workspace_bytes": [_i],
     "hrseg_boundary_workspace_bytes": [_p, _i, _i, C.POINTER(C.c_int)],
     "hrseg_instances_workspace_bytes": [_p, _i],
@@ -385,6 +389,13 @@ def components_tile():
     """(width, height) of the tile a block of hrseg_label_components labels in LDS (a constant of the library)"""
     w, h = C.c_int(0), C.c_int(0)
     call_raw("hrseg_components_tile", C.byref(w), C.byref(h))
+    return int(w.value), int(h.value)
+
+
+def border_tile():
+    """(width, height) of the tile a block of hrseg_border_weights searches from LDS (a constant of the library)"""
+    w, h = C.c_int(0), C.c_int(0)
+    call_raw("hrseg_border_tile", C.byref(w), C.byref(h))
     return int(w.value), int(h.value)
 
 

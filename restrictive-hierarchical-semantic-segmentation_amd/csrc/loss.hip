@@ -18,12 +18,12 @@
     else hipLaunchKernelGGL((KERNEL<16>), grid, dim3(256), 0, st, __VA_ARGS__);              \
   } while (0)
 
-// the same ladder for kernels with two more template arguments: KERNEL<CT, FLAG, FLAG2>
-#define LAUNCH_CT_FLAGS(KERNEL, FLAG, FLAG2, C, grid, st, ...)                                            \
-  do {                                                                                                    \
-    if ((C) <= 4) hipLaunchKernelGGL((KERNEL<4, FLAG, FLAG2>), grid, dim3(256), 0, st, __VA_ARGS__);      \
-    else if ((C) <= 8) hipLaunchKernelGGL((KERNEL<8, FLAG, FLAG2>), grid, dim3(256), 0, st, __VA_ARGS__); \
-    else hipLaunchKernelGGL((KERNEL<16, FLAG, FLAG2>), grid, dim3(256), 0, st, __VA_ARGS__);              \
+// the same ladder for kernels with three more template arguments: KERNEL<CT, FLAG, FLAG2, FLAG3>
+#define LAUNCH_CT_FLAGS(KERNEL, FLAG, FLAG2, FLAG3, C, grid, st, ...)                                            \
+  do {                                                                                                           \
+    if ((C) <= 4) hipLaunchKernelGGL((KERNEL<4, FLAG, FLAG2, FLAG3>), grid, dim3(256), 0, st, __VA_ARGS__);      \
+    else if ((C) <= 8) hipLaunchKernelGGL((KERNEL<8, FLAG, FLAG2, FLAG3>), grid, dim3(256), 0, st, __VA_ARGS__); \
+    else hipLaunchKernelGGL((KERNEL<16, FLAG, FLAG2, FLAG3>), grid, dim3(256), 0, st, __VA_ARGS__);              \
   } while (0)
 
 // --------------------------------------------------------------------------- loss
@@ -53,11 +53,16 @@ __global__ void zero_f64_kernel(double* p, int n) {
 // OHEM (online hard example mining, ohem.h): slots 0 and 1 -- the CE's -- run over the pixels the selection kept, read from
 // the stored scores q[B*hw] and the record; the Dice slots 2..4 still run over every valid pixel.  The three arguments behind
 // gamma are read by the OHEM instances only.
-template <int CT, bool FOCAL, bool OHEM>
+// PW (per-pixel weights, hrseg.h "border weights"; without OHEM only): slots 0 and 1 become sum pw and sum pw t (1-p)^gamma logp,
+// with pw[B*hw] read by the PW instances only.  The weight multiplies t, so the term keeps the shape -- and the roundings --
+// of the instance without weights: a map of ones, or of any power of two, gives that instance's bits.
+template <int CT, bool FOCAL, bool OHEM, bool PW>
 __global__ __launch_bounds__(256) void loss_partials_kernel(const float* __restrict__ z, const float* __restrict__ t,
                                                             double* __restrict__ partial, int C, long hw,
                                                             long pix_per_block, float gamma, const float* __restrict__ q,
-                                                            const OhemRecord* __restrict__ rec, float thresh) {
+                                                            const OhemRecord* __restrict__ rec, float thresh,
+                                                            const float* __restrict__ pw) {
+  static_assert(!(OHEM && PW), "per-pixel weights are not combined with OHEM");
   __shared__ float red[4][CT * 5];
   const int b = blockIdx.y;
   const long lo = (long)blockIdx.x * pix_per_block;
@@ -74,6 +79,8 @@ __global__ __launch_bounds__(256) void loss_partials_kernel(const float* __restr
   for (long pix = lo + threadIdx.x; pix < hi; pix += 256) {
     bool kept = true;
     if constexpr (OHEM) kept = ohem_kept(q[(size_t)b * hw + pix], thresh, lam_k);
+    float wpix = 1.f;
+    if constexpr (PW) wpix = pw[(size_t)b * hw + pix];
     float zz[CT], tt[CT];
     float m = -INFINITY;
 #pragma unroll
@@ -100,16 +107,17 @@ __global__ __launch_bounds__(256) void loss_partials_kernel(const float* __restr
       if (c < C && tt[c] != -1.f) {
         const float logp = zz[c] - ls, p = expf(zz[c]) * inv;
         if (!OHEM || kept) {
-          acc[c][0] += 1.f;
+          const float wt = PW ? wpix * tt[c] : tt[c];
+          acc[c][0] += PW ? wpix : 1.f;
           if constexpr (FOCAL) {
             if (tt[c] != 0.f) {
               const float om = (pre + rest[c]) * inv;
-              acc[c][1] += tt[c] * focal_pow(om, gamma) * focal_logp(om, logp);
+              acc[c][1] += wt * focal_pow(om, gamma) * focal_logp(om, logp);
             } else {
-              acc[c][1] += tt[c] * logp;      // 0, or the NaN of a poisoned pixel
+              acc[c][1] += wt * logp;         // 0, or the NaN of a poisoned pixel
             }
           } else {
-            acc[c][1] += tt[c] * logp;
+            acc[c][1] += wt * logp;
           }
         }
         acc[c][2] += p * tt[c];
@@ -198,18 +206,23 @@ __global__ void loss_finalize_kernel(const double* __restrict__ partial, const f
 // softmax Jacobian behind it is the same.  The bracket is (1-p)^gamma (1 - gamma p log p / (1-p)), 0 in the limit 1-p -> 0.
 // OHEM: the selection is a constant, so the CE part of dz is simply 0 at the pixels it did not keep (the same stored scores
 // and record as the forward: the two cannot disagree); the Dice part is untouched.
-template <int CT, bool FOCAL, bool OHEM>
+// PW: the CE part of dz at a pixel is multiplied by pw there, through the CE's seed g[0] (one register, none more live: through t
+// the CT = 16 focal instance went to 168 bytes of scratch); the Dice part is untouched.
+template <int CT, bool FOCAL, bool OHEM, bool PW>
 __global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__ z, const float* __restrict__ t,
                                                        const float* __restrict__ coef, const float* __restrict__ g,
                                                        float* __restrict__ dz, int acc, int C, long hw, float gamma,
                                                        const float* __restrict__ q, const OhemRecord* __restrict__ rec,
-                                                       float thresh) {
+                                                       float thresh, const float* __restrict__ pw) {
+  static_assert(!(OHEM && PW), "per-pixel weights are not combined with OHEM");
   const int b = blockIdx.y;
   const long pix = (long)blockIdx.x * 256 + threadIdx.x;
   if (pix >= hw) return;
-  const float gce = g[0], gdice = g[1];
+  float gce = g[0];
+  const float gdice = g[1];
   bool kept = true;
   if constexpr (OHEM) kept = ohem_kept(q[(size_t)b * hw + pix], thresh, rec->lam_k);
+  if constexpr (PW) gce *= pw[(size_t)b * hw + pix];
   const float* zb = z + (size_t)b * C * hw + pix;
   const float* tb = t + (size_t)b * C * hw + pix;
   float zz[CT], tt[CT], p[CT];
@@ -274,11 +287,16 @@ static bool loss_option_ok(float v) { return v >= 0.f && v <= FLT_MAX; }
 // masked instances of the same kernels.
 struct OhemArgs { const float* q; const OhemRecord* rec; float thresh; };
 static const OhemArgs* const NO_OHEM = nullptr;
+// The _pw entry points are the _opt ones with one weight per pixel on the CE term (`pw` set; hrseg.h "border weights"): the PW
+// instances of the same kernels.  Never together with `ohem`.
+struct PixelWeights { const float* pw; };
+static const PixelWeights* const NO_PW = nullptr;
 
 static int loss_partials(const char* name, const float* z, const float* t, double* partial, int B, int C, long hw,
-                         float gamma, const OhemArgs* ohem, hrseg_stream_t stream) {
+                         float gamma, const OhemArgs* ohem, const PixelWeights* pixw, hrseg_stream_t stream) {
   HRSEG_CHECK_ARG(z && t && partial && B > 0 && C > 0 && C <= MAXC && hw > 0, "%s: bad arguments (C=%d)", name, C);
   HRSEG_CHECK_ARG(loss_option_ok(gamma), "%s: gamma must be finite and >= 0 (got %g)", name, (double)gamma);
+  if (pixw) HRSEG_CHECK_ARG(pixw->pw && !ohem, "%s: null pointer (pw)", name);
   if (ohem) {
     HRSEG_CHECK_ARG(ohem->q && ohem->rec, "%s: null pointer (q, record)", name);
     HRSEG_CHECK_ARG(ohem_thresh_ok(ohem->thresh), "%s: thresh must be a finite number in [0, 1] (got %g)", name, (double)ohem->thresh);
@@ -293,13 +311,17 @@ static int loss_partials(const char* name, const float* z, const float* t, doubl
   const float* q = ohem ? ohem->q : nullptr;
   const OhemRecord* rec = ohem ? ohem->rec : nullptr;
   const float thresh = ohem ? ohem->thresh : 0.f;
+  const float* pw = pixw ? pixw->pw : nullptr;
   if (ohem) {
-    if (gamma > 0.f) LAUNCH_CT_FLAGS(loss_partials_kernel, true, true, C, grid, st, z, t, partial, C, hw, ppb, gamma, q, rec, thresh);
-    else LAUNCH_CT_FLAGS(loss_partials_kernel, false, true, C, grid, st, z, t, partial, C, hw, ppb, gamma, q, rec, thresh);
+    if (gamma > 0.f) LAUNCH_CT_FLAGS(loss_partials_kernel, true, true, false, C, grid, st, z, t, partial, C, hw, ppb, gamma, q, rec, thresh, pw);
+    else LAUNCH_CT_FLAGS(loss_partials_kernel, false, true, false, C, grid, st, z, t, partial, C, hw, ppb, gamma, q, rec, thresh, pw);
     hrseg_count(CNT_OHEM);
+  } else if (pixw) {
+    if (gamma > 0.f) LAUNCH_CT_FLAGS(loss_partials_kernel, true, false, true, C, grid, st, z, t, partial, C, hw, ppb, gamma, q, rec, thresh, pw);
+    else LAUNCH_CT_FLAGS(loss_partials_kernel, false, false, true, C, grid, st, z, t, partial, C, hw, ppb, gamma, q, rec, thresh, pw);
   } else {
-    if (gamma > 0.f) LAUNCH_CT_FLAGS(loss_partials_kernel, true, false, C, grid, st, z, t, partial, C, hw, ppb, gamma, q, rec, thresh);
-    else LAUNCH_CT_FLAGS(loss_partials_kernel, false, false, C, grid, st, z, t, partial, C, hw, ppb, gamma, q, rec, thresh);
+    if (gamma > 0.f) LAUNCH_CT_FLAGS(loss_partials_kernel, true, false, false, C, grid, st, z, t, partial, C, hw, ppb, gamma, q, rec, thresh, pw);
+    else LAUNCH_CT_FLAGS(loss_partials_kernel, false, false, false, C, grid, st, z, t, partial, C, hw, ppb, gamma, q, rec, thresh, pw);
   }
   HRSEG_LAUNCH_CHECK("loss_partials");
   return 0;
@@ -318,9 +340,11 @@ static int loss_finalize(const char* name, const double* partial, const float* w
 }
 
 static int loss_bwd(const char* name, const float* z, const float* t, const float* coef, const float* g, float* dz,
-                    int accumulate, int B, int C, long hw, float gamma, const OhemArgs* ohem, hrseg_stream_t stream) {
+                    int accumulate, int B, int C, long hw, float gamma, const OhemArgs* ohem, const PixelWeights* pixw,
+                    hrseg_stream_t stream) {
   HRSEG_CHECK_ARG(z && t && coef && g && dz && B > 0 && C > 0 && C <= MAXC && hw > 0, "%s: bad arguments", name);
   HRSEG_CHECK_ARG(loss_option_ok(gamma), "%s: gamma must be finite and >= 0 (got %g)", name, (double)gamma);
+  if (pixw) HRSEG_CHECK_ARG(pixw->pw && !ohem, "%s: null pointer (pw)", name);
   if (ohem) {
     HRSEG_CHECK_ARG(ohem->q && ohem->rec, "%s: null pointer (q, record)", name);
     HRSEG_CHECK_ARG(ohem_thresh_ok(ohem->thresh), "%s: thresh must be a finite number in [0, 1] (got %g)", name, (double)ohem->thresh);
@@ -330,13 +354,17 @@ static int loss_bwd(const char* name, const float* z, const float* t, const floa
   const float* q = ohem ? ohem->q : nullptr;
   const OhemRecord* rec = ohem ? ohem->rec : nullptr;
   const float thresh = ohem ? ohem->thresh : 0.f;
+  const float* pw = pixw ? pixw->pw : nullptr;
   if (ohem) {
-    if (gamma > 0.f) LAUNCH_CT_FLAGS(loss_bwd_kernel, true, true, C, grid, st, z, t, coef, g, dz, accumulate, C, hw, gamma, q, rec, thresh);
-    else LAUNCH_CT_FLAGS(loss_bwd_kernel, false, true, C, grid, st, z, t, coef, g, dz, accumulate, C, hw, gamma, q, rec, thresh);
+    if (gamma > 0.f) LAUNCH_CT_FLAGS(loss_bwd_kernel, true, true, false, C, grid, st, z, t, coef, g, dz, accumulate, C, hw, gamma, q, rec, thresh, pw);
+    else LAUNCH_CT_FLAGS(loss_bwd_kernel, false, true, false, C, grid, st, z, t, coef, g, dz, accumulate, C, hw, gamma, q, rec, thresh, pw);
     hrseg_count(CNT_OHEM);
+  } else if (pixw) {
+    if (gamma > 0.f) LAUNCH_CT_FLAGS(loss_bwd_kernel, true, false, true, C, grid, st, z, t, coef, g, dz, accumulate, C, hw, gamma, q, rec, thresh, pw);
+    else LAUNCH_CT_FLAGS(loss_bwd_kernel, false, false, true, C, grid, st, z, t, coef, g, dz, accumulate, C, hw, gamma, q, rec, thresh, pw);
   } else {
-    if (gamma > 0.f) LAUNCH_CT_FLAGS(loss_bwd_kernel, true, false, C, grid, st, z, t, coef, g, dz, accumulate, C, hw, gamma, q, rec, thresh);
-    else LAUNCH_CT_FLAGS(loss_bwd_kernel, false, false, C, grid, st, z, t, coef, g, dz, accumulate, C, hw, gamma, q, rec, thresh);
+    if (gamma > 0.f) LAUNCH_CT_FLAGS(loss_bwd_kernel, true, false, false, C, grid, st, z, t, coef, g, dz, accumulate, C, hw, gamma, q, rec, thresh, pw);
+    else LAUNCH_CT_FLAGS(loss_bwd_kernel, false, false, false, C, grid, st, z, t, coef, g, dz, accumulate, C, hw, gamma, q, rec, thresh, pw);
   }
   HRSEG_LAUNCH_CHECK("loss_bwd");
   return 0;
@@ -344,11 +372,11 @@ static int loss_bwd(const char* name, const float* z, const float* t, const floa
 
 extern "C" int hrseg_loss_partials(const float* z, const float* t, double* partial, int B, int C, long hw,
                                    hrseg_stream_t stream) {
-  return loss_partials("hrseg_loss_partials", z, t, partial, B, C, hw, 0.f, NO_OHEM, stream);
+  return loss_partials("hrseg_loss_partials", z, t, partial, B, C, hw, 0.f, NO_OHEM, NO_PW, stream);
 }
 extern "C" int hrseg_loss_partials_opt(const float* z, const float* t, double* partial, int B, int C, long hw, float gamma,
                                        hrseg_stream_t stream) {
-  return loss_partials("hrseg_loss_partials_opt", z, t, partial, B, C, hw, gamma, NO_OHEM, stream);
+  return loss_partials("hrseg_loss_partials_opt", z, t, partial, B, C, hw, gamma, NO_OHEM, NO_PW, stream);
 }
 extern "C" int hrseg_loss_finalize(const double* partial, const float* w, int B, int C, float* out, float* coef,
                                    hrseg_stream_t stream) {
@@ -360,22 +388,32 @@ extern "C" int hrseg_loss_finalize_opt(const double* partial, const float* w, in
 }
 extern "C" int hrseg_loss_bwd(const float* z, const float* t, const float* coef, const float* g, float* dz,
                               int accumulate, int B, int C, long hw, hrseg_stream_t stream) {
-  return loss_bwd("hrseg_loss_bwd", z, t, coef, g, dz, accumulate, B, C, hw, 0.f, NO_OHEM, stream);
+  return loss_bwd("hrseg_loss_bwd", z, t, coef, g, dz, accumulate, B, C, hw, 0.f, NO_OHEM, NO_PW, stream);
 }
 extern "C" int hrseg_loss_bwd_opt(const float* z, const float* t, const float* coef, const float* g, float* dz,
                                   int accumulate, int B, int C, long hw, float gamma, hrseg_stream_t stream) {
-  return loss_bwd("hrseg_loss_bwd_opt", z, t, coef, g, dz, accumulate, B, C, hw, gamma, NO_OHEM, stream);
+  return loss_bwd("hrseg_loss_bwd_opt", z, t, coef, g, dz, accumulate, B, C, hw, gamma, NO_OHEM, NO_PW, stream);
 }
 extern "C" int hrseg_loss_partials_ohem(const float* z, const float* t, const float* q, const void* record, float thresh,
                                         double* partial, int B, int C, long hw, float gamma, hrseg_stream_t stream) {
   const OhemArgs ohem = {q, (const OhemRecord*)record, thresh};
-  return loss_partials("hrseg_loss_partials_ohem", z, t, partial, B, C, hw, gamma, &ohem, stream);
+  return loss_partials("hrseg_loss_partials_ohem", z, t, partial, B, C, hw, gamma, &ohem, NO_PW, stream);
 }
 extern "C" int hrseg_loss_bwd_ohem(const float* z, const float* t, const float* q, const void* record, float thresh,
                                    const float* coef, const float* g, float* dz, int accumulate, int B, int C, long hw,
                                    float gamma, hrseg_stream_t stream) {
   const OhemArgs ohem = {q, (const OhemRecord*)record, thresh};
-  return loss_bwd("hrseg_loss_bwd_ohem", z, t, coef, g, dz, accumulate, B, C, hw, gamma, &ohem, stream);
+  return loss_bwd("hrseg_loss_bwd_ohem", z, t, coef, g, dz, accumulate, B, C, hw, gamma, &ohem, NO_PW, stream);
+}
+extern "C" int hrseg_loss_partials_pw(const float* z, const float* t, const float* pw, double* partial, int B, int C, long hw,
+                                      float gamma, hrseg_stream_t stream) {
+  const PixelWeights pixw = {pw};
+  return loss_partials("hrseg_loss_partials_pw", z, t, partial, B, C, hw, gamma, NO_OHEM, &pixw, stream);
+}
+extern "C" int hrseg_loss_bwd_pw(const float* z, const float* t, const float* pw, const float* coef, const float* g, float* dz,
+                                 int accumulate, int B, int C, long hw, float gamma, hrseg_stream_t stream) {
+  const PixelWeights pixw = {pw};
+  return loss_bwd("hrseg_loss_bwd_pw", z, t, coef, g, dz, accumulate, B, C, hw, gamma, NO_OHEM, &pixw, stream);
 }
 
 // --------------------------------------------------------------------------- predictions / confusion counts

@@ -1674,43 +1674,96 @@ def ohem_select(q, thresh, min_kept, record=None, workspace=None):
     return record
 
 
-def loss_fwd(z, t, w, options=None, ohem=None):
+BORDER_MAX_RADIUS = 32              # HRSEG_BORDER_MAX_RADIUS
+BORDER_MAX_PIXELS = 1 << 31
+
+
+def border_weights(t, radius, lut, want_d2=False):
+    """t [B,C,H,W] fp32 target planes (-1 / 0 / 1), lut [radius^2 + 1] fp32 on t's device -> (labels [B,H,W] uint8,
+    v [B,H,W] fp32[, d2 [B,H,W] int32]): the label map, lut[d2] and the squared distance to the nearest other label within
+    `radius` (include/hrseg.h, "border weights"; hrseg_border_weights)"""
+    if t.dim() != 4 or min(t.shape) < 1:
+        raise ValueError(f"border_weights: t must be [B,C,H,W], got {tuple(t.shape)}")
+    B, Cn, H, W = t.shape
+    if Cn > 16:
+        raise ValueError(f"border_weights: {Cn} channels, at most 16")
+    if H * W >= BORDER_MAX_PIXELS:
+        raise ValueError(f"border_weights: {H} x {W} has 2^31 pixels or more")
+    radius = int(radius)
+    if not 1 <= radius <= BORDER_MAX_RADIUS:
+        raise ValueError(f"border_weights: radius {radius} outside 1..{BORDER_MAX_RADIUS}")
+    assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous(), "border_weights: t must be contiguous fp32 on the device"
+    assert lut.dtype == torch.float32 and lut.device == t.device and lut.is_contiguous(), \
+        "border_weights: lut must be contiguous fp32 on t's device"
+    if lut.numel() != radius * radius + 1:
+        raise ValueError(f"border_weights: lut has {lut.numel()} entries, radius {radius} needs {radius * radius + 1}")
+    labels = torch.empty((B, H, W), dtype=torch.uint8, device=t.device)
+    v = torch.empty((B, H, W), dtype=torch.float32, device=t.device)
+    d2 = torch.empty((B, H, W), dtype=torch.int32, device=t.device) if want_d2 else None
+    call("hrseg_border_weights", ptr(t), B, Cn, H, W, radius, ptr(lut), ptr(labels), ptr(v), ptr(d2))
+    return (labels, v, d2) if want_d2 else (labels, v)
+
+
+def _pixel_weight(who, pw, z):
+    """a [B,H,W] / [B,1,H,W] / [B*H*W] fp32 tensor on z's device, contiguous -> itself"""
+    B, _, H, W = z.shape
+    assert pw.dtype == torch.float32 and pw.device == z.device and pw.is_contiguous() and pw.numel() == B * H * W, \
+        f"{who}: pixel_weight must be contiguous fp32 [B,H,W] on the logits' device"
+    return pw
+
+
+def loss_fwd(z, t, w, options=None, ohem=None, pixel_weight=None):
     """-> (out[3] = ce, dice, n_valid_dice ; coef for the backward).  options = (focal gamma, Dice smooth, Tversky alpha,
     beta) selects the hrseg_loss_*_opt entry points; None = the calls without options (gamma 0, smooth 0, alpha = beta = 0.5).
     ohem = (thresh, min_kept): online hard example mining on the CE term -- scores, selection, then the masked partials; the
-    return value gains a third entry, the OhemState loss_bwd needs.  None = exactly the calls above."""
+    return value gains a third entry, the OhemState loss_bwd needs.  None = exactly the calls above.
+    pixel_weight [B,H,W] fp32: one weight per pixel on the CE term (hrseg_loss_partials_pw; include/hrseg.h, "border
+    weights"); not together with ohem.  None = exactly the calls above."""
     z, t = _c(z), _c(t)
     B, Cn, H, W = z.shape
+    if pixel_weight is not None and ohem is not None:
+        raise ValueError("loss_fwd: pixel_weight and ohem are not combined")
     part = torch.empty(B * Cn * 5, dtype=torch.float64, device=z.device)
     out = torch.empty(3, dtype=torch.float32, device=z.device)
     coef = torch.empty(B * Cn * 4, dtype=torch.float32, device=z.device)
     state = None
+    own = ohem is not None or pixel_weight is not None          # the partials come from an entry point of the option's own
     if ohem is not None:
         thresh, min_kept = float(ohem[0]), int(ohem[1])
         q = ohem_scores(z, t)
         state = OhemState(thresh, min_kept, q, ohem_select(q, thresh, min_kept))
         gamma = 0.0 if options is None else float(options[0])
         call("hrseg_loss_partials_ohem", ptr(z), ptr(t), ptr(q), ptr(state.record), thresh, ptr(part), B, Cn, H * W, gamma)
+    elif pixel_weight is not None:
+        pw = _pixel_weight("loss_fwd", pixel_weight, z)
+        call("hrseg_loss_partials_pw", ptr(z), ptr(t), ptr(pw), ptr(part), B, Cn, H * W, 0.0 if options is None else float(options[0]))
     if options is None:
-        if ohem is None:
+        if not own:
             call("hrseg_loss_partials", ptr(z), ptr(t), ptr(part), B, Cn, H * W)
         call("hrseg_loss_finalize", ptr(part), ptr(w), B, Cn, ptr(out), ptr(coef))
     else:
         gamma, smooth, alpha, beta = (float(v) for v in options)
-        if ohem is None:
+        if not own:
             call("hrseg_loss_partials_opt", ptr(z), ptr(t), ptr(part), B, Cn, H * W, gamma)
         call("hrseg_loss_finalize_opt", ptr(part), ptr(w), B, Cn, smooth, alpha, beta, ptr(out), ptr(coef))
     return (out, coef) if ohem is None else (out, coef, state)
 
 
-def loss_bwd(z, t, coef, g, dz=None, accumulate=False, options=None, ohem=None):
+def loss_bwd(z, t, coef, g, dz=None, accumulate=False, options=None, ohem=None, pixel_weight=None):
     """`options`: the ones loss_fwd produced `coef` with (the backward itself reads the focal gamma only); `ohem`: the
-    OhemState that loss_fwd returned (the keep decision is read from its stored scores and record, never recomputed)"""
+    OhemState that loss_fwd returned (the keep decision is read from its stored scores and record, never recomputed);
+    `pixel_weight`: the map loss_fwd was given (hrseg_loss_bwd_pw)"""
     z, t = _c(z), _c(t)
     B, Cn, H, W = z.shape
     if dz is None:
         dz, accumulate = torch.empty_like(z), False
-    if ohem is not None:
+    if pixel_weight is not None:
+        if ohem is not None:
+            raise ValueError("loss_bwd: pixel_weight and ohem are not combined")
+        pw = _pixel_weight("loss_bwd", pixel_weight, z)
+        call("hrseg_loss_bwd_pw", ptr(z), ptr(t), ptr(pw), ptr(coef), ptr(g), ptr(dz), int(accumulate), B, Cn, H * W,
+             0.0 if options is None else float(options[0]))
+    elif ohem is not None:
         call("hrseg_loss_bwd_ohem", ptr(z), ptr(t), ptr(ohem.q), ptr(ohem.record), float(ohem.thresh), ptr(coef), ptr(g), ptr(dz),
              int(accumulate), B, Cn, H * W, 0.0 if options is None else float(options[0]))
     elif options is None:

@@ -444,7 +444,8 @@ def get_loss(output_logits, targets, lossFuncts, levelLoss, level_weights=None, 
         ce_fn, dice_fn = lossFuncts[L][0], lossFuncts[L][1]
         if isinstance(ce_fn, losses.CrossEntropyLoss) and isinstance(dice_fn, losses.SoftDiceLoss):
             res = losses.fused_ce_dice(output_logits[L], targets[L], level_weight, losses.LossOptions.from_pair(ce_fn, dice_fn),
-                                       ohem=losses.OhemOptions.from_ce(ce_fn), record_to=ce_fn)
+                                       ohem=losses.OhemOptions.from_ce(ce_fn), record_to=ce_fn,
+                                       pixel_weight=ce_fn.border_map(targets[L]))
             # Dice is 0 with zero gradient when no item is valid == the reference skipping None; under data
             # parallelism its divisor is the global count of valid items (losses.global_batch_dice)
             sync = (torch.is_grad_enabled() and res.requires_grad) if sync_dice is None else bool(sync_dice)
@@ -527,6 +528,10 @@ class GraphedTrainStep:
                if isinstance(fns[0], losses.CrossEntropyLoss)):
             raise NotImplementedError("GraphedTrainStep: online hard example mining (CrossEntropyLoss(ohem_thresh=...)) has not been "
                                       "run inside a captured hipGraph; use the taped or the eager step")
+        if any(losses.BorderOptions.from_ce(fns[0]) is not None for fns in lossFuncts
+               if isinstance(fns[0], losses.CrossEntropyLoss)):
+            raise NotImplementedError("GraphedTrainStep: border weights (CrossEntropyLoss(border=...)) have not been run inside a "
+                                      "captured hipGraph; use the taped or the eager step")
         self.model, self.optimizer = model, optimizer
         self.x, self.t = data.clone(), target.clone()
         level_loss = []
@@ -612,6 +617,13 @@ class TapedTrainStep:
         self.ohem_opts = [losses.OhemOptions.from_ce(lossFuncts[L][0]) for L in range(self.n_levels)]
         self.ohem = [None] * self.n_levels
         self._ce_fns = [lossFuncts[L][0] for L in range(self.n_levels)]
+        # and its border weights (None = off): the table is copied to the device here, outside the pool and the recording; the
+        # label map and the weight map of a level are buffers of the step, left in the loss object's `border` / `last_border`
+        self.border = [getattr(fn, "border", None) for fn in self._ce_fns]
+        self.border_maps = [None] * self.n_levels               # (label map, weight map) of the level's latest step
+        for bw in self.border:
+            if bw is not None:
+                bw.lut(dev)
         # d loss / d (ce, dice, n_valid) per level; the Dice entry carries the data-parallel divisor correction
         self.seed = [torch.tensor([1.0, 1.0, 0.0], dtype=torch.float32, device=dev) for _ in range(self.n_levels)]
         self._n_all = torch.zeros(self.n_levels, dtype=torch.float32, device=dev)
@@ -672,7 +684,7 @@ class TapedTrainStep:
             p.grad = None
         run = m._run(self.x, True)
         logits = run.logits
-        onehots, cms, outs, coefs, ohem = [], [], [], [], [None] * self.n_levels
+        onehots, cms, outs, coefs, ohem, pw = [], [], [], [], [None] * self.n_levels, [None] * self.n_levels
         for L, (z, t) in enumerate(zip(logits, self.t_levels)):
             oh, cm = ops.predict_metrics(z, t, child=(L > 0), mask_pred=True)
             onehots.append(oh)
@@ -682,7 +694,12 @@ class TapedTrainStep:
                 outs.append(None)
                 coefs.append(None)
                 continue
-            if self.ohem_opts[L] is None:
+            if self.border[L] is not None:
+                pw[L] = self._ce_fns[L].border_map(t)
+                self.border_maps[L] = (self.border[L].labels, pw[L])    # (one BorderWeights may serve several levels)
+            if pw[L] is not None:
+                o, c = ops.loss_fwd(z, t, self.w[L], self.opts[L], pixel_weight=pw[L])
+            elif self.ohem_opts[L] is None:
                 o, c = ops.loss_fwd(z, t, self.w[L], self.opts[L])
             else:
                 o, c, ohem[L] = ops.loss_fwd(z, t, self.w[L], self.opts[L], ohem=self.ohem_opts[L])
@@ -700,7 +717,7 @@ class TapedTrainStep:
             if len(live) != self.n_levels:
                 raise NotImplementedError("TapedTrainStep: level0_pretrain_epochs together with data parallelism")
             _lib.host_call(lambda: self._dice_sync(live))
-        dz = [ops.loss_bwd(z, t, coefs[L], self.seed[L], options=self.opts[L], ohem=ohem[L]) if outs[L] is not None else None
+        dz = [ops.loss_bwd(z, t, coefs[L], self.seed[L], options=self.opts[L], ohem=ohem[L], pixel_weight=pw[L]) if outs[L] is not None else None
               for L, (z, t) in enumerate(zip(logits, self.t_levels))]
         n_probs = len(run.probs)
         run.backward([None] * n_probs, dz)
@@ -819,7 +836,8 @@ def taped_step_for(model, optimizer, lossFuncts, args, class_tree, data, target,
            bool(getattr(optimizer, "clip_path", False)),       # the path, not the threshold: that lives on the device
            bool(getattr(optimizer, "ema_path", False)),        # likewise: the decay is read from device memory
            tuple(losses.LossOptions.from_pair(c, d) for c, d in lossFuncts),   # by value in the recorded loss calls
-           tuple(losses.OhemOptions.from_ce(c) for c, _ in lossFuncts))        # likewise: thresh and min_kept of every level
+           tuple(losses.OhemOptions.from_ce(c) for c, _ in lossFuncts),        # likewise: thresh and min_kept of every level
+           tuple(losses.BorderOptions.from_ce(c) for c, _ in lossFuncts))      # likewise: w0, sigma and radius (table and search)
     cache = m.__dict__.setdefault("_hr_tapes", {})
     step = cache.get(key)
     if step is not None:
