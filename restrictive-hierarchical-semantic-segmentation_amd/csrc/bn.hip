@@ -817,10 +817,12 @@ extern "C" int hrseg_bn_fold(const float* w, const float* bias, const float* gam
 static int check_bn_fwd(const hrseg_bn_fwd_t& p, int training, int phases) {
   if (int e = check_c(p.C, "hrseg_bn_fwd_group")) return e;
   const bool stats = training && (phases & 1), finalize = phases & 2, apply = phases & 4;
-  HRSEG_CHECK_ARG(p.coef, "hrseg_bn_fwd_group: bad tensor arguments (coef)");
-  HRSEG_CHECK_ARG(!(stats || apply) || (p.y && p.ldy >= p.C && p.ldy % 4 == 0), "hrseg_bn_fwd_group: bad tensor arguments (y, ldy)");
+  HRSEG_CHECK_ARG(p.coef && al16(p.coef), "hrseg_bn_fwd_group: bad tensor arguments (coef)");
+  HRSEG_CHECK_ARG(!(stats || apply) || (p.y && p.ldy >= p.C && p.ldy % 4 == 0 && al16(p.y)), "hrseg_bn_fwd_group: bad tensor arguments (y, ldy)");
   HRSEG_CHECK_ARG(!(stats || apply || (training && finalize)) || p.npix > 0, "hrseg_bn_fwd_group: bad tensor arguments (npix)");
-  HRSEG_CHECK_ARG(!apply || (p.z && p.ldz >= p.C && p.ldz % 4 == 0), "hrseg_bn_fwd_group: bad tensor arguments (the apply phase needs z, ldz)");
+  HRSEG_CHECK_ARG(!apply || (p.z && p.ldz >= p.C && p.ldz % 4 == 0 && al16(p.z)), "hrseg_bn_fwd_group: bad tensor arguments (the apply phase needs z, ldz)");
+  if (apply && p.residual)
+    if (int e = check_operand(p.residual, p.ldr, p.C, "hrseg_bn_fwd_group", "residual")) return e;
   HRSEG_CHECK_ARG(!(stats || (training && finalize)) || (p.partial && p.nchunks > 0), "hrseg_bn_fwd_group: training needs partial/nchunks");
   HRSEG_CHECK_ARG(training || !finalize || (p.running_mean && p.running_var), "hrseg_bn_fwd_group: eval needs running stats");
   return 0;
@@ -884,6 +886,14 @@ extern "C" int hrseg_bn_bwd_group_phases(int n, const hrseg_bn_bwd_t* probs, int
                     "hrseg_bn_bwd_group: bad arguments");
     HRSEG_CHECK_ARG(p.nseg <= 1 || (p.nchunks % p.nseg == 0 && p.npix % p.nseg == 0),
                     "hrseg_bn_bwd_group: nseg=%d must divide nchunks=%d and npix", p.nseg, p.nchunks);
+    if (int e = check_operand(p.dz, p.lddz, p.C, "hrseg_bn_bwd_group", "dz")) return e;
+    if (int e = check_operand(p.y, p.ldy, p.C, "hrseg_bn_bwd_group", "y")) return e;
+    if (int e = check_operand(p.dy, p.lddy, p.C, "hrseg_bn_bwd_group", "dy")) return e;
+    if (p.relu && p.z)
+      if (int e = check_operand(p.z, p.ldz, p.C, "hrseg_bn_bwd_group", "z")) return e;
+    if (p.dres)
+      if (int e = check_operand(p.dres, p.lddres, p.C, "hrseg_bn_bwd_group", "dres")) return e;
+    HRSEG_CHECK_ARG(al16(p.coef), "hrseg_bn_bwd_group: coef must be 16-byte aligned");
     g.p[i] = p;
   }
   int end = 0;

@@ -776,6 +776,8 @@ extern "C" int hrseg_maxpool2_fwd(const float* x, int ldx, float* y, int ldy, in
                                   hrseg_stream_t stream) {
   if (int e = check_c(C, "hrseg_maxpool2_fwd")) return e;
   HRSEG_CHECK_ARG(x && y && B > 0 && Hi >= 2 && Wi >= 2, "hrseg_maxpool2_fwd: bad arguments");
+  if (int e = check_operand(x, ldx, C, "hrseg_maxpool2_fwd", "x")) return e;
+  if (int e = check_operand(y, ldy, C, "hrseg_maxpool2_fwd", "y")) return e;
   const long npix = (long)B * (Hi / 2) * (Wi / 2);
   hipLaunchKernelGGL(maxpool2_fwd_kernel, dim3(elem_grid(npix, C)), dim3(256), 0, (hipStream_t)stream, x, ldx, y, ldy,
                      B, Hi, Wi, C);
@@ -787,6 +789,9 @@ extern "C" int hrseg_maxpool2_bwd(const float* x, int ldx, const float* dy, int 
                                   int accumulate, int B, int Hi, int Wi, int C, hrseg_stream_t stream) {
   if (int e = check_c(C, "hrseg_maxpool2_bwd")) return e;
   HRSEG_CHECK_ARG(x && dy && dx && B > 0 && Hi >= 2 && Wi >= 2, "hrseg_maxpool2_bwd: bad arguments");
+  if (int e = check_operand(x, ldx, C, "hrseg_maxpool2_bwd", "x")) return e;
+  if (int e = check_operand(dy, lddy, C, "hrseg_maxpool2_bwd", "dy")) return e;
+  if (int e = check_operand(dx, lddx, C, "hrseg_maxpool2_bwd", "dx")) return e;
   const long ncell = (long)B * ((Hi + 1) / 2) * ((Wi + 1) / 2);
   hipLaunchKernelGGL(maxpool2_bwd_kernel, dim3(elem_grid(ncell, C)), dim3(256), 0, (hipStream_t)stream, x, ldx, dy,
                      lddy, dx, lddx, accumulate, B, Hi, Wi, C);
@@ -801,6 +806,8 @@ extern "C" int hrseg_bilinear_fwd(const float* in, int ldin, int B, int Hi, int 
   HRSEG_CHECK_ARG(in && out && B > 0 && Hi > 0 && Wi > 0 && Hr > 0 && Wr > 0 && py >= 0 && px >= 0 &&
                       py + Hr <= Hout && px + Wr <= Wout,
                   "hrseg_bilinear_fwd: placed image %dx%d at (%d,%d) does not fit %dx%d", Hr, Wr, py, px, Hout, Wout);
+  if (int e = check_operand(in, ldin, C, "hrseg_bilinear_fwd", "in")) return e;
+  if (int e = check_operand(out, ldout, C, "hrseg_bilinear_fwd", "out")) return e;
   const long npix = (long)B * Hout * Wout;
   hipLaunchKernelGGL(bilinear_fwd_kernel, dim3(elem_grid(npix, C)), dim3(256), 0, (hipStream_t)stream, in, ldin, B, Hi,
                      Wi, C, out, ldout, Hout, Wout, Hr, Wr, py, px, resize_scale(Hi, Hr, align_corners),
@@ -816,6 +823,8 @@ extern "C" int hrseg_bilinear_bwd(const float* dout, int lddout, int B, int Hi, 
   HRSEG_CHECK_ARG(dout && din && B > 0 && Hi > 0 && Wi > 0 && Hr > 0 && Wr > 0 && py >= 0 && px >= 0 &&
                       py + Hr <= Hout && px + Wr <= Wout,
                   "hrseg_bilinear_bwd: bad geometry");
+  if (int e = check_operand(dout, lddout, C, "hrseg_bilinear_bwd", "dout")) return e;
+  if (int e = check_operand(din, lddin, C, "hrseg_bilinear_bwd", "din")) return e;
   const long npix = (long)B * Hi * Wi;
   // row splits: enough blocks to fill the chip, at most half the footprint rows, Q*RS <= 256
   const int Q = C / 4;
@@ -842,14 +851,15 @@ extern "C" int hrseg_fuse_sum(int n_same, const float* const* same, const int* l
   HRSEG_CHECK_ARG(n_same >= 1 && n_same <= 4 && n_low >= 0 && n_low <= 3 && same && ld_same && out && B > 0 && H > 0 && W > 0,
                   "hrseg_fuse_sum: 1..4 same-resolution terms and 0..3 low-resolution terms");
   HRSEG_CHECK_ARG(n_low == 0 || (low && ld_low && Hi && Wi), "hrseg_fuse_sum: low-resolution terms need their geometry");
+  if (int e = check_operand(out, ldo, C, "hrseg_fuse_sum", "out")) return e;
   FuseSumArgs a{};
   a.n_same = n_same; a.n_low = n_low;
   for (int i = 0; i < n_same; ++i) {
-    HRSEG_CHECK_ARG(same[i] && ld_same[i] >= C && ld_same[i] % 4 == 0, "hrseg_fuse_sum: bad same-resolution term %d", i);
+    HRSEG_CHECK_ARG(same[i] && ld_same[i] >= C && ld_same[i] % 4 == 0 && al16(same[i]), "hrseg_fuse_sum: bad same-resolution term %d", i);
     a.same[i] = same[i]; a.ld_same[i] = ld_same[i];
   }
   for (int j = 0; j < n_low; ++j) {
-    HRSEG_CHECK_ARG(low[j] && ld_low[j] >= C && ld_low[j] % 4 == 0 && Hi[j] > 0 && Wi[j] > 0, "hrseg_fuse_sum: bad low-resolution term %d", j);
+    HRSEG_CHECK_ARG(low[j] && ld_low[j] >= C && ld_low[j] % 4 == 0 && al16(low[j]) && Hi[j] > 0 && Wi[j] > 0, "hrseg_fuse_sum: bad low-resolution term %d", j);
     a.low[j] = low[j]; a.ld_low[j] = ld_low[j]; a.Hi[j] = Hi[j]; a.Wi[j] = Wi[j];
     a.sh[j] = resize_scale(Hi[j], H, align_corners);
     a.sw[j] = resize_scale(Wi[j], W, align_corners);
@@ -1058,6 +1068,9 @@ extern "C" int hrseg_add(const float* a, int lda, const float* b, int ldb, float
                          int C, hrseg_stream_t stream) {
   if (int e = check_c(C, "hrseg_add")) return e;
   HRSEG_CHECK_ARG(a && b && out && npix > 0, "hrseg_add: bad arguments");
+  if (int e = check_operand(a, lda, C, "hrseg_add", "a")) return e;
+  if (int e = check_operand(b, ldb, C, "hrseg_add", "b")) return e;
+  if (int e = check_operand(out, ldo, C, "hrseg_add", "out")) return e;
   hipLaunchKernelGGL(add_kernel, dim3(elem_grid(npix, C)), dim3(256), 0, (hipStream_t)stream, a, lda, b, ldb, out, ldo,
                      relu, npix, C);
   HRSEG_LAUNCH_CHECK("add");
@@ -1068,6 +1081,8 @@ extern "C" int hrseg_copy(const float* in, int ldin, float* out, int ldout, int 
                           hrseg_stream_t stream) {
   if (int e = check_c(C, "hrseg_copy")) return e;
   HRSEG_CHECK_ARG(in && out && npix > 0, "hrseg_copy: bad arguments");
+  if (int e = check_operand(in, ldin, C, "hrseg_copy", "in")) return e;
+  if (int e = check_operand(out, ldout, C, "hrseg_copy", "out")) return e;
   hipLaunchKernelGGL(copy_kernel, dim3(elem_grid(npix, C)), dim3(256), 0, (hipStream_t)stream, in, ldin, out, ldout,
                      accumulate, npix, C);
   HRSEG_LAUNCH_CHECK("copy");
@@ -1078,6 +1093,9 @@ extern "C" int hrseg_relu_bwd(const float* dz, int lddz, const float* z, int ldz
                               int C, hrseg_stream_t stream) {
   if (int e = check_c(C, "hrseg_relu_bwd")) return e;
   HRSEG_CHECK_ARG(dz && z && dx && npix > 0, "hrseg_relu_bwd: bad arguments");
+  if (int e = check_operand(dz, lddz, C, "hrseg_relu_bwd", "dz")) return e;
+  if (int e = check_operand(z, ldz, C, "hrseg_relu_bwd", "z")) return e;
+  if (int e = check_operand(dx, lddx, C, "hrseg_relu_bwd", "dx")) return e;
   hipLaunchKernelGGL(relu_bwd_kernel, dim3(elem_grid(npix, C)), dim3(256), 0, (hipStream_t)stream, dz, lddz, z, ldz,
                      dx, lddx, npix, C);
   HRSEG_LAUNCH_CHECK("relu_bwd");
@@ -1086,7 +1104,8 @@ extern "C" int hrseg_relu_bwd(const float* dz, int lddz, const float* z, int ldz
 
 extern "C" int hrseg_absmax(const float* x, int ldx, long npix, int C, float* out64, hrseg_stream_t stream) {
   if (int e = check_c(C, "hrseg_absmax")) return e;
-  HRSEG_CHECK_ARG(x && out64 && npix > 0 && ldx >= C, "hrseg_absmax: bad arguments");
+  HRSEG_CHECK_ARG(x && out64 && npix > 0, "hrseg_absmax: bad arguments");
+  if (int e = check_operand(x, ldx, C, "hrseg_absmax", "x")) return e;
   hipLaunchKernelGGL(absmax_kernel, dim3(elem_grid(npix, C)), dim3(256), 0, (hipStream_t)stream, x, ldx, npix, C, out64);
   HRSEG_LAUNCH_CHECK("absmax");
   return 0;
@@ -1094,7 +1113,7 @@ extern "C" int hrseg_absmax(const float* x, int ldx, long npix, int C, float* ou
 
 extern "C" int hrseg_nchw_to_nhwc(const float* in, float* out, int ldout, int B, int C, int H, int W,
                                   hrseg_stream_t stream) {
-  HRSEG_CHECK_ARG(in && out && B > 0 && C > 0 && ldout >= C, "hrseg_nchw_to_nhwc: bad arguments");
+  HRSEG_CHECK_ARG(in && out && B > 0 && C > 0 && H > 0 && W > 0 && ldout >= C, "hrseg_nchw_to_nhwc: bad arguments");
   const long n = (long)B * H * W;
   hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, in, out, ldout, B,
                      C, (long)H * W);
@@ -1104,7 +1123,7 @@ extern "C" int hrseg_nchw_to_nhwc(const float* in, float* out, int ldout, int B,
 
 extern "C" int hrseg_nhwc_to_nchw(const float* in, int ldin, float* out, int B, int C, int H, int W,
                                   hrseg_stream_t stream) {
-  HRSEG_CHECK_ARG(in && out && B > 0 && C > 0 && ldin >= C, "hrseg_nhwc_to_nchw: bad arguments");
+  HRSEG_CHECK_ARG(in && out && B > 0 && C > 0 && H > 0 && W > 0 && ldin >= C, "hrseg_nhwc_to_nchw: bad arguments");
   const long n = (long)B * H * W;
   hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, in, ldin, out, B,
                      C, (long)H * W);

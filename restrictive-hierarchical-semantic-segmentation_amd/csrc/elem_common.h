@@ -48,3 +48,11 @@ static inline int flat_blocks(long n4) {
   return (int)blocks;
 }
 static inline bool al16(const void* q) { return (uintptr_t)q % 16 == 0; }
+
+// An NHWC operand as the 16-byte accesses of the pixel-lane kernels need it: rows of at least C floats that start on
+// 16-byte boundaries (ld < C overlaps pixels, ld % 4 != 0 or an odd base is a misaligned access on the device)
+static int check_operand(const void* p, int ld, int C, const char* who, const char* what) {
+  HRSEG_CHECK_ARG(ld >= C && ld % 4 == 0, "%s: leading dimension %d of %s must be >= C=%d and a multiple of 4", who, ld, what, C);
+  HRSEG_CHECK_ARG(al16(p), "%s: %s must be 16-byte aligned", who, what);
+  return 0;
+}

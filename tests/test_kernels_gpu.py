@@ -1,7 +1,10 @@
 """The HIP entry points against a plain fp32 torch-CPU reference of the same op (through the
 C ABI, on the GPU), one or a few shapes each.  Tolerances are relative to the reference's max magnitude.
 The sweep over the head / resize / composition / loss / consistency / AdamW kernels' templates, loops and
-flags -- and hrseg_consistency_bwd and hrseg_adamw_dev, which nothing here calls -- is tests/test_headloss_gpu.py."""
+flags -- and hrseg_consistency_bwd and hrseg_adamw_dev, which nothing here calls -- is tests/test_headloss_gpu.py.
+The sweep over the BatchNorm, max pool, bilinear, fuse-sum and glue kernels (every channel mapping, grid-stride trip, chunk
+count, flag and stride, under bounds derived by float64 references) is tests/test_bnelem_gpu.py with tests/bnelem_ref.py,
+tests/test_bnelem_cpu.py and tests/test_bnelem_abi.py."""
 import numpy as np
 import pytest
 import torch
