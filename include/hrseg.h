@@ -179,7 +179,7 @@ int hrseg_conv_wgrad_group_ws(int n, const float* const* x, const float* const* 
  * "label_components" / "filter_components" (post-processing) and "score_boundaries" (boundary scoring, HRSEG_SCORE_BOUNDARIES_LAUNCHES
  * per hrseg_score_boundaries call), "score_instances" (instance scoring) and "score_calibration" (calibration scoring, 1 launch
  * per hrseg_score_calibration call), "decode_hedged" (the hedged decode, 1 launch per hrseg_decode_hedged call) and "mix" (the
- * mixing augmentation, 1 launch per hrseg_mix_* call) and "border_weights" (2 launches per hrseg_border_weights call) are families of their own, outside the NULL total and the convolution
+ * mixing augmentation, 1 launch per hrseg_mix_* call) and "border_weights" (2 launches per hrseg_border_weights call) and "consensus_labels" (1 launch per hrseg_consensus_labels call) are families of their own, outside the NULL total and the convolution
  * counts. */
 long hrseg_launch_count(const char* family, int reset);
 /* tile-plan overrides and A/B switches for the sweep tools under tools/ (value 0 = automatic plan).  Keys: igemm_wtm,
@@ -1238,6 +1238,69 @@ int hrseg_score_calibration(int nlevels, const float* const* z, const int* C, co
                             const float* inv_temp /* HOST [nlevels] */, const unsigned char* gt, const long* gdesc,
                             const unsigned long long* path_lut, int n_bins, long long* hist, long long* ignored,
                             int B, int S, int per_image, hrseg_stream_t stream);
+
+/* ------------------------------------------------------------------ consensus (Data/consensus.py; csrc/consensus.hip)
+ * Several label maps of the same images -> one, voted down the class tree, plus the integer counters every inter-map
+ * agreement figure follows from.  The maps may say less than a leaf per pixel: internal nodes' bytes (hrseg_decode_hedged,
+ * partial labels) and bytes that say nothing at all.
+ *
+ * Inputs.  M member batches, 1 <= M <= HRSEG_CONSENSUS_MAX_MEMBERS.  Each member is a packed uint8 buffer of B ragged maps
+ * in the descriptor format of hrseg_score_labels ([B][4] int64: byte offset, H, W, 1; offsets are arbitrary bytes, gaps are
+ * allowed).  members: HOST array of M DEVICE pointers (like z of the decodes).  desc: ONE DEVICE table [M][B][4], member
+ * m's rows at desc + 4 B m; desc_host its HOST copy (the [2][B][4] pair convention of the scorers, extended to M).  Every
+ * member must give the same H_b x W_b for sample b.  path_lut: DEVICE [256] uint64 in exactly the format of
+ * hrseg_score_labels, INCLUDING entries that end at an internal node (zero bytes below it); the entry rule stated there
+ * applies unchanged.  An entry of 0 (reject byte, ignore byte, foreign byte) means: this member ABSTAINS at this pixel.
+ * The tree, the output bytes and the quorum travel in hrseg_consensus_t (a kernel argument: no device table).
+ *
+ * Per pixel, with e_m the path entry of member m's byte:
+ *   votes[L][c] = the number of members whose byte L of e_m equals c + 1.  A member that names a child has named its
+ *     parent, so votes never grow down a path (no restriction to "members who agreed above" is needed).
+ *   quorum q is an absolute count with 2 q > M and q <= M.  An abstention counts against a node -- deliberately: the
+ *     denominator is M.  Each member names at most one node per level and 2 q > M, so at most one node per level reaches q:
+ *     the nodes that reach q form one chain from a root.
+ *   The CONSENSUS NODE is the deepest node of that chain.  labels[offset + i] = out_val[L][c] of that node (a leaf's pixel
+ *     value, or an internal node's byte); none_val if no level-0 node reaches q.
+ *   support (optional, may be NULL; uint8, packed as labels): the votes of the consensus node, 0 where labels is none_val.
+ * Both outputs are packed as MEMBER 0 is: pixel i of sample b lies at the byte offset of row b of member 0's table.
+ * Worked example, M = 3, q = 2: (tooth, enamel, enamel) -> tooth has 3 votes, enamel 2: enamel.  (enamel, dentin, tooth)
+ * -> tooth 3, enamel 1, dentin 1: the byte of "tooth".  (upper-tooth, lower-tooth, reject) -> no root reaches 2: none_val.
+ *
+ * Counters: DEVICE int64 [per_image ? B : 1][cells], += (a dataset total accumulates in place).  N = sum C nodes in
+ * breadth-first channel order (node = sum_{l<L} C[l] + c), P = M (M - 1) / 2 pairs i < j in lexicographic order.  The cells
+ * of a row, in this order:
+ *   ended    N + 1   pixels whose consensus ended ON each node, then "none"
+ *   votes    N x M   votes[n][k-1] = pixels where exactly k members have node n on their path, k = 1..M (k = 0 follows on
+ *                    the host)
+ *   area     M x N   pixels where member m has node n on its path
+ *   both     P x N   pixels where both members of the pair have node n on their path
+ *   abstain  M       pixels where member m's entry is 0
+ * cells = N + 1 + 2 N M + P N + M <= 2889.  Everything is integer arithmetic: the same bytes in every run, independent of
+ * the block order and of the "deterministic" knob.
+ *
+ * One launch, family "consensus_labels", outside the NULL total.  No workspace, no device allocation, no synchronisation,
+ * no host read.  The kernel never reads outside [offset, offset + H*W) of any member and never writes outside the output
+ * spans.  A block takes HRSEG_CONSENSUS_BLOCK_STEP pixels per step, a lane HRSEG_CONSENSUS_LANE_STEP consecutive ones.
+ * Refused, each before any launch, with -1 and a message that starts with the entry point's name: null required pointers
+ * (members and each of its M entries, desc, desc_host, path_lut, cons, labels, counts); B outside 1..65535; M outside
+ * 1..8; 2 q <= M or q > M; nlevels outside 1..8, a C[L] outside 1..16, sum C > 64; an out_val of an existing node or
+ * none_val outside 0..255, or any two of them equal; a host descriptor row with a negative offset, H < 1, W < 1,
+ * channels != 1 or H * W >= 2^31; members that disagree on a size (the message names the member, the image and both
+ * sizes); counts or path_lut not 8-byte aligned; labels not 4-byte aligned (the rule of the decodes' labels).  Entries of
+ * out_val beyond the tree's channels are not read. */
+#define HRSEG_CONSENSUS_MAX_MEMBERS 8
+#define HRSEG_CONSENSUS_LANE_STEP 16
+#define HRSEG_CONSENSUS_BLOCK_STEP 4096
+typedef struct {
+  int nlevels;
+  int C[HRSEG_SCORE_MAX_LEVELS];                                    /* channels per level */
+  int out_val[HRSEG_SCORE_MAX_LEVELS][HRSEG_SCORE_MAX_CHANNELS];    /* the byte written where the consensus ends ON node (L, c) */
+  int none_val;                                                     /* the byte written where no level-0 node reaches the quorum */
+  int quorum;                                                       /* absolute count: 2 * quorum > M, quorum <= M */
+} hrseg_consensus_t;
+int hrseg_consensus_labels(int M, const unsigned char* const* members, const long* desc, const long* desc_host,
+                           const unsigned long long* path_lut, const hrseg_consensus_t* cons, unsigned char* labels,
+                           unsigned char* support, long long* counts, int B, int per_image, hrseg_stream_t stream);
 
 /* ------------------------------------------------------------------ level synthesis for flat models (evaluation side; csrc/targets.hip)
  * predictEval.py:85-129 get_parent_masks (parent = union of its descendant leaves, "any > 0") and :134-185

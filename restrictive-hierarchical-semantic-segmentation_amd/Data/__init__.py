@@ -9,3 +9,4 @@ from .instances import DeviceInstanceScore, InstanceScores  # noqa: F401
 from .calibration import CalibrationScores, DeviceCalibrationScore  # noqa: F401
 from .hedge import Hedge  # noqa: F401
 from .mix import DeviceMix  # noqa: F401
+from .consensus import ConsensusLabels, DeviceConsensus  # noqa: F401

@@ -71,6 +71,11 @@ class Hedge(C.Structure):
     _fields_ = [("tau", (_f * 16) * 8), ("stop_val", (_i * 16) * 8), ("reject_val", _i)]
 
 
+class Consensus(C.Structure):
+    """hrseg_consensus_t"""
+    _fields_ = [("nlevels", _i), ("C", _i * 8), ("out_val", (_i * 16) * 8), ("none_val", _i), ("quorum", _i)]
+
+
 # name -> argtypes, exactly the prototypes of include/hrseg.h
 PROTOTYPES = {
     "hrseg_conv_fwd_group": [_i, _p, _p, _p, _p, C.POINTER(ConvShape), _p],
@@ -158,6 +163,7 @@ PROTOTYPES = {
     "hrseg_window_crops": [_p, _p, _p, _p, _p, _i, _i, _i, _p],
     "hrseg_decode_windows": [_i, _p, C.POINTER(C.c_int), C.POINTER(DecodeTree), _p, _p, _p, _p, _p, _p, _i, _i, _i, _p],
     "hrseg_score_labels": [_p, _p, _p, _p, _p, _i, C.POINTER(C.c_int), _p, _p, _i, _i, _p],
+    "hrseg_consensus_labels": [_i, _p, _p, _p, _p, C.POINTER(Consensus), _p, _p, _p, _i, _i, _p],
     "hrseg_label_components": [_p, _p, _p, _i, _p, _i, _p, _p, _p],
     "hrseg_filter_components": [_p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p],
     "hrseg_score_boundaries": [_p, _p, _p, _p, _p, _p, _i, C.POINTER(C.c_int), _l, _i, _p, _p, _i, _p],
@@ -270,7 +276,7 @@ def launch_count(family=None, reset=False) -> int:
     under "window_crops" / "decode_windows", the post-processing under "label_components" / "filter_components", the
     boundary scoring under "score_boundaries", the instance scoring's masked copy and scoring launches under
     "score_instances", the calibration scoring under "score_calibration", the hedged decode under "decode_hedged", the mixing augmentation
-    under "mix")"""
+    under "mix", the border weights under "border_weights", the vote over several label maps under "consensus_labels")"""
     return int(_lib.hrseg_launch_count(None if family is None else family.encode(), int(reset)))
 
 

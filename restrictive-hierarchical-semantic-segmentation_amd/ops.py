@@ -1136,6 +1136,112 @@ def score_labels(pred, pdesc, pdesc_host, gt, gdesc, gdesc_host, tables, out=Non
     return counts, ignored
 
 
+CONSENSUS_MAX_MEMBERS = 8           # HRSEG_CONSENSUS_MAX_MEMBERS
+# pixels a lane / a block of hrseg_consensus_labels takes per step (HRSEG_CONSENSUS_*_STEP of include/hrseg.h)
+CONSENSUS_LANE_STEP, CONSENSUS_BLOCK_STEP = 16, 4096
+CONSENSUS_MAX_PIXELS = 1 << 31
+
+
+def consensus_cells(nodes, M):
+    """cells of a row of hrseg_consensus_labels counters, and the first cell of each block:
+    (total, dict(ended, votes, area, both, abstain))"""
+    P = M * (M - 1) // 2
+    first = dict(ended=0, votes=nodes + 1, area=nodes + 1 + nodes * M, both=nodes + 1 + 2 * nodes * M,
+                 abstain=nodes + 1 + 2 * nodes * M + P * nodes)
+    return first["abstain"] + M, first
+
+
+def check_consensus(tables, out_val, none_val, quorum, M):
+    """the rules of hrseg_consensus_labels on its host tables: a Data.score.ScoreTables (check_score_tables), out_val per
+    level and channel and none_val in uint8 and all different, 1 <= M <= 8, 2 * quorum > M and quorum <= M (ValueError
+    otherwise; needs no GPU)"""
+    check_score_tables(tables)
+    if not 1 <= M <= CONSENSUS_MAX_MEMBERS:
+        raise ValueError(f"consensus_labels: {M} members, supported 1..{CONSENSUS_MAX_MEMBERS}")
+    if not (2 * quorum > M and quorum <= M):
+        raise ValueError(f"consensus_labels: quorum {quorum} of {M} members: need 2 * quorum > M and quorum <= M")
+    name = lambda L, c: f"'{tables.names[L][c]}'" if tables.names else f"(level {L}, channel {c})"      # noqa: E731
+    if not 0 <= int(none_val) <= 255:
+        raise ValueError(f"consensus_labels: none value {none_val} not in 0..255")
+    owner = {int(none_val): "the none value"}
+    if len(out_val) != len(tables.C):
+        raise ValueError(f"consensus_labels: out_val has {len(out_val)} levels, the tree {len(tables.C)}")
+    for L, n in enumerate(tables.C):
+        if len(out_val[L]) != n:
+            raise ValueError(f"consensus_labels: out_val of level {L} does not have {n} entries")
+        for c in range(n):
+            v = int(out_val[L][c])
+            if not 0 <= v <= 255:
+                raise ValueError(f"consensus_labels: {name(L, c)} has the output value {v}, not in 0..255")
+            if v in owner:
+                raise ValueError(f"consensus_labels: {owner[v]} and {name(L, c)} share the byte {v}")
+            owner[v] = name(L, c)
+
+
+def _consensus_struct(tables, out_val, none_val, quorum):
+    s = _lib.Consensus()
+    s.nlevels = len(tables.C)
+    for L, n in enumerate(tables.C):
+        s.C[L] = int(n)
+        for c in range(n):
+            s.out_val[L][c] = int(out_val[L][c])
+    s.none_val, s.quorum = int(none_val), int(quorum)
+    return s
+
+
+def consensus_labels(members, tables, out_val, none_val, quorum, per_image=False, counts=None, want_support=False, labels=None,
+                     support=None):
+    """vote M label maps of the same images down the class tree (hrseg_consensus_labels; the semantics are stated in
+    include/hrseg.h under "consensus").  members: list of (buffer, desc, desc_host) triples, packed uint8 device buffers with
+    [B,4] int64 descriptors (device, and their host copies for the checks) of equal (H, W) per sample; tables: a
+    Data.score.ScoreTables whose path table knows the internal nodes' bytes; out_val per level and channel, none_val, quorum
+    -> (labels, support or None, counts [R, cells] int64), R = B (per_image) or 1, the outputs packed as member 0 is (a
+    buffer of member 0's size; bytes outside the spans are not written).  counts = the counters of an earlier call with the
+    same M, batch size and per_image: they are added to.  labels / support: buffers to write into (else allocated).
+    One launch, no synchronisation."""
+    members = list(members)
+    M = len(members)
+    check_consensus(tables, out_val, none_val, quorum, M)
+    rows0 = None
+    for m, (buf, desc, host) in enumerate(members):
+        _check_ragged(buf, desc, host, (1,))
+        if buf.device != members[0][0].device:
+            raise ValueError(f"consensus_labels: member {m} lives on another device than member 0")
+        rows = host.tolist()
+        if m == 0:
+            rows0 = rows
+            if not rows:
+                raise ValueError("consensus_labels: an empty batch")
+        if len(rows) != len(rows0):
+            raise ValueError(f"consensus_labels: member {m} has {len(rows)} maps, member 0 has {len(rows0)}")
+        for b, ((_, H, W, _), (_, H0, W0, _)) in enumerate(zip(rows, rows0)):
+            if (H, W) != (H0, W0):
+                raise ValueError(f"consensus_labels: member {m}, sample {b}: {H}x{W}, member 0 has {H0}x{W0}")
+            if H * W >= CONSENSUS_MAX_PIXELS:
+                raise ValueError(f"consensus_labels: member {m}, sample {b}: {H}x{W} has 2^31 pixels or more")
+    device, n = members[0][0].device, members[0][0].numel()
+    B, R = len(rows0), len(rows0) if per_image else 1
+    total, _ = consensus_cells(sum(tables.C), M)
+    if counts is None:
+        counts = zeros((R, total), torch.int64, device)
+    elif counts.dtype != torch.int64 or not counts.is_cuda or tuple(counts.shape) != (R, total) or not counts.is_contiguous():
+        raise ValueError(f"consensus_labels: counts must be a contiguous int64 device tensor of shape {(R, total)}")
+    outs = []
+    for what, t, wanted in (("labels", labels, True), ("support", support, want_support or support is not None)):
+        if t is None:
+            t = torch.empty(n, dtype=torch.uint8, device=device) if wanted else None
+        elif t.dtype != torch.uint8 or not t.is_cuda or t.dim() != 1 or t.numel() < n or not t.is_contiguous():
+            raise ValueError(f"consensus_labels: {what} must be a contiguous uint8 device buffer of at least {n} bytes")
+        outs.append(t)
+    labels, support = outs
+    host = torch.stack([h.to(torch.int64) for _, _, h in members]).contiguous()          # [M,B,4]
+    desc = host.to(device, non_blocking=True)
+    call("hrseg_consensus_labels", M, _lib.ptr_array([buf for buf, _, _ in members]), ptr(desc), host.data_ptr(),
+         ptr(tables.device_lut(device)), C.byref(_consensus_struct(tables, out_val, none_val, quorum)), ptr(labels), ptr(support),
+         ptr(counts), B, int(bool(per_image)))
+    return labels, support, counts
+
+
 CALIBRATION_MAX_BINS = 32
 
 

@@ -468,6 +468,40 @@ class Predictor:
         return maps if self.postprocess is None else self.postprocess.apply(maps)
 
 
+class EnsemblePredictor:
+    """Several predictors, one answer: `out = EnsemblePredictor(predictors, cons)(images)` runs every member `Predictor` on the
+    batch and votes their label maps down the class tree (Data.DeviceConsensus, one launch) -> ConsensusLabels.  The members
+    may differ in model, `tta`, `window`, `hedge` and `postprocess` -- folds of one recipe, checkpoints of one run, the EMA
+    and the live weights; they share the class tree, and `cons` must know the bytes of every hedged member
+    (`DeviceConsensus.from_hedge(h)`).  The members' own maps of the latest call stay in `last_members`.
+    `scores = ensemble.score(images, labels)` decodes every member at the ground-truth maps' own sizes, votes, and scores the
+    consensus maps against them with a DeviceScore that knows the internal bytes (`cons.scorer`) -> SourceScores; the voted
+    maps of that call stay in `last_labels`.  A pixel without a consensus counts as a prediction outside the class map."""
+
+    def __init__(self, predictors, cons):
+        self.predictors, self.cons = list(predictors), cons
+        if not 1 <= len(self.predictors) <= ops.CONSENSUS_MAX_MEMBERS:
+            raise ValueError(f"EnsemblePredictor: {len(self.predictors)} members, supported 1..{ops.CONSENSUS_MAX_MEMBERS}")
+        for m, p in enumerate(self.predictors):
+            if p.hedge is not None and any(cons.values.get(n) != v for n, v in p.hedge.values.items()):
+                raise ValueError(f"EnsemblePredictor: member {m} writes internal bytes the consensus does not know "
+                                 "(build it with DeviceConsensus.from_hedge)")
+        self.last_members, self.last_labels = None, None
+
+    def _vote(self, images, sizes, per_image, want_support):
+        self.last_members = [p._predict(images, sizes) for p in self.predictors]
+        return self.cons(self.last_members, per_image=per_image, want_support=want_support)
+
+    def __call__(self, images, per_image=False, want_support=False):
+        return self._vote(images, None, per_image, want_support)
+
+    def score(self, images, labels=None, out=None, per_image=True):
+        """images and labels as for Predictor.score -> SourceScores of the consensus maps"""
+        gt = Predictor._ground_truth("EnsemblePredictor.score", images, labels)
+        self.last_labels = self._vote(images, [(H, W) for _, H, W, _ in gt[2].tolist()], False, False)
+        return self.cons.scorer.score(self.last_labels, gt, out, per_image)
+
+
 def write_metrics_csv(path, accuracy, iou, dice, precision, recall, class_metrics):
     """metrics.csv of predict() (predictEval.py:556-573): one "Average" row, one row per class"""
     import csv
@@ -660,6 +694,29 @@ def write_hedge_csv(path, summary):
             wr.writerow([name, summary[name], share(summary[name]), ""])
         for L, c in enumerate(summary["coverage"]):
             wr.writerow([f"coverage@{L}", "", "" if math.isnan(c) else c, ""])
+
+
+def write_consensus_csv(path, summary):
+    """metrics_consensus.csv of a ConsensusLabels.summary(): one "node" row per tree node (pixels ended there, voters, the
+    unanimous share, mean votes, Fleiss' kappa), the "none" row, one "pair" row per member pair and node (both, the two areas,
+    Dice, IoU, fn, fp, agreement), one "member" row per member (its abstained share); empty cells where a figure has no
+    denominator"""
+    import csv
+    blank = lambda v: "" if isinstance(v, float) and math.isnan(v) else v        # noqa: E731
+    with open(path, "w", newline="") as f:
+        wr = csv.writer(f)
+        wr.writerow(["Row", "Name", "Members", "Pixels", "Voters", "Unanimous", "MeanVotes", "Kappa", "Both", "AreaI", "AreaJ", "Dice",
+                     "IoU", "FN", "FP", "Agreement", "Abstained"])
+        for name, r in summary["nodes"].items():
+            wr.writerow(["node", name, "", r["ended"], r["voters"], blank(r["unanimous"]), blank(r["mean_votes"]), blank(r["kappa"])] +
+                        [""] * 9)
+        wr.writerow(["none", "none", "", summary["none"]] + [""] * 13)
+        for (i, j), rows in summary["pairs"].items():
+            for name, r in rows.items():
+                wr.writerow(["pair", name, f"{i}-{j}"] + [""] * 5 + [r["both"], r["area_i"], r["area_j"]] +
+                            [blank(r[k]) for k in ("dice", "iou", "fn", "fp", "agreement")] + [""])
+        for m, a in enumerate(summary["abstained"]):
+            wr.writerow(["member", "", m] + [""] * 13 + [blank(a)])
 
 
 def write_calibration_csv(path, summary):
