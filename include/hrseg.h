@@ -179,7 +179,7 @@ int hrseg_conv_wgrad_group_ws(int n, const float* const* x, const float* const* 
  * "label_components" / "filter_components" (post-processing) and "score_boundaries" (boundary scoring, HRSEG_SCORE_BOUNDARIES_LAUNCHES
  * per hrseg_score_boundaries call), "score_instances" (instance scoring) and "score_calibration" (calibration scoring, 1 launch
  * per hrseg_score_calibration call), "decode_hedged" (the hedged decode, 1 launch per hrseg_decode_hedged call) and "mix" (the
- * mixing augmentation, 1 launch per hrseg_mix_* call) and "border_weights" (2 launches per hrseg_border_weights call) and "consensus_labels" (1 launch per hrseg_consensus_labels call) are families of their own, outside the NULL total and the convolution
+ * mixing augmentation, 1 launch per hrseg_mix_* call) and "border_weights" (2 launches per hrseg_border_weights call) and "consensus_labels" (1 launch per hrseg_consensus_labels call) and "tree_kl" (1 launch per hrseg_tree_kl / hrseg_tree_kl_bwd call) are families of their own, outside the NULL total and the convolution
  * counts. */
 long hrseg_launch_count(const char* family, int reset);
 /* tile-plan overrides and A/B switches for the sweep tools under tools/ (value 0 = automatic plan).  Keys: igemm_wtm,
@@ -575,6 +575,50 @@ int hrseg_loss_partials_pw(const float* z, const float* t, const float* pw, doub
                            float gamma, hrseg_stream_t stream);
 int hrseg_loss_bwd_pw(const float* z, const float* t, const float* pw, const float* coef, const float* g, float* dz,
                       int accumulate, int B, int C, long hw, float gamma, hrseg_stream_t stream);
+/* ---- tree distillation (csrc/distill.hip; Metrics/losses.py TreeDistillation)
+ * A loss that pulls the student's distribution towards a teacher's, level by level: per sibling group the KL between the
+ * teacher's and the student's conditional distribution over the children, weighted by the teacher's composed probability of
+ * the parent (the soft form of the restrictive -1 mask).  With those weights the sum over the levels is the KL between the two
+ * composed leaf distributions (chain rule of KL).
+ *
+ * One level.  z [B,C,hw] fp32 NCHW the student logits, u the teacher logits of the same shape, wprev [B,Cprev,hw] the teacher's
+ * parent probabilities or NULL (every weight is 1; the parents of the group table are not read and Cprev is ignored), pw [B*hw]
+ * one weight per pixel or NULL (1).  The group table is that of hrseg_compose_fwd: consecutive groups, sizes sum to C, C <= 16;
+ * level 0 and flat models pass one group of size C with wprev = NULL.  inv_temp = beta = 1/T, finite and > 0; thresh in [0, 1].
+ * Per pixel i of image b and group g with channels c, everything in fp32, no operation fused with another:
+ *   a_c = beta * u_c,  ma = max_c a_c,  xa_c = a_c - ma,  lq_c = xa_c - log(sum_c exp(xa_c)),  q_c = exp(xa_c) * (1 / sum_c exp(xa_c))
+ *   lp_c, p_c         the same from z
+ *   kl_g = sum_c q_c * (lq_c - lp_c)       a saturated q_c = 0 gives 0 * finite = 0, never 0 * log 0; a group of one gives
+ *                                          exactly 0 and a gradient of exactly 0; u == z gives exactly 0 and 0
+ *   omega_g = wprev[b, parent_g, i] or 1;  m = pw[b*hw + i] or 1
+ *   conf_g = omega_g / sum_c exp(u_c - max_c u_c)      the teacher's composed probability of the group's top child at
+ *                                          temperature 1 whatever beta is: with wprev the model's own composition, the hedged
+ *                                          decode's T_L of a path through this group
+ *   the group is DROPPED iff conf_g < thresh (fp32, <): a NaN conf is never dropped, and thresh = 0 keeps everything and gives
+ *   the bits of the instance without the gate.
+ *   hrseg_tree_kl       out[g][3] (double, +=) = the sums over the kept (pixel, group) pairs of (m * omega_g) * kl_g and of
+ *             m * omega_g, and their number.  Per-thread and per-block sums are fp64; one atomicAdd per block and slot, and under
+ *             the `deterministic` knob one block in all, so two runs give the same bytes.
+ *   hrseg_tree_kl_bwd   dz[b,j,i] (=|+=, `accumulate`) ((g[0] * scale) * (m * omega_g)) * beta * (p_j - q_j) for j in a kept group;
+ *             a dropped group writes exactly 0, or adds nothing when accumulating.  g is a DEVICE scalar, scale comes by value.
+ *             u, wprev and pw get no gradient.  Both calls must be given the same inv_temp and thresh.
+ * Non-finite values.  A NaN among the logits of a kept group, on either side, makes the group's first out slot NaN and dz NaN on
+ * the group's channels at that pixel, whatever m and omega_g are (0 * NaN stays NaN); other pixels and groups are untouched.  A
+ * teacher NaN makes conf_g NaN, so its group is always kept; a student NaN in a group that the gate drops is dropped with it.
+ * Infinite logits, in a group that holds at least one finite logit on that side: a +Inf logit on either side is Inf - Inf = NaN in
+ * xa (resp. the student's), so the first out slot and dz on the group's channels are NaN as for a NaN; conf_g is NaN too (kept).
+ * A -Inf teacher logit has q_c = 0 and lq_c = -Inf: the first out slot is NaN (0 * -Inf), dz stays finite (q_j = 0 there).  A
+ * -Inf student logit has lp_c = -Inf: the first out slot is +Inf where q_c > 0 (NaN where q_c == 0), dz stays finite (p_j = 0).
+ * One launch per call, no workspace, no allocation, no synchronisation; counted under the family "tree_kl" (outside the NULL
+ * total).  Refused (-1, the message starts with the entry point's name) before any launch: a null z, u, out, g or dz, B < 1,
+ * C outside 1..16, hw < 1, a bad group table (the three messages of hrseg_compose_fwd's), wprev set with Cprev outside 1..16 or
+ * a parent outside Cprev, inv_temp not finite or <= 0, thresh outside [0, 1] or NaN. */
+int hrseg_tree_kl(const float* z, const float* u, const float* wprev, const float* pw, float inv_temp, float thresh,
+                  double* out, int B, int C, int Cprev, long hw, int ngroups, const int* group_parent,
+                  const int* group_size, hrseg_stream_t stream);
+int hrseg_tree_kl_bwd(const float* z, const float* u, const float* wprev, const float* pw, float inv_temp, float thresh,
+                      const float* g, float scale, float* dz, int accumulate, int B, int C, int Cprev, long hw,
+                      int ngroups, const int* group_parent, const int* group_size, hrseg_stream_t stream);
 /* per-class metric vectors of nlevels (1..8) levels from their confusion counts in ONE launch: cm[L] (DEVICE, int64
  * [K_L][K_L], (target, predicted) as hrseg_predict_metrics counts them), child[L] != 0: label 0 is the synthetic background
  * of a child level (its row is dropped, its class not reported).  out (DEVICE) receives [5][sum_L (K_L - child_L)] floats:

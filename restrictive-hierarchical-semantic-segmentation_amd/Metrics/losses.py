@@ -353,3 +353,157 @@ def grouped_conditional_kl(z_children_all, probs_prev_level, groups, levels_prev
     if sum(g for _, g in live) != z_children_all.shape[1]:
         raise ValueError("group sizes do not add up to the level's channels")
     return _GroupKL.apply(z_children_all, probs_prev_level, [p for p, _ in live], [g for _, g in live])
+
+
+class _TreeKL(torch.autograd.Function):
+    """(student logits, teacher logits, parent probabilities or None, pixel weights or None, ...) -> scale * sum_g out[g][0] of one
+    level (hrseg_tree_kl), differentiable w.r.t. the student logits only (hrseg_tree_kl_bwd)"""
+
+    @staticmethod
+    def forward(ctx, z, u, wprev, pw, inv_temp, thresh, gp, gs, scale, records):
+        z = z.contiguous()
+        out = ops.tree_kl_fwd(z, u, wprev, pw, inv_temp, thresh, gp, gs)
+        if records is not None:
+            records.append(out)
+        ctx.save_for_backward(z, u)
+        ctx.meta = (wprev, pw, inv_temp, thresh, gp, gs, scale)      # constants of the step: no gradient flows to them
+        return (out[:, 0].sum() * scale).float()
+
+    @staticmethod
+    def backward(ctx, g):
+        z, u = ctx.saved_tensors
+        wprev, pw, inv_temp, thresh, gp, gs, scale = ctx.meta
+        dz = ops.tree_kl_bwd(z, u, wprev, pw, inv_temp, thresh, g.reshape(1).float().contiguous(), scale, gp, gs)
+        return (dz,) + (None,) * 9
+
+
+def _per_level(name, value, n, check):
+    """a scalar or one value per level -> a list of n checked floats"""
+    vals = [value] * n if isinstance(value, (int, float)) else list(value)
+    if len(vals) != n:
+        raise ValueError(f"{name} has {len(vals)} entries, the tree has {n} levels")
+    return [check(name, v) for v in vals]
+
+
+def _temperature(name, v):
+    v = float(v)
+    if not (math.isfinite(v) and v > 0.0 and math.isfinite(1.0 / v)):
+        raise ValueError(f"{name} must be finite and > 0, got {v!r}")
+    return v
+
+
+def _unit_interval(name, v):
+    v = float(v)
+    if not 0.0 <= v <= 1.0:
+        raise ValueError(f"{name} must be in [0, 1], got {v!r}")
+    return v
+
+
+class TreeDistillation(nn.Module):
+    """Tree distillation (include/hrseg.h, "tree distillation"): per level and sibling group the KL between
+    the teacher's and the student's conditional distribution over the children at temperature T, weighted by the teacher's
+    composed probability of the parent (``restrictive=True``; the soft form of the restrictive -1 mask, and with it the levels
+    add up to the KL between the two composed leaf distributions) and kept only where the teacher's confidence
+    omega / sum_c exp(u_c - max u) -- the hedged decode's T_L -- reaches ``thresh`` (the FixMatch threshold; 0 = no gate).
+
+        forward(student_logits, teacher_logits, teacher_probs=None, pixel_weight=None)
+            = sum_L level_weight_L * T_L^2 / (B*H*W) * sum_g out_L[g][0]          (a 0-dim tensor)
+
+    One hrseg_tree_kl launch per level forward and one hrseg_tree_kl_bwd backward: the divisor and T^2 travel in the backward's
+    ``scale``, so there is no finalize launch.  Differentiable w.r.t. the student logits only.
+
+    ``groups``: per level a (group_parent, group_size) pair, or None = one group of all the level's channels (level 0, flat
+    models); a level whose pair is empty is skipped.  ``for_model`` takes them from a model.  ``temperature`` and ``thresh``:
+    scalars or one value per level.  ``restrictive=True`` needs ``teacher_probs``, the probabilities the teacher's forward returns
+    beside its logits: level L >= 1 is weighted by ``teacher_probs[L-1]``.  ``last_records``: the per-level ``out`` tensors
+    ([ngroups,3] float64, on the device; None for a skipped level) of the latest call; ``kept_fraction()`` reads them."""
+
+    def __init__(self, temperature=1.0, thresh=0.0, restrictive=True, level_weights=None, groups=(None,)):
+        super().__init__()
+        self.groups = []
+        for L, g in enumerate(groups):
+            if g is not None:
+                gp, gs = [int(v) for v in g[0]], [int(v) for v in g[1]]
+                if len(gp) != len(gs) or any(v < 1 for v in gs) or any(v < 0 for v in gp) or sum(gs) > 16:
+                    raise ValueError(f"level {L}: bad group table {g!r}")
+                g = (gp, gs)
+            self.groups.append(g)
+        n = len(self.groups)
+        if n < 1:
+            raise ValueError("TreeDistillation needs at least one level")
+        self.temperature = _per_level("temperature", temperature, n, _temperature)
+        self.thresh = _per_level("thresh", thresh, n, _unit_interval)
+        self.restrictive = bool(restrictive)
+        self.level_weights = [1.0] * n if level_weights is None else _per_level("level_weights", level_weights, n, _option)
+        self.last_records = None
+
+    @classmethod
+    def for_model(cls, model, temperature=1.0, thresh=0.0, restrictive=True, level_weights=None):
+        """the groups of ``model.levels`` / ``model.child_groups``: level 0 is one group of its channels, level L >= 1 one group
+        per parent that has children.  A flat model (no ``levels``) gets one level with one group."""
+        groups = [None]
+        if hasattr(model, "levels") and hasattr(model, "child_groups"):
+            for L in range(1, len(model.levels)):
+                live = [(model.levels[L - 1].index(p), len(ch)) for p, ch in model.child_groups[L - 1] if len(ch) > 0]
+                groups.append(([p for p, _ in live], [n for _, n in live]))
+        return cls(temperature, thresh, restrictive, level_weights, groups=groups)
+
+    def kept_fraction(self):
+        """kept (pixel, group) pairs over all pairs of the latest call, per level (None: skipped level, or no call yet).  The
+        one host read: for logging."""
+        if self.last_records is None:
+            return None
+        return [None if r is None else float(r[:, 2].sum().item()) / float(n) for r, n in zip(self.last_records, self._pairs)]
+
+    def forward(self, student_logits, teacher_logits, teacher_probs=None, pixel_weight=None):
+        if isinstance(student_logits, torch.Tensor):
+            student_logits = [student_logits]
+        if isinstance(teacher_logits, torch.Tensor):
+            teacher_logits = [teacher_logits]
+        if isinstance(teacher_probs, torch.Tensor):
+            teacher_probs = [teacher_probs]
+        n = len(self.groups)
+        if len(student_logits) != n or len(teacher_logits) != n:
+            raise ValueError(f"TreeDistillation has {n} levels, got {len(student_logits)} student and {len(teacher_logits)} "
+                             "teacher logit tensors")
+        if self.restrictive and n > 1 and (teacher_probs is None or len(teacher_probs) < n - 1):
+            raise ValueError("restrictive=True needs teacher_probs, the probabilities the teacher's forward returns beside its logits")
+        z0 = student_logits[0]
+        pw = None if pixel_weight is None else _pixel_weight(pixel_weight, z0)
+        records, pairs, total = [], [], None
+        for L in range(n):
+            z, u = student_logits[L], teacher_logits[L]
+            if not isinstance(z, torch.Tensor) or not isinstance(u, torch.Tensor) or z.dim() != 4 or u.shape != z.shape:
+                raise ValueError(f"level {L}: student and teacher logits must be [B,C,H,W] tensors of one shape")
+            if z.shape[0] != z0.shape[0] or z.shape[2:] != z0.shape[2:]:
+                raise ValueError(f"level {L}: logits are {tuple(z.shape)}, level 0 has {tuple(z0.shape)}")
+            if z.dtype != torch.float32 or u.dtype != torch.float32:
+                raise ValueError(f"level {L}: logits must be float32, got {z.dtype} and {u.dtype}")
+            if u.device != z.device or not z.is_cuda:
+                raise ValueError(f"level {L}: student logits are on {z.device}, teacher logits on {u.device}; both must be on one GPU")
+            gp, gs = ([0], [z.shape[1]]) if self.groups[L] is None else self.groups[L]
+            if not gs:
+                records.append(None)
+                pairs.append(0)
+                continue
+            if sum(gs) != z.shape[1]:
+                raise ValueError(f"level {L}: group sizes {gs} do not add up to the logits' {z.shape[1]} channels")
+            wprev = None
+            if self.restrictive and L > 0:
+                wprev = teacher_probs[L - 1]
+                if not isinstance(wprev, torch.Tensor) or wprev.dim() != 4 or wprev.shape[0] != z.shape[0] or \
+                        wprev.shape[2:] != z.shape[2:] or wprev.shape[1] <= max(gp):
+                    raise ValueError(f"level {L}: teacher_probs[{L - 1}] must be [B,Cprev,H,W] with Cprev > {max(gp)} matching the logits")
+                if wprev.dtype != torch.float32 or wprev.device != z.device:
+                    raise ValueError(f"level {L}: teacher_probs[{L - 1}] must be float32 on the logits' device")
+                wprev = wprev.detach().contiguous()
+            T = self.temperature[L]
+            npix = z.shape[0] * z.shape[2] * z.shape[3]
+            lvl = []
+            part = _TreeKL.apply(z, u.detach().contiguous(), wprev, pw, 1.0 / T, self.thresh[L], gp, gs,
+                                 self.level_weights[L] * T * T / npix, lvl)
+            records.append(lvl[0])
+            pairs.append(npix * len(gs))
+            total = part if total is None else total + part
+        self.last_records, self._pairs = records, pairs
+        return z0.sum() * 0 if total is None else total

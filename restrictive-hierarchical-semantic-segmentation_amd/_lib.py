@@ -135,6 +135,8 @@ PROTOTYPES = {
     "hrseg_consistency_bwd": [_p, _p, _p, _f, _p, _p, _i, _i, _i, _l, _i, _p, _p, _p],
     "hrseg_group_kl": [_p, _p, _p, _i, _i, _i, _l, _i, _p, _p, _p],
     "hrseg_group_kl_bwd": [_p, _p, _p, _f, _p, _i, _i, _i, _l, _i, _p, _p, _p],
+    "hrseg_tree_kl": [_p, _p, _p, _p, _f, _f, _p, _i, _i, _i, _l, _i, _p, _p, _p],
+    "hrseg_tree_kl_bwd": [_p, _p, _p, _p, _f, _f, _p, _f, _p, _i, _i, _i, _i, _l, _i, _p, _p, _p],
     "hrseg_predict_metrics": [_p, _p, _p, _p, _i, _i, _l, _i, _i, _p],
     "hrseg_metric_vectors": [_i, _p, _p, _p, _p, _p],
     "hrseg_adamw": [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _f, _f, _f, _p],
@@ -276,7 +278,8 @@ def launch_count(family=None, reset=False) -> int:
     under "window_crops" / "decode_windows", the post-processing under "label_components" / "filter_components", the
     boundary scoring under "score_boundaries", the instance scoring's masked copy and scoring launches under
     "score_instances", the calibration scoring under "score_calibration", the hedged decode under "decode_hedged", the mixing augmentation
-    under "mix", the border weights under "border_weights", the vote over several label maps under "consensus_labels")"""
+    under "mix", the border weights under "border_weights", the vote over several label maps under "consensus_labels", the tree
+    distillation's forward and backward calls under "tree_kl")"""
     return int(_lib.hrseg_launch_count(None if family is None else family.encode(), int(reset)))
 
 

@@ -6,26 +6,7 @@
 // (<= 16), so a thread owns one pixel and walks the C planes (each plane access is coalesced across lanes).
 #include "common.h"
 #include "level_common.h"
-
-struct Groups {
-  int n;
-  int parent[MAXC];
-  int size[MAXC];
-};
-
-static int fill_groups(Groups& g, int ngroups, const int* parent, const int* size, int C, int Cprev, const char* who) {
-  HRSEG_CHECK_ARG(ngroups >= 0 && ngroups <= MAXC && (ngroups == 0 || (parent && size)), "%s: bad group table", who);
-  g.n = ngroups;
-  int tot = 0;
-  for (int i = 0; i < ngroups; ++i) {
-    HRSEG_CHECK_ARG(parent[i] >= 0 && parent[i] < Cprev && size[i] > 0, "%s: group %d out of range", who, i);
-    g.parent[i] = parent[i];
-    g.size[i] = size[i];
-    tot += size[i];
-  }
-  HRSEG_CHECK_ARG(tot == C || ngroups == 0, "%s: group sizes sum to %d, level has %d channels", who, tot, C);
-  return 0;
-}
+#include "group_table.h"      // struct Groups, fill_groups (shared with distill.hip)
 
 // The prelude the six entry points with a group table share, after the null checks of their own pointers: the sizes
 // ("bad arguments"), then the table itself (fill_groups), refused under the entry point's name `who` (a literal).  It reads

@@ -17,7 +17,8 @@
 // "score_calibration" (calibration.hip) the calibration scoring's one launch, "decode_hedged" (decode_hedged.hip) the hedged
 // decode's one launch per call, "mix" (mix.hip) the kernel launches of the mixing augmentation: one per entry point,
 // "border_weights" (border_weight.hip) the two launches of a border weight map: label extraction and search,
-// "consensus_labels" (consensus.hip) the one launch of a vote over several label maps.
+// "consensus_labels" (consensus.hip) the one launch of a vote over several label maps, "tree_kl" (distill.hip) the one launch
+// of a tree distillation call, forward or backward.
 #define HRSEG_FAMILIES(X)                   \
   X(WS, "ws", 1)                            \
   X(WS_GROUP, "ws_group", 1)                \
@@ -54,7 +55,8 @@
   X(DECODE_HEDGED, "decode_hedged", 0)  \
   X(MIX, "mix", 0)  \
   X(BORDER_WEIGHTS, "border_weights", 0)  \
-  X(CONSENSUS_LABELS, "consensus_labels", 0)
+  X(CONSENSUS_LABELS, "consensus_labels", 0)  \
+  X(TREE_KL, "tree_kl", 0)
 #define HRSEG_X(id, name, conv) CNT_##id,
 enum { HRSEG_FAMILIES(HRSEG_X) CNT_N };
 #undef HRSEG_X

@@ -8,6 +8,7 @@ current stream and never synchronises.  torch is used for allocation only.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import NamedTuple
 
@@ -1913,6 +1914,55 @@ def group_kl_bwd(z, pprev, g, scale, group_parent, group_size):
     dz = torch.empty_like(z)
     call("hrseg_group_kl_bwd", ptr(z), ptr(pprev), ptr(g), float(scale), ptr(dz), B, Cn, pprev.shape[1], H * W,
          *_group_args(group_parent, group_size))
+    return dz
+
+
+def _tree_kl_args(who, z, u, wprev, pw, inv_temp, thresh, group_parent, group_size):
+    """shape / dtype / device checks shared by tree_kl_fwd and tree_kl_bwd -> (B, C, Cprev, hw)"""
+    if z.dim() != 4 or u.shape != z.shape:
+        raise ValueError(f"{who}: student and teacher logits must both be [B,C,H,W], got {tuple(z.shape)} and {tuple(u.shape)}")
+    B, Cn, H, W = z.shape
+    for name, t in (("student logits", z), ("teacher logits", u), ("teacher parent probabilities", wprev), ("pixel_weight", pw)):
+        if t is not None and (t.dtype != torch.float32 or t.device != z.device or not t.is_cuda or not t.is_contiguous()):
+            raise ValueError(f"{who}: {name} must be contiguous float32 on the student logits' device (a GPU)")
+    if wprev is not None and (wprev.dim() != 4 or wprev.shape[0] != B or tuple(wprev.shape[2:]) != (H, W)):
+        raise ValueError(f"{who}: teacher parent probabilities must be [{B},Cprev,{H},{W}], got {tuple(wprev.shape)}")
+    if pw is not None and pw.numel() != B * H * W:
+        raise ValueError(f"{who}: pixel_weight must hold {B} x {H} x {W} values, got {tuple(pw.shape)}")
+    if len(group_parent) != len(group_size) or sum(group_size) != Cn:
+        raise ValueError(f"{who}: group sizes {list(group_size)} do not add up to the level's {Cn} channels")
+    if not (math.isfinite(inv_temp) and inv_temp > 0.0):
+        raise ValueError(f"{who}: inv_temp must be finite and > 0, got {inv_temp!r}")
+    if not 0.0 <= thresh <= 1.0:
+        raise ValueError(f"{who}: thresh must be in [0, 1], got {thresh!r}")
+    return B, Cn, (1 if wprev is None else wprev.shape[1]), H * W
+
+
+def tree_kl_fwd(z, u, wprev, pw, inv_temp, thresh, group_parent, group_size, out=None):
+    """-> [ngroups,3] float64: per group the sums over the kept (pixel, group) pairs of m omega kl and of m omega, and their
+    number (hrseg_tree_kl; include/hrseg.h, "tree distillation").  wprev / pw may be None; `out` is added to when given."""
+    inv_temp, thresh = float(inv_temp), float(thresh)
+    B, Cn, Cprev, hw = _tree_kl_args("tree_kl_fwd", z, u, wprev, pw, inv_temp, thresh, group_parent, group_size)
+    if out is None:
+        out = zeros((len(group_size), 3), torch.float64, z.device)
+    call("hrseg_tree_kl", ptr(z), ptr(u), ptr(wprev), ptr(pw), inv_temp, thresh, ptr(out), B, Cn, Cprev, hw,
+         *_group_args(group_parent, group_size))
+    return out
+
+
+def tree_kl_bwd(z, u, wprev, pw, inv_temp, thresh, g, scale, group_parent, group_size, dz=None, accumulate=False):
+    """-> dz (=|+=) g[0] * scale * m omega beta (p - q) on the kept groups (hrseg_tree_kl_bwd); g: a 1-element fp32 device
+    tensor; the same inv_temp and thresh as the forward call"""
+    inv_temp, thresh = float(inv_temp), float(thresh)
+    B, Cn, Cprev, hw = _tree_kl_args("tree_kl_bwd", z, u, wprev, pw, inv_temp, thresh, group_parent, group_size)
+    if dz is None:
+        dz, accumulate = torch.empty_like(z), False
+    elif dz.shape != z.shape or dz.dtype != torch.float32 or dz.device != z.device or not dz.is_contiguous():
+        raise ValueError("tree_kl_bwd: dz must be a contiguous float32 tensor of the logits' shape on their device")
+    if g.dtype != torch.float32 or g.device != z.device or g.numel() < 1:
+        raise ValueError("tree_kl_bwd: g must be a float32 tensor on the logits' device")
+    call("hrseg_tree_kl_bwd", ptr(z), ptr(u), ptr(wprev), ptr(pw), inv_temp, thresh, ptr(g), float(scale), ptr(dz), int(accumulate),
+         B, Cn, Cprev, hw, *_group_args(group_parent, group_size))
     return dz
 
 

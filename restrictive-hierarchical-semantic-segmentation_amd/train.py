@@ -18,6 +18,7 @@ from __future__ import annotations
 import contextlib
 import gc
 import time
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -420,7 +421,7 @@ def _append_metrics(vec, accuracy, IoU, dice, precision, recall, clssMetrics, ho
 # ----------------------------------------------------------------------------- loss
 def get_loss(output_logits, targets, lossFuncts, levelLoss, level_weights=None, loss=0.0, lvlLossGrad=[],
              cur_level=None, cur_epoch=None, pretrain_epoch=None, probs_per_level=None, model=None, *, lambda_kl=None,
-             kl_probs=None, sync_dice=None):
+             kl_probs=None, sync_dice=None, distill=None, teacher=None):
     """reference train.py:111-152.  With this package's loss objects each level is ONE fused
     CE+Dice launch; ``levelLoss`` accumulates 0-dim device tensors (no .item() sync) that
     behave like the reference's floats under ``+`` and ``/``.
@@ -431,7 +432,10 @@ def get_loss(output_logits, targets, lossFuncts, levelLoss, level_weights=None, 
     tiny all-reduce per level).  Default None = only where a gradient is being built (the train step, which every rank
     runs in lock-step); validation (``test()``, under no_grad, possibly on one rank or on shards of unequal length)
     never enters a collective and reports the rank-local loss.  ``levelLoss`` always accumulates the unscaled local
-    CE + Dice."""
+    CE + Dice.
+    ``distill`` (a losses.TreeDistillation) with ``teacher`` (a Teacher record, e.g. from ``ema_teacher``) adds
+    distill(output_logits, teacher.logits, teacher.probs, teacher.pixel_weight), the tree distillation loss over every level
+    whatever the pre-training cap; with None nothing is issued that was not issued before."""
     total_levels = len(output_logits)
     if pretrain_epoch is not None:
         cur_level_cap = int(min(total_levels - 1, (cur_epoch // pretrain_epoch)))
@@ -470,6 +474,10 @@ def get_loss(output_logits, targets, lossFuncts, levelLoss, level_weights=None, 
                 continue
             loss = loss + float(lambda_kl) * losses.grouped_conditional_kl(output_logits[L], gate[L - 1],
                                                                           model.child_groups[L - 1], model.levels[L - 1])
+    if distill is not None:
+        if teacher is None:
+            raise ValueError("get_loss: distill needs a teacher (train.ema_teacher, or any Teacher(probs, logits) record)")
+        loss = loss + distill(output_logits, teacher.logits, teacher.probs, teacher.pixel_weight)
     return loss, lvlLossGrad, levelLoss
 
 
@@ -490,9 +498,37 @@ def _model_call(model, data, args, class_tree):
     return model(data)
 
 
-def train_step(model, optimizer, data, target, lossFuncts, args, class_tree, levelLoss, epoch_num=1):
+class Teacher(NamedTuple):
+    """what a distilled step reads of its teacher: the per-level probabilities and logits of the teacher's forward (lists, one
+    tensor per level; a flat model: lists of one) and an optional [B,H,W] weight per pixel.  Any source of logits will do: a
+    second model, the mean of several, or mix.gather(...) applied to both fields after a ClassMix."""
+    probs: list
+    logits: list
+    pixel_weight: object = None
+
+
+def ema_teacher(model, optimizer, data, args, class_tree):
+    """The averaged weights' opinion on `data`: one forward inside ``optimizer.ema_parameters()``, in eval mode and under
+    no_grad; the model's training flag is put back afterwards.  -> Teacher(probs, logits, pixel_weight=None).
+    The distilled step is the EAGER one (train_step): TapedTrainStep / GraphedTrainStep / train_epoch do not take a teacher,
+    because a teacher forward between two replays swaps the parameter buffer's contents under the persistent weight images
+    of the recorded step (the arena caveat of ADVICE.md item 5); a recorded teacher-plus-student step is the follow-up."""
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad(), optimizer.ema_parameters():
+            probs, logits = _model_call(model, data, args, class_tree)
+    finally:
+        model.train(was_training)
+    if isinstance(logits, torch.Tensor):
+        probs, logits = [probs], [logits]
+    return Teacher([p.detach() for p in probs], [z.detach() for z in logits], None)
+
+
+def train_step(model, optimizer, data, target, lossFuncts, args, class_tree, levelLoss, epoch_num=1, distill=None, teacher=None):
     """One batch of the reference's train loop (train.py:179-246), fully asynchronous:
-    returns (loss tensor, per-level confusion matrices)."""
+    returns (loss tensor, per-level confusion matrices).  ``distill`` / ``teacher``: passed on to get_loss (the tree
+    distillation loss; this eager step is the distilled step, see ema_teacher); None issues exactly what it always did."""
     targets = split_targets(target, args)
     optimizer.zero_grad()
     _, output_logits = _model_call(model, data, args, class_tree)
@@ -506,7 +542,7 @@ def train_step(model, optimizer, data, target, lossFuncts, args, class_tree, lev
     probs_per_level = output_class if args.model_type == 1 else None
     loss, _, levelLoss = get_loss(output_logits, targets, lossFuncts, levelLoss, args.level_weights, 0.0, [],
                                   cur_epoch=epoch_num, pretrain_epoch=args.level0_pretrain_epochs,
-                                  probs_per_level=probs_per_level, model=_unwrap(model))
+                                  probs_per_level=probs_per_level, model=_unwrap(model), distill=distill, teacher=teacher)
     loss.backward()
     optimizer.step()
     return loss.detach(), cms
